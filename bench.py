@@ -6,7 +6,7 @@ Metric (BASELINE.json): AuxIVA iterations/sec at 2048 bins x 4000 frames x 8 mic
 loop body reference overiva.py:138-190; prologue and epilogue are outside the timed region and X is
 resident in HBM when it starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1 shards the 2048 bins over the ranks (strong scaling: the problem is fixed) with one RCCL
@@ -182,10 +182,12 @@ def _median(v):
 _PRE_PASS_STEPS = 0
 
 
-def _time_plan(plan, args, repeats=0):
+def _time_plan(plan, args, repeats=0, outputs=None):
     """W untimed warm-up iterations, then exactly K timed ones bracketed by synchronisation (the contract measurement);
     then `repeats` more measurements of the same K iterations (for the median); then the same K again with every kernel
-    bracketed by HIP events on the plan's stream"""
+    bracketed by HIP events on the plan's stream.  With `outputs` (a dict, --dump-outputs) the demixing matrices start
+    again from the identity after the pre-pass, and outputs["W"] receives them as the K-th timed step left them: W + K
+    iterations from the identity, whatever the length of the pre-pass"""
     import torch
 
     # (an untimed pass first: the first replay of the captured graphs and the clock ramp of a GPU that was idle -- the box has
@@ -202,6 +204,8 @@ def _time_plan(plan, args, repeats=0):
         plan.sync()
         n_pre += args.steps
     _PRE_PASS_STEPS = n_pre
+    if outputs is not None:
+        plan.set_w(None)
     plan.iterate(args.warmup)
     plan.sync()
     torch.cuda.synchronize()
@@ -210,6 +214,8 @@ def _time_plan(plan, args, repeats=0):
     plan.sync()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if outputs is not None:
+        outputs["W"] = plan.get_w(np.complex128)     # (exact in `fast` too: its float32 state widened)
     more = []
     for _ in range(repeats):
         t0 = time.perf_counter()
@@ -543,8 +549,10 @@ def run_single(args):
                                 "stage_ms_per_step": {k: v / args.steps for k, v in stages2.items()},
                                 "roofline": {k: roof2[k] for k in ("bound", "kernel", "achieved", "unit", "frac")}})
     plan = _make_plan(oa, X, shape, args.precision, args.graph)
-    dt, total_ms, stages, more = _time_plan(plan, args, repeats=args.repeats)
+    outputs = {} if args.dump_outputs else None
+    dt, total_ms, stages, more = _time_plan(plan, args, repeats=args.repeats, outputs=outputs)
     pre_pass = _PRE_PASS_STEPS
+    dumped = dump_outputs(args.dump_outputs, outputs) if args.dump_outputs else None
     W = plan.get_w()
     assert np.all(np.isfinite(W))
     splits = plan.cov_splits()
@@ -575,6 +583,8 @@ def run_single(args):
     roofline.update({"stage_ms_per_step": per_step, "event_timed_ms_per_step": total_ms / args.steps, "cov_splits": splits})
     out = result_line(args, 1, dt)
     out["untimed_pre_pass_steps"] = pre_pass        # (see _time_plan: >= 50 ms of untimed iterations in front of the W warm-up steps)
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "iterations_from_identity": args.warmup + args.steps, "arrays": dumped}
     if digests is not None:
         out["w_digest_shards"] = {"iterations": args.w_digest, "shards": args.digest_shards, "sha256_16": digests}
     if more:
@@ -923,6 +933,27 @@ def run_sharded(args):
     return out if rank == 0 else None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, a complex one as float (..., 2) = (real, imaginary) of the same
+    precision; at most DUMP_LIMIT_BYTES in all.  Returns {name: {"shape", "dtype"}} of what was written."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in conv.items()}
+
+
 def result_line(args, n_gpus, seconds):
     return {
         "metric": f"AuxIVA iterations/sec ({F} bins x {T} frames x {M} mics)",
@@ -1075,6 +1106,10 @@ def main():
                          "equal shards through the four-launch path give the bits of one GPU")
     ap.add_argument("--digest-shards", type=int, default=1)
     ap.add_argument("--w-dump", default=None, metavar="DIR", help="with --w-digest: also save those matrices as DIR/w_rank<r>of<N>.npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="single GPU: after the timed steps save what they computed -- the demixing matrices W (F, M, K) as "
+                         "DIR/W.npy, float64 (F, M, K, 2) = (real, imaginary).  The warm-up and timed steps then start from the "
+                         "identity after the untimed pre-pass, so that equal arguments give equal inputs and equal iteration counts")
     ap.add_argument("--launch-timeout", type=int, default=600,
                     help="seconds a sharded run may take before its watchdog ends it with a non-zero exit code")
     ap.add_argument("--launch-grace", type=int, default=60, help=argparse.SUPPRESS)
@@ -1083,6 +1118,8 @@ def main():
     if args.precision is None:
         args.precision = "mixed"      # overiva_amd.overiva.resolve_precision for complex64 input
     world_env = int(os.environ.get("WORLD_SIZE", "0") or 0)
+    if args.dump_outputs and (args.gpus > 1 or world_env > 1 or args.force_sharded):
+        ap.error("--dump-outputs is for the single-GPU run (--gpus 1)")
     if args.gpus > 1 and world_env == 0:
         # no launcher around us: be one.  Nothing above touched a GPU (no torch import, no HIP call).
         sys.exit(launch_ranks(args, sys.argv[1:]))

@@ -164,7 +164,10 @@ def make_exchange(engine, dist, group, rank, world, p_local, p_all, prefer=None)
                 # iterations would have hung exactly there.
                 flat.copy_((torch.arange(n, device=p_local.device, dtype=torch.float32) % 251) + 1000.0 * rank + 7)
                 engine.stream.synchronize()
-                side = torch.cuda.Stream(device=p_local.device)
+                # (the side stream has another priority than the waiting one: HIP keeps one pool of hardware queues per
+                #  priority, and in a process with more streams than queues a stream of the SAME priority may share the
+                #  waiting stream's queue -- its push would then sit behind the very wait it is meant to release)
+                side = torch.cuda.Stream(device=p_local.device, priority=0 if engine.stream.priority < 0 else -1)
                 x.epoch += 1
                 x.wait()
                 done = torch.cuda.Event()

@@ -83,3 +83,36 @@ def test_launcher_retries_a_failed_push_attempt_with_the_collective(tmp_path, ca
     d = json.loads(lines[-1])
     assert rc == 0 and d["exchange"] == "collective"
     assert [a["exchange"] for a in d["launcher"]["attempts"]] == ["push", "collective"] and d["launcher"]["attempts"][0]["returncode"] != 0
+
+
+# ---- --dump-outputs ----------------------------------------------------------------------------------------------------
+def test_dump_outputs_writes_real_arrays_of_the_same_precision(tmp_path):
+    import numpy as np
+
+    rng = np.random.default_rng(3)
+    W = rng.standard_normal((5, 4, 2)) + 1j * rng.standard_normal((5, 4, 2))
+    info = bench.dump_outputs(str(tmp_path / "out"), {"W": W, "W32": W.astype(np.complex64)})
+    got = np.load(tmp_path / "out" / "W.npy")
+    assert got.dtype == np.float64 and got.shape == (5, 4, 2, 2) and np.array_equal(got[..., 0] + 1j * got[..., 1], W)
+    got32 = np.load(tmp_path / "out" / "W32.npy")
+    assert got32.dtype == np.float32 and np.array_equal(got32[..., 0] + 1j * got32[..., 1], W.astype(np.complex64))
+    assert info == {"W": {"shape": [5, 4, 2, 2], "dtype": "float64"}, "W32": {"shape": [5, 4, 2, 2], "dtype": "float32"}}
+
+
+def test_dump_outputs_refuses_more_than_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import pytest
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1000)
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "out"), {"W": np.zeros(100, np.complex128)})
+    assert not (tmp_path / "out").exists()
+
+
+def test_dump_outputs_is_refused_for_a_sharded_run(tmp_path):
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, bench.__file__, "--gpus", "2", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and not (tmp_path / "out").exists()

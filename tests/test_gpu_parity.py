@@ -8,7 +8,8 @@ STFT input; the distance is ||a-b||_F / ||b||_F.
   - complex128 input (``precise``: float64 covariance accumulation and per-bin algebra on complex64-rounded data), against
     the reference's complex128 result: ``1e-5``, scaled by ``amp / 10`` only where the reference itself amplifies rounding
     by more than 10 (fixture key ``amp_*`` = measured amplification of a relative input perturbation in the reference,
-    tests/golden/make_golden.py); nothing is compared where it is chaotic (amp > 1e3, conftest.chaotic);
+    tests/golden/make_golden.py); where it is chaotic (amp > 1e3, conftest.chaotic) no value is compared, the run must give
+    the same bits twice (_same_twice);
   - complex64 input: on frame axes up to 256 long with up to 8 channels ``auto`` runs ``precise`` too (round 6: the reference
     forms those covariances in complex128 as well, overiva.py:179), except where the X-resident kernel keeps ``mixed`` (2, 6, 8
     channels with 1-2 sources); elsewhere ``mixed`` (float32 products and lane chains, float64 sums and per-bin algebra) --
@@ -58,6 +59,25 @@ def _log(**row):
     if path:
         with open(path, "a") as f:
             f.write(json.dumps(row) + "\n")
+
+
+def _same_twice(run):
+    """where the reference itself is chaotic (conftest.chaotic) or its own complex64 arithmetic is, no value can be pinned on
+    the result.  What still holds there: the GPU path is deterministic -- the same call twice returns the same bits, all
+    finite (or raises the same LinAlgError twice: a singular solve, as numpy.linalg.solve raises in the reference).
+    Returns the arrays of the first call, or None when it raised."""
+    outs = []
+    for _ in range(2):
+        try:
+            outs.append(tuple(np.array(a) for a in run()))
+        except np.linalg.LinAlgError:
+            outs.append(None)
+    a, b = outs
+    assert (a is None) == (b is None), "one call raised LinAlgError and the other did not"
+    if a is not None:
+        assert all(np.all(np.isfinite(x)) for x in a)
+        assert all(np.array_equal(x, y) for x, y in zip(a, b))
+    return a
 
 
 def _c64_floor(fn_ref64, ref128):
@@ -349,11 +369,13 @@ def _demix(X, W):
 @pytest.mark.parametrize("n_iter", [0, 1, 2, 5, 20])
 @pytest.mark.parametrize("dt", ["c64", "c128"])
 def test_overiva_matches_reference(oa, golden, model, n_iter, dt):
-    """default arithmetic against the real reference's stored results"""
-    if chaotic(golden, model, n_iter):
-        pytest.skip("reference is ill-conditioned here (see conftest.chaotic)")
+    """default arithmetic against the real reference's stored results (where the reference is chaotic: the same bits twice)"""
     X, K = golden["X"], int(golden["K"])
     Xin = X if dt == "c64" else X.astype(np.complex128)
+    if chaotic(golden, model, n_iter):
+        out = _same_twice(lambda: oa.overiva(Xin, n_src=K, n_iter=n_iter, proj_back=False, model=model, return_filters=True))
+        assert out is None or (out[0].dtype == Xin.dtype and out[1].shape == (X.shape[1], X.shape[2], K))
+        return
     Y, W = oa.overiva(Xin, n_src=K, n_iter=n_iter, proj_back=False, model=model, return_filters=True)
     assert Y.dtype == Xin.dtype and W.dtype == Xin.dtype
     assert Y.shape == (X.shape[0], X.shape[1], K) and W.shape == (X.shape[1], X.shape[2], K)
@@ -393,10 +415,12 @@ def test_overiva_matches_reference(oa, golden, model, n_iter, dt):
 @pytest.mark.parametrize("model", ["laplace", "gauss"])
 @pytest.mark.parametrize("n_iter", [1, 5, 20])
 def test_fast_mode_accuracy(oa, golden, fast_mode, model, n_iter):
-    """the float32 mode: 1e-5 where the reference is well conditioned, a documented envelope elsewhere"""
-    if chaotic(golden, model, n_iter):
-        pytest.skip("reference is ill-conditioned here (see conftest.chaotic)")
+    """the float32 mode: 1e-5 where the reference is well conditioned, a documented envelope elsewhere (where the reference is
+    chaotic: the same bits twice)"""
     X, K = golden["X"], int(golden["K"])
+    if chaotic(golden, model, n_iter):
+        _same_twice(lambda: oa.overiva(X, n_src=K, n_iter=n_iter, proj_back=False, model=model, return_filters=True))
+        return
     _, W = oa.overiva(X, n_src=K, n_iter=n_iter, proj_back=False, model=model, return_filters=True)
     ref128 = golden[f"W_c128_{model}_{n_iter}"]
     floor = orc.rel_err(golden[f"W_c64_{model}_{n_iter}"], ref128)
@@ -411,9 +435,15 @@ def test_fast_mode_accuracy(oa, golden, fast_mode, model, n_iter):
 @pytest.mark.needs('Ypb_c128_{model}_12')
 @pytest.mark.parametrize("model", ["laplace", "gauss"])
 def test_proj_back_and_callback(oa, golden, model):
-    if chaotic(golden, model, 12):
-        pytest.skip("reference is ill-conditioned here (see conftest.chaotic)")
     X, K = golden["X"], int(golden["K"])
+    if chaotic(golden, model, 12):        # (the reference is chaotic here: the same bits twice, callbacks included)
+        def run():
+            seen = []
+            Y = oa.overiva(X.astype(np.complex128), n_src=K, n_iter=12, proj_back=True, model=model, callback=lambda y: seen.append(np.array(y)))
+            assert len(seen) == 2
+            return (Y, *seen)
+        _same_twice(run)
+        return
     got = []
     Y = oa.overiva(X.astype(np.complex128), n_src=K, n_iter=12, proj_back=True, model=model,
                    callback=lambda y: got.append(np.array(y)))
@@ -562,7 +592,13 @@ def test_odd_shapes_against_oracle(oa, shape, model):
         # nothing to pin where that arithmetic is itself chaotic
         floor = _c64_floor(lambda: orc.overiva_faithful(X, n_src=K, n_iter=4, proj_back=True, model=model, return_filters=True)[1], Wr)
         if not floor < 1e-2:
-            pytest.skip(f"the reference's complex64 arithmetic is chaotic here (floor {floor:.1e}), ours {eW:.1e}")
+            # nothing to pin on the complex64 result: the call gives the same bits (or the same error) twice, and complex128
+            # input, which runs `precise`, still reaches the complex128 result
+            print(f"\n[parity] T{T} F{F} M{M} K{K} {model}: reference complex64 arithmetic chaotic (floor {floor:.1e}), ours {eW:.1e}")
+            _same_twice(lambda: oa.overiva(X, n_src=K, n_iter=4, proj_back=True, model=model, return_filters=True))
+            Y, W = oa.overiva(X.astype(np.complex128), n_src=K, n_iter=4, proj_back=True, model=model, return_filters=True)
+            assert orc.rel_err(W, Wr) < TOL and orc.rel_err(Y, Yr) < 2 * TOL
+            return
         bound = max(TOL, 1.5 * floor)       # the same 1.5 floors test_overiva_matches_reference allows complex64 input
     _log(test="odd_shape", fixture=f"T{T}F{F}M{M}K{K}", model=model, n_iter=4, input="c64", mode=mode, W_vs_c128=eW,
          Y_vs_c128=eY)
