@@ -36,9 +36,10 @@ extern "C" {
 #define OIVA_MODEL_LAPLACE 0   /* overiva.py:152-153, :161-163 */
 #define OIVA_MODEL_GAUSS 1     /* overiva.py:154-155, :164-167 */
 
-/* Documented limit (the reference has none): at most 16 channels.  Every shape in BASELINE.json and in the
- * reference's overiva_sim_config.json has <= 16; oiva_plan_create rejects more with OIVA_ERR_ARG. */
-#define OIVA_MAX_CHANNELS 16
+/* Documented limit (the reference has none): at most 32 channels.  1..16 channels run the kernels tuned per shape; 17..32
+ * run one generic wide path (kernels_wide.hip), selected by the channel count alone.  oiva_plan_create rejects more with
+ * OIVA_ERR_ARG. */
+#define OIVA_MAX_CHANNELS 32
 
 /* Arithmetic of a plan (oiva_plan_set_precision).  Device data (X, Y, the W the streaming kernels read) is always
  * complex64; these bits choose where float64 is used on top of it.

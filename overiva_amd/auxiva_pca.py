@@ -26,6 +26,7 @@ def auxiva_pca(X, n_src=None, **kwargs):
     X = np.asarray(X)
     dtype = _ov._complex_dtype(X)
     n_frames, n_freq, n_chan = X.shape
+    _ov.check_channels(n_chan, what="auxiva_pca")
     if n_src is None:
         n_src = n_chan
     kwargs.pop("proj_back")                                                   # auxiva_pca.py:86

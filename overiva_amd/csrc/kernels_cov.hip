@@ -419,7 +419,7 @@ hipError_t dispatch_cov(int M, int kc, bool unit, Fn&& fn) {
 
 }  // namespace
 
-bool cov_supported(int M) { return M >= 1 && M <= OIVA_MAX_CHANNELS; }
+bool cov_supported(int M) { return M >= 1 && M <= kWideMax; }
 
 // sources handled per pass over X
 int cov_sources_per_pass(int M, int K, bool f64, bool short_axis) {
@@ -459,6 +459,7 @@ hipError_t launch_pad_channels(hipStream_t s, const float2* X, float2* Xpad, lon
 
 hipError_t launch_cov(hipStream_t s, const float2* X, const float2* Xpad, const float* R, float* Wt, float* wscale, int model, int raw,
                       void* Vpart, bool f64, int T, int F, int M, int K, const CovGeom& g) {
+    if (M > kNarrowMax) return launch_cov_wide(s, X, R, Wt, wscale, model, raw, static_cast<double*>(Vpart), T, F, M, K, g);
     if (g.pad && Xpad == nullptr) return hipErrorInvalidValue;
     const float2* Xv = g.pad ? Xpad : X;        // what the vector-ALU kernels of 10..16 channels read, at a pitch of Mp channels
     const int Mp = g.pad ? M + 1 : M;

@@ -22,7 +22,7 @@ namespace {
 //  column k of the table each: strided 4-byte stores and loads from 16 CUs into the same lines, 4 + 5 -> 17 us at 8 channels /
 //  2 sources in float64, 7 + 7 -> 50 at 16 / 16, equal (9.7 against 10.0) at 235 frames.  gamma needs every block of a source, so a
 //  row-major split would have to wait inside the kernel.)
-constexpr int kMaxK = OIVA_MAX_CHANNELS;
+constexpr int kMaxK = kNarrowMax;
 __global__ __launch_bounds__(kBlock) void weights_kernel(const float* __restrict__ R, float* __restrict__ Wt,
                                                          float* __restrict__ wscale, int model, int raw, int T, int K,
                                                          int Kp) {

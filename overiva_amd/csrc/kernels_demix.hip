@@ -267,6 +267,7 @@ hipError_t pow_blocks_per_cu(int M, int kp, int tcp, int* n) {
 
 hipError_t launch_power(hipStream_t s, const float2* X, const float2* Xpad, const float2* What, float* Ppart, int T, int F, int M,
                         int K, const PowGeom& g) {
+    if (M > kNarrowMax) return launch_power_wide(s, X, What, Ppart, T, F, M, K, g);
     // more than 4 sources would take several VALU passes over X (register budget): one MFMA pass instead
     // (measured at 16 channels: 16 sources 770 -> 325 us; 2 sources 191 us VALU vs 332 us MFMA); an odd channel count
     // reads the copy of X padded by one zero channel (16-byte loads instead of 8-byte ones)
@@ -282,6 +283,7 @@ hipError_t launch_power(hipStream_t s, const float2* X, const float2* Xpad, cons
 
 hipError_t launch_demix_stats(hipStream_t s, const float2* X, const float2* What, float* Spart, int T, int F, int M,
                               int K, const CovGeom& g) {
+    if (M > kNarrowMax) return launch_demix_stats_wide(s, X, What, Spart, T, F, M, K, g);
 #define CALL(MM) return launch_stats_one<MM, 2>(s, X, What, Spart, T, F, K, g);
     OIVA_DISPATCH_M(CALL)
 #undef CALL
@@ -290,6 +292,7 @@ hipError_t launch_demix_stats(hipStream_t s, const float2* X, const float2* What
 
 hipError_t launch_demix_write(hipStream_t s, const float2* X, const float2* What, const float* Spart, int nsplit,
                               float2* Y, int T, int F, int M, int K) {
+    if (M > kNarrowMax) return launch_demix_write_wide(s, X, What, Spart, nsplit, Y, T, F, M, K);
 #define CALL(MM) return launch_write_one<MM, 2>(s, X, What, Spart, nsplit, Y, T, F, K);
     OIVA_DISPATCH_M(CALL)
 #undef CALL

@@ -15,8 +15,6 @@
 namespace oiva {
 namespace {
 
-constexpr int NMAX = OIVA_MAX_CHANNELS;
-
 struct Zd {
     double re, im;
 };
@@ -40,6 +38,8 @@ __device__ __forceinline__ void pair_of(int n, int r, int k, int& p, int& q) {
 // lapack_phase: the convention of LAPACK's zgeev, which numpy.linalg.eig -- the call of the reference's init_eig,
 // overiva.py:106-109 -- inherits: every eigenvector is scaled by a phase that makes its largest component real (and
 // positive); W = conj(vecs) as the reference stores it.  Without it the vectors keep the Jacobi rotations' phases.
+// NMAX: the largest M of the instantiation (kNarrowMax; kWideMax for the wide path, 50 KB of LDS)
+template <int NMAX>
 __global__ __launch_bounds__(64) void pca_subspace_kernel(const double* __restrict__ Cx, float2* __restrict__ What,
                                                           double2* __restrict__ What64, double* __restrict__ evals, int F, int M,
                                                           int K, int lapack_phase) {
@@ -197,7 +197,11 @@ __global__ __launch_bounds__(64) void pca_subspace_kernel(const double* __restri
 
 hipError_t launch_pca_subspace(hipStream_t s, const double* Cx, float2* What, double2* What64, double* evals, int F, int M, int K,
                                bool lapack_phase) {
-    hipLaunchKernelGGL(pca_subspace_kernel, dim3(F), dim3(64), 0, s, Cx, What, What64, evals, F, M, K, lapack_phase ? 1 : 0);
+    if (M > kWideMax) return hipErrorInvalidValue;
+    if (M > kNarrowMax)
+        hipLaunchKernelGGL(pca_subspace_kernel<kWideMax>, dim3(F), dim3(64), 0, s, Cx, What, What64, evals, F, M, K, lapack_phase ? 1 : 0);
+    else
+        hipLaunchKernelGGL(pca_subspace_kernel<kNarrowMax>, dim3(F), dim3(64), 0, s, Cx, What, What64, evals, F, M, K, lapack_phase ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -16,7 +16,7 @@
 namespace oiva {
 namespace {
 
-constexpr int MX = OIVA_MAX_CHANNELS;
+constexpr int MX = kNarrowMax;      // (OGIVE: 1..16 channels)
 
 struct Z {
     double re, im;

@@ -736,6 +736,7 @@ hipError_t launch_sg(hipStream_t s, const UpdateArgs& a) {
 }  // namespace
 
 hipError_t launch_update(hipStream_t s, const UpdateArgs& a) {
+    if (a.M > kNarrowMax) return launch_update_wide(s, a);      // (either layout: the matrices live in LDS)
     if (a.layout == 0) {  // square layout: one lane per matrix element
         if (a.M <= 2) return launch_sq<2>(s, a);
         if (a.M <= 4) return launch_sq<4>(s, a);

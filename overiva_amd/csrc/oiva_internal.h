@@ -9,6 +9,11 @@
 
 namespace oiva {
 
+// channel counts of the kernels tuned per shape (1..kNarrowMax: register arrays sized by it) and of the generic wide path
+// (kNarrowMax + 1 .. kWideMax = OIVA_MAX_CHANNELS, kernels_wide.hip), chosen by the channel count alone
+constexpr int kNarrowMax = 16;
+constexpr int kWideMax = OIVA_MAX_CHANNELS;
+
 // records the thread-local message oiva_last_error() returns and hands back `code` (defined in plan.hip)
 int fail_with(int code, const std::string& msg);
 // exchange.hip: rank / world / slot size and every rank's gather buffer as mapped in this process; -1 unless connected
@@ -294,6 +299,21 @@ hipError_t launch_ogive_step(hipStream_t s, const OgiveState& st, const void* Vp
 // ascending or nullptr; lapack_phase: W = conj(vecs) with every vector's largest component real (overiva.py:106-109)
 hipError_t launch_pca_subspace(hipStream_t s, const double* Cx, float2* What, double2* What64, double* evals, int F, int M, int K,
                                bool lapack_phase);
+
+// The wide path, 17..32 channels (kernels_wide.hip): the launchers above hand over to these for M > kNarrowMax.  Same buffer
+// layouts as the narrow kernels (Vpart always float64).
+bool wide_channels(int M);
+int wide_cov_sources_per_pass(int K);
+int wide_pow_sources_per_pass(int K);
+//   covariance: float64 sums of exact float64 products whatever the arithmetic mode; Wt: (T, K) doubles of scratch
+hipError_t launch_cov_wide(hipStream_t s, const float2* X, const float* R, void* Wt, float* wscale, int model, int raw, double* Vpart,
+                           int T, int F, int M, int K, const CovGeom& g);
+hipError_t launch_power_wide(hipStream_t s, const float2* X, const float2* What, float* Ppart, int T, int F, int M, int K, const PowGeom& g);
+hipError_t launch_demix_stats_wide(hipStream_t s, const float2* X, const float2* What, float* Spart, int T, int F, int M, int K,
+                                   const CovGeom& g);
+hipError_t launch_demix_write_wide(hipStream_t s, const float2* X, const float2* What, const float* Spart, int nsplit, float2* Y, int T,
+                                   int F, int M, int K);
+hipError_t launch_update_wide(hipStream_t s, const UpdateArgs& a);
 
 // dense complex128 <-> complex64 conversion on the device
 hipError_t launch_cast_c128_to_c64(hipStream_t s, const double2* in, float2* out, long long n);

@@ -158,6 +158,7 @@ struct oiva_plan {
     float* Ppart = nullptr;     // [nb (or more, zero padded)][T][K]
     int ppart_alloc = 0;
     float* Plocal = nullptr;    // (T,K)
+    void* Wwide = nullptr;      // 17..32 channels: (T, K) float64 final weights of the covariance pass
     float* R = nullptr;         // (T,K)
     float* wscale = nullptr;    // (K)
     float* Spart = nullptr;     // [nsplit][F][K][3]
@@ -185,7 +186,7 @@ struct oiva_plan {
     // chains across lanes in float64 and store float64 partials; the 9..16-channel matrix-core kernel stores its
     // accumulator type
     bool vpart_f64() const { return vpart_f64_of(cov); }
-    bool vpart_f64_of(const CovGeom& g) const { return cov_f64() || M <= 8 || g.quad || (g.half16 && !g.part32); }
+    bool vpart_f64_of(const CovGeom& g) const { return cov_f64() || M <= 8 || M > kNarrowMax || g.quad || (g.half16 && !g.part32); }
     int use_graph = 0;
     // OGIVE (ive.py): per-bin state, allocated by oiva_plan_ogive_begin
     OgiveState og{};
@@ -266,6 +267,24 @@ int mixed_min_splits(int capacity, int blocks_per_split, int T) {
 
 void choose_cov_geom(oiva_plan* p, int nsplit_req) {
     CovGeom g;
+    if (p->M > kNarrowMax) {
+        // 17..32 channels (kernels_wide.hip): one workgroup per (bin, split, pass of sources), float64 sums in every mode;
+        // splits only to fill the chip with two workgroups per CU
+        g.kc = wide_cov_sources_per_pass(p->K);
+        g.nbg = p->F;
+        int nsplit = nsplit_req;
+        if (nsplit <= 0) {
+            // (counted on F_total, not on this plan's bins: every rank of a bin-sharded run then groups the frames of a bin
+            //  into the same splits as one plan over all bins does, and its float64 partials add up to the same bits)
+            const int groups = p->F_total * ceil_div(p->K, g.kc);
+            nsplit = 1;
+            while (groups * nsplit < 2 * p->n_cu && ceil_div(p->T, nsplit + 1) >= 128) ++nsplit;
+        }
+        g.tc = round_up(ceil_div(p->T, nsplit), 4);
+        g.nsplit = ceil_div(p->T, g.tc);
+        p->cov = g;
+        return;
+    }
     // float64, 8 channels: two lanes per (bin, frame), 32 bins per workgroup (kernels_cov_pair64.hip); else 16 bins
     // (same geometry, float32: 8 channels with three or more sources, four per pass -- kernels_cov_pair32.hip)
     g.pair32 = !p->cov_f64() && cov_pair32_supported(p->M, p->K);
@@ -389,6 +408,16 @@ void choose_cov_geom(oiva_plan* p, int nsplit_req) {
 
 void choose_stats_geom(oiva_plan* p) {
     CovGeom g;
+    if (p->M > kNarrowMax) {
+        // 17..32 channels: frame splits counted on F_total (as the covariance's above: the same partial sums on every rank)
+        g.nbg = ceil_div(p->F_total, 64);
+        g.kc = 2;
+        const int nsplit = std::min(16, pick_splits(p->n_cu * 4, g.nbg * ceil_div(p->K, g.kc), p->T, 128));
+        g.tc = round_up(ceil_div(p->T, nsplit), 16);
+        g.nsplit = ceil_div(p->T, g.tc);
+        p->stg = g;
+        return;
+    }
     g.nbg = ceil_div(p->F, kBinsPerWave);
     g.kc = 2;
     const int nz = ceil_div(p->K, g.kc);
@@ -401,6 +430,16 @@ void choose_stats_geom(oiva_plan* p) {
 void choose_pow_geom(oiva_plan* p, int nsplit_req) {
     PowGeom g;
     g.nb = ceil_div(p->F, kBinsPerWave * kWaves);
+    if (p->M > kNarrowMax) {
+        // 17..32 channels (kernels_wide.hip): one lane per bin of a 64-bin batch; about four workgroups per CU
+        g.kp = wide_pow_sources_per_pass(p->K);
+        const int groups = g.nb * ceil_div(p->K, g.kp);
+        const int nsplit = nsplit_req > 0 ? nsplit_req : pick_splits(p->n_cu * 4, groups, p->T, 16);
+        g.tcp = round_up(ceil_div(p->T, nsplit), 4);
+        g.nsplit = ceil_div(p->T, g.tcp);
+        p->pw = g;
+        return;
+    }
     g.kp = pow_sources_per_pass(p->M, p->K);
     int nsplit = nsplit_req;
     if (nsplit <= 0) {
@@ -472,7 +511,7 @@ int stage_activation(oiva_plan* p, const float* parts, int nparts) {
     return OIVA_OK;
 }
 int stage_cov(oiva_plan* p) {
-    HIP_TRY(launch_cov(p->stream, p->X, p->X_pad, p->R, p->Plocal /* weights scratch, (T,16) */, p->wscale, p->model,
+    HIP_TRY(launch_cov(p->stream, p->X, p->X_pad, p->R, p->Wwide ? static_cast<float*>(p->Wwide) : p->Plocal /* weights scratch, (T,16) */, p->wscale, p->model,
                        p->raw_weights, p->Vpart, p->cov_f64(), p->T, p->F, p->M, p->K, p->cov));
     p->wscale_pending = !p->raw_weights;
     return OIVA_OK;
@@ -502,7 +541,7 @@ int stage_update(oiva_plan* p, bool init_only) {
 // covariance and per-bin update as one launch (kernels_cov_update.hip) where the plan's geometry is the kernel's: the headline
 // shape and its neighbours (8 channels, 2 sources, four frame splits)
 bool cov_update_applies(const oiva_plan* p) {
-    return p->fuse_cov_update && !p->cov_f64() && !p->cov.pair32 && !p->raw_weights && !(p->prec & OIVA_PREC_UPDATE_ROWS) && p->K < p->M &&
+    return p->M <= kNarrowMax && p->fuse_cov_update && !p->cov_f64() && !p->cov.pair32 && !p->raw_weights && !(p->prec & OIVA_PREC_UPDATE_ROWS) && p->K < p->M &&
            cov_update_supported(p->M, p->K, p->T, p->F, p->cov.nsplit, p->cov.tc);
 }
 int stage_cov_update(oiva_plan* p) {
@@ -539,7 +578,7 @@ constexpr int kResidentStampIters = 256;
 bool resident_applies(const oiva_plan* p) {
     // (the float64 covariance of `precise` exists in the kernel for 4 channels: 32 float64 accumulators per lane)
     const bool arith_ok = !p->cov_f64() || (p->M == 4 && p->upd_f64());
-    return p->res_on && p->res_ok && (p->F == p->F_total || p->res_world > 1) && arith_ok && !p->raw_weights && !p->wscale_pending;
+    return p->M <= kNarrowMax && p->res_on && p->res_ok && (p->F == p->F_total || p->res_world > 1) && arith_ok && !p->raw_weights && !p->wscale_pending;
 }
 
 int resident_alloc(oiva_plan* p) {
@@ -788,7 +827,7 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
     NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
     *out = nullptr;
     NEED(T >= 1 && F >= 1, OIVA_ERR_ARG, "T and F must be >= 1");
-    NEED(M >= 1 && M <= OIVA_MAX_CHANNELS, OIVA_ERR_ARG, "number of channels must be in 1..16");
+    NEED(M >= 1 && M <= OIVA_MAX_CHANNELS, OIVA_ERR_ARG, "number of channels must be in 1..32");
     NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "n_src must be in 1..n_chan");
     NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
     NEED(F_total >= F, OIVA_ERR_ARG, "F_total must be >= F");
@@ -821,7 +860,7 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
             p->n_cu = prop.multiProcessorCount;
     }
-    if (M > 8 && M % 2 == 1) {
+    if (M > 8 && M <= kNarrowMax && M % 2 == 1) {
         // 9 / 11 / 13 / 15 channels: the vector-ALU covariance kernels read 16-byte pieces at an even channel pitch, so
         // they get their own copy of X with one zero channel per bin (filled by oiva_plan_covariance; + (M + 1) / M of X)
         hipError_t ep = dev_malloc((void**)&p->X_pad, (size_t)T * F * (M + 1) * sizeof(float2));
@@ -852,6 +891,7 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
     alloc((void**)&p->Ppart, (size_t)p->pw.nb * nTK * sizeof(float));
     p->ppart_alloc = p->pw.nb;
     alloc((void**)&p->Plocal, std::max(nTK, ((size_t)T + 1) * 32) * sizeof(float));   // also the (T + 1, 16) weights scratch (floats or doubles)
+    if (M > kNarrowMax) alloc((void**)&p->Wwide, nTK * sizeof(double));                // the wide path's (T, K) float64 weights
     alloc((void**)&p->R, r_buffer_bytes(T, K));   // activations, zeroed pad rows, per-block sums (rsum_offset_floats)
     if (e == hipSuccess) e = hipMemset(p->R, 0, r_buffer_bytes(T, K));
     alloc((void**)&p->wscale, (size_t)K * sizeof(float));
@@ -889,7 +929,7 @@ int oiva_plan_destroy(oiva_plan* p) {
         p->io_c128[i] = nullptr;
     }
     void* bufs[] = {p->X_pad, p->What, p->What64, p->Cx,        p->Vpart,    p->Ppart, p->Plocal, p->res_block, p->res_trace_buf, p->res_what, p->res_what64,
-                    p->R,       p->wscale, p->Spart, p->scratch_c, p->scratch_p};
+                    p->R,       p->wscale, p->Spart, p->scratch_c, p->scratch_p, p->Wwide};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (void* b : p->og_bufs)
@@ -1832,6 +1872,8 @@ int oiva_plan_resident_debug_from(oiva_plan* p, int timeout_ms, int stall_block,
 
 // ---- OGIVE (reference ive.py:33-256) ----------------------------------------------------------------
 int oiva_plan_ogive_begin(oiva_plan* p, int update_mode, int model) {
+    NEED(p, OIVA_ERR_ARG, "null plan");
+    NEED(p->M <= kNarrowMax, OIVA_ERR_ARG, "OGIVE runs on 1..16 channels (its per-bin state is sized for them)");
     int rc = check_ready(p);
     if (rc) return rc;
     NEED(p->K == 1, OIVA_ERR_ARG, "OGIVE extracts one source: create the plan with K = 1");

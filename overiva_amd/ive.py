@@ -71,6 +71,7 @@ def ogive(
         raise ValueError("X must have shape (n_frames, n_freq, n_chan)")
     dtype = _ov._complex_dtype(X)
     n_frames, n_freq, n_chan = X.shape
+    _ov.check_channels(n_chan, limit=16, what="ogive")   # (OGIVE keeps its per-bin matrices in 16-wide arrays)
     if model not in ("laplace", "gauss"):
         raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
     if update not in UPDATE_IDS:                 # the reference silently treats anything else as 'demix' (ive.py:175-180)

@@ -15,7 +15,8 @@ arithmetic is (``resolve_precision``).  ``"fast"`` is float32 in the per-bin alg
 Documented deviations from the reference:
 * X is held as complex64 on the device even for complex128 input (a 6e-8 relative input perturbation); the
   result is cast back to the input's complex dtype;
-* at most 16 channels (``OIVA_MAX_CHANNELS``; the reference has no limit);
+* at most 32 channels (``OIVA_MAX_CHANNELS``; the reference has no limit): more raise ``ValueError`` before any device
+  call.  17..32 channels run one generic wide path (``csrc/kernels_wide.hip``) under the same arithmetic contract;
 * an unknown ``model`` raises ``ValueError`` (the reference silently returns NaN, ``overiva.py:152-167``);
 * the returned ``W`` is a fresh contiguous ``(n_freq, n_chan, n_src)`` array, not a view of ``W_hat``
   (``overiva.py:90,201-202``).
@@ -45,6 +46,15 @@ def set_precision(mode):
 
 # frame axes up to this long count as short: the reference's own calls (4096-point frames of ~10 s of audio: 160-235 frames)
 SHORT_FRAME_AXIS = 256
+
+
+MAX_CHANNELS = 32   # OIVA_MAX_CHANNELS: 1..16 channels run the kernels tuned per shape, 17..32 the generic wide path
+
+
+def check_channels(n_chan, limit=MAX_CHANNELS, what="overiva"):
+    """ValueError before any device call when X has more channels than the library serves"""
+    if not 1 <= n_chan <= limit:
+        raise ValueError(f"{what} runs on 1..{limit} channels, X has {n_chan}")
 
 
 def resolve_precision(dtype, n_chan, mode=None, n_src=None, n_frames=None):
@@ -192,6 +202,7 @@ def overiva(
         raise ValueError("X must have shape (n_frames, n_freq, n_chan)")
     dtype = _complex_dtype(X)
     n_frames, n_freq, n_chan = X.shape
+    check_channels(n_chan)
     if n_src is None:  # default to the determined case, overiva.py:83-84
         n_src = n_chan
     if not 1 <= n_src <= n_chan:
