@@ -360,6 +360,34 @@ int oiva_plan_ogive_iterate(oiva_plan *p, int first_epoch, int n, double step_si
                             int *converged, double *max_delta);
 
 /*
+ * Batched OverIVA: B independent problems of one shape (T frames, F bins, M <= 8 channels, K sources) per set of launches
+ * (kernels_batch.hip).  The life cycle mirrors a plan's; every stage serves all B problems at once and the iteration is four
+ * launches whatever B (demix+power, activation, weighted covariance, per-bin update), replayed from one captured graph.
+ * Arithmetic: always OIVA_PREC_PRECISE.  A problem's result does not depend on B or on its place in the batch: every sum is
+ * ordered by the bin and frame within its own problem.
+ *   X (B, T, F, M): host complex64 or complex128 (converted on the device), or a borrowed dense complex64 device array.
+ *   W0 (B, F, M, K) complex64 or (f64) complex128, or NULL for the identity (overiva.py:113-117).
+ *   Y (B, T, F, K) complex64 or complex128; W (B, F, M, K).
+ *   oiva_batch_get_w copies W out even when it returns OIVA_ERR_NUMERIC (some problem's W holds non-finite values; the
+ *   message names them); oiva_batch_status fills status[B] with 1 for such a problem, else 0 (both synchronise).
+ *   oiva_batch_time_stages: n eager iterations with events around every stage; per_stage_ms[4] (demix_power, activation,
+ *   weighted_cov, ip_update) per iteration, total_ms per iteration of a replay of the captured graph of n iterations.
+ */
+typedef struct oiva_batch oiva_batch;
+int oiva_batch_create(oiva_batch **out, int device, int B, int T, int F, int M, int K, int model, void *stream);
+int oiva_batch_destroy(oiva_batch *b);
+int oiva_batch_set_x_host(oiva_batch *b, const void *X_host, int f64);
+int oiva_batch_set_x_dev(oiva_batch *b, const void *X_dev);
+int oiva_batch_covariance(oiva_batch *b);
+int oiva_batch_set_w(oiva_batch *b, const void *W0_host, int f64);
+int oiva_batch_set_w_eig(oiva_batch *b);
+int oiva_batch_iterate(oiva_batch *b, int n);
+int oiva_batch_demix(oiva_batch *b, void *Y_host, int f64, int proj_back);
+int oiva_batch_get_w(oiva_batch *b, void *W_host, int f64);
+int oiva_batch_status(oiva_batch *b, int *status);
+int oiva_batch_time_stages(oiva_batch *b, int n, float *total_ms, float *per_stage_ms);
+
+/*
  * STFT analysis / synthesis on the GPU (hipFFT): time-domain audio in and out next to the solver.
  * Replaces, in the reference's drivers, pra.transform.analysis(mics_signals.T, framesize, framesize // 2, win=win_a)
  * (overiva_oneshot.py:293-295, overiva_sim.py:206-207) and pra.transform.synthesis(Y, framesize, framesize // 2,

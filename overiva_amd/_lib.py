@@ -104,6 +104,18 @@ SIGNATURES = {
     "oiva_test_time_stage": [_vp, _i, _i, _fp],
     "oiva_plan_ogive_begin": [_vp, _i, _i],
     "oiva_plan_ogive_iterate": [_vp, _i, _i, C.c_double, C.c_double, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double)],
+    "oiva_batch_create": [C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i, _vp],
+    "oiva_batch_destroy": [_vp],
+    "oiva_batch_set_x_host": [_vp, _vp, _i],
+    "oiva_batch_set_x_dev": [_vp, _vp],
+    "oiva_batch_covariance": [_vp],
+    "oiva_batch_set_w": [_vp, _vp, _i],
+    "oiva_batch_set_w_eig": [_vp],
+    "oiva_batch_iterate": [_vp, _i],
+    "oiva_batch_demix": [_vp, _vp, _i, _i],
+    "oiva_batch_get_w": [_vp, _vp, _i],
+    "oiva_batch_status": [_vp, C.POINTER(_i)],
+    "oiva_batch_time_stages": [_vp, _i, _fp, _fp],
     "oiva_stft_create": [C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp],
     "oiva_stft_destroy": [_vp],
     "oiva_stft_shape": [_vp, C.POINTER(_i), C.POINTER(_i)],

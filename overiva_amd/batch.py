@@ -1,0 +1,209 @@
+"""``overiva_batch()``: many same-shape OverIVA problems per set of launches (``oiva_batch``, csrc/kernels_batch.hip).
+
+The reference's own calls separate 10-second rooms -- 2049 bins x 160-235 frames x 2-8 microphones -- one ``overiva()`` call
+each, and a single call of that size leaves the GPU mostly idle (every kernel is a few workgroup lifetimes long, and a launch
+costs 4-5 us of each).  ``overiva_batch(X)`` takes B such problems as one (B, T, F, M) array and runs every stage for all of them
+at once: the iteration is four launches whatever B, replayed from one captured graph.  Problem ``b``'s result is that of
+``overiva(X[b], ...)`` with the same arguments in the ``precise`` arithmetic, and its bits do not depend on B or on its place in
+the batch.
+
+Arithmetic: always ``precise`` (float64 sums of exact float64 products in the covariance passes, float64 per-bin algebra, W_hat
+carried in complex128) -- what ``"auto"`` picks for these call sizes anyway; ``set_precision()`` does not change it.  X lives on
+the device as complex64; complex128 input is converted on the device.
+"""
+import ctypes as C
+import sys
+
+import numpy as np
+
+from . import _lib, sharded
+from .overiva import _complex_dtype, get_device
+
+_overiva_module = sys.modules[__package__ + ".overiva"]   # (the package's attribute `overiva` is the function)
+MAX_CHANNELS = 8
+_info = {}
+
+
+def last_batch_info():
+    """what the last ``overiva_batch()`` call ran: ``{"precision": "precise", "batched": B, ...}``"""
+    return dict(_info)
+
+
+class BatchPlan:
+    """Owns the device state of B problems of shape (T, F, M) with K sources (``oiva_batch``).
+
+    Stages as ``Plan``'s: ``set_x``, ``covariance``, ``set_w`` / ``set_w_eig``, ``iterate``, ``demix``, ``get_w``; ``status``
+    reports which problems hold a non-finite W."""
+
+    def __init__(self, B, T, F, M, K, model="laplace", device=None, stream=None):
+        if model not in _lib.MODEL_IDS:
+            raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
+        self.lib = _lib.load()
+        self.B, self.T, self.F, self.M, self.K = int(B), int(T), int(F), int(M), int(K)
+        self.model = model
+        self.device = get_device() if device is None else int(device)
+        h = C.c_void_p()
+        _lib.check(self.lib.oiva_batch_create(C.byref(h), self.device, self.B, self.T, self.F, self.M, self.K,
+                                              _lib.MODEL_IDS[model], C.c_void_p(stream) if stream else None))
+        self.h = h
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.oiva_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def shape(self):
+        return (self.B, self.T, self.F, self.M)
+
+    def set_x(self, X):
+        """X: (B, T, F, M) complex64 or complex128 host array (complex128 is converted on the device)"""
+        X = np.asarray(X)
+        if X.shape != self.shape:
+            raise ValueError(f"X has shape {X.shape}, batch expects {self.shape}")
+        if X.dtype != np.complex128:
+            X = np.ascontiguousarray(X, dtype=np.complex64)
+        else:
+            X = np.ascontiguousarray(X)
+        _lib.check(self.lib.oiva_batch_set_x_host(self.h, _lib.ptr(X), 1 if X.dtype == np.complex128 else 0))
+
+    def set_x_device(self, dev_ptr, keepalive=None):
+        """borrow a dense (B, T, F, M) complex64 device array (e.g. a torch tensor's data_ptr())"""
+        self._keep = keepalive
+        _lib.check(self.lib.oiva_batch_set_x_dev(self.h, C.c_void_p(int(dev_ptr))))
+
+    def covariance(self):
+        _lib.check(self.lib.oiva_batch_covariance(self.h))
+
+    def set_w(self, W0=None):
+        """W0: None (identity), broadcastable to (F, M, K) (one start for every problem), or (B, F, M, K)"""
+        if W0 is None:
+            _lib.check(self.lib.oiva_batch_set_w(self.h, None, 0))
+            return
+        W0 = np.asarray(W0)
+        dt = np.complex64 if W0.dtype == np.complex64 else np.complex128
+        W0 = np.ascontiguousarray(np.broadcast_to(W0, (self.B, self.F, self.M, self.K)), dtype=dt)
+        _lib.check(self.lib.oiva_batch_set_w(self.h, _lib.ptr(W0), 1 if dt == np.complex128 else 0))
+
+    def set_w_eig(self):
+        _lib.check(self.lib.oiva_batch_set_w_eig(self.h))
+
+    def iterate(self, n=1):
+        _lib.check(self.lib.oiva_batch_iterate(self.h, int(n)))
+
+    def demix(self, proj_back=True, dtype=np.complex64):
+        """Y (B, T, F, K) in complex64 or complex128"""
+        out = np.empty((self.B, self.T, self.F, self.K), dtype)
+        _lib.check(self.lib.oiva_batch_demix(self.h, _lib.ptr(out), 1 if out.dtype == np.complex128 else 0, 1 if proj_back else 0))
+        return out
+
+    def get_w(self, dtype=np.complex128, check=True):
+        """W (B, F, M, K); with ``check`` a non-finite W of any problem raises ``LinAlgError`` naming them"""
+        out = np.empty((self.B, self.F, self.M, self.K), dtype)
+        rc = self.lib.oiva_batch_get_w(self.h, _lib.ptr(out), 1 if out.dtype == np.complex128 else 0)
+        if rc != _lib.ERR_NUMERIC or check:
+            _lib.check(rc)
+        return out
+
+    def status(self):
+        """(B,) bool: True where the problem's W holds a non-finite value"""
+        st = (C.c_int * self.B)()
+        _lib.check(self.lib.oiva_batch_status(self.h, st))
+        return np.array(list(st), dtype=bool)
+
+    def time_stages(self, n):
+        """n eager iterations with events around every stage (ms per iteration per stage), and ms per iteration of a replayed
+        graph of n (<= 32) iterations; both advance the state"""
+        total = C.c_float()
+        arr = (C.c_float * _lib.N_STAGES)()
+        _lib.check(self.lib.oiva_batch_time_stages(self.h, int(n), C.byref(total), arr))
+        return total.value, dict(zip(_lib.STAGE_NAMES, list(arr)))
+
+
+def _check_args(X, n_src, model, W0, n_iter):
+    X = np.asarray(X)
+    if X.ndim != 4:
+        raise ValueError("X must have shape (batch, n_frames, n_freq, n_chan)")
+    dtype = _complex_dtype(X)
+    B, T, F, M = X.shape
+    if B < 1 or T < 1 or F < 1:
+        raise ValueError(f"X has shape {X.shape}: every dimension must be >= 1")
+    if not 1 <= M <= MAX_CHANNELS:
+        raise ValueError(f"overiva_batch runs on 1..{MAX_CHANNELS} channels, X has {M}")
+    K = M if n_src is None else n_src
+    if not isinstance(K, (int, np.integer)) or not 1 <= K <= M:
+        raise ValueError(f"n_src must be in 1..{M}")
+    if model not in ("laplace", "gauss"):
+        raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
+    if n_iter < 0:
+        raise ValueError("n_iter must be >= 0")
+    if W0 is not None:
+        W0 = np.asarray(W0)
+        try:
+            shared = np.broadcast_shapes(W0.shape, (F, M, K)) == (F, M, K)
+        except ValueError:
+            shared = False
+        if not shared and W0.shape != (B, F, M, K):
+            raise ValueError(f"W0 has shape {W0.shape}: expected one broadcastable to {(F, M, K)} or {(B, F, M, K)}")
+    if sharded.active_group() is not None:
+        raise ValueError("overiva_batch does not run under enable_bin_sharding(): disable bin sharding for batched calls")
+    return X, dtype, int(K)
+
+
+def overiva_batch(X, n_src=None, n_iter=20, proj_back=True, W0=None, model="laplace", init_eig=False, return_filters=False,
+                  callback=None):
+    """
+    ``overiva()`` (reference overiva.py:28-204) on B problems of one shape at once.
+
+    Parameters
+    ----------
+    X: ndarray (batch, nframes, nfrequencies, nchannels), complex
+        STFT representations, 1..8 channels
+    n_src, n_iter, proj_back, model, init_eig, return_filters:
+        as ``overiva()``, the same for every problem
+    W0: ndarray broadcastable to (nfrequencies, nchannels, nsrc) (one start for all), or (batch, nfrequencies, nchannels, nsrc)
+    callback: func
+        Called with the current (batch, nframes, nfrequencies, nsrc) estimate at epochs 0, 10, 20, ...
+
+    Returns
+    -------
+    Y (batch, nframes, nfrequencies, nsrc) in the dtype of X, or ``(Y, W)`` with W (batch, nfrequencies, nchannels, nsrc).
+    A problem whose W ends non-finite raises ``numpy.linalg.LinAlgError`` naming every such problem.
+    """
+    global _info
+    X, dtype, K = _check_args(X, n_src, model, W0, n_iter)
+    B, T, F, M = X.shape
+    with BatchPlan(B, T, F, M, K, model) as plan:
+        plan.set_x(X)
+        plan.covariance()
+        if W0 is None and init_eig:
+            plan.set_w_eig()                      # overiva.py:106-109, the device eigensolver per bin
+        else:
+            plan.set_w(W0)
+        epoch = 0
+        while epoch < n_iter:
+            if callback is not None and epoch % 10 == 0:      # overiva.py:142-148
+                callback(plan.demix(proj_back, dtype))
+            step = n_iter - epoch if callback is None else min(n_iter - epoch, 10 - epoch % 10)
+            plan.iterate(step)
+            epoch += step
+        Y = plan.demix(proj_back, dtype)
+        _info = {"precision": "precise", "batched": B, "sharded": False, "shape": (T, F, M, K)}
+        _overiva_module._last_info = dict(_info)        # (what last_solver_info() reports)
+        W = plan.get_w(np.complex128)               # (raises LinAlgError naming the non-finite problems, overiva.py:182)
+        if return_filters:
+            return Y, W.astype(dtype, copy=False)
+        return Y

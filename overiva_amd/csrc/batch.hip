@@ -1,0 +1,503 @@
+// C ABI of the batched iteration (oiva_batch_*, include/overiva_hip.h): B problems of one shape, up to 8 channels, in the
+// `precise` arithmetic.  Host code only; the kernels that read X or the activations live in kernels_batch.hip, the per-bin
+// stages are the single-problem kernels run on B*F bins.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "oiva_internal.h"
+
+using namespace oiva;
+
+namespace {
+
+#define HIP_TRY(expr)                                                                                          \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess) return fail_with(OIVA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+#define NEED(cond, code, msg)                       \
+    do {                                            \
+        if (!(cond)) return fail_with(code, msg);   \
+    } while (0)
+
+int ceil_div(int a, int b) { return (a + b - 1) / b; }
+int round_up(int a, int b) { return ceil_div(a, b) * b; }
+
+constexpr int kBatchMaxChannels = 8;
+constexpr int kCovFramesPerSplit = 256;   // frame splits of the covariance pass: ceil(T / 256), a function of T alone
+constexpr int kPowFramesPerSplit = 64;    // frame splits of the power pass (each partial power is one workgroup's: any split gives the same bits)
+constexpr int kGraphMaxIters = 32;        // longest captured graph: an iterate(n) call is ceil(n / 32) replays
+constexpr int kGraphCache = 4;
+constexpr size_t kStageBytes = (size_t)256 << 20;   // staging of complex128 input
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        (void)hipGetDevice(&prev);
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+}  // namespace
+
+struct oiva_batch {
+    int device = 0;
+    int B = 0, T = 0, F = 0, M = 0, K = 0, model = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    const float2* X = nullptr;     // (B, T, F, M)
+    float2* X_owned = nullptr;
+    float2* What = nullptr;        // (B*F, M, M) complex64: what the streaming kernels read
+    double2* What64 = nullptr;     // (B*F, M, M) complex128: carried between iterations by the float64 update
+    double* Cx = nullptr;          // [B*F][M*M] packed, / T
+    double* Vpart = nullptr;       // [nsplit][B*F][K][M*M]
+    float* Ppart = nullptr;        // [B][nb][T][K]
+    float* R = nullptr;            // B activation buffers of r_stride floats
+    size_t r_stride = 0;
+    float* wscale = nullptr;       // (B, K)
+    float* Spart = nullptr;        // [stg.nsplit][F][K][3]: projection-back sums of one problem at a time
+    float2* Y = nullptr;           // (B, T, F, K), allocated on first demix
+    double2* Y128 = nullptr;
+    int nsplit = 1, tc = 1;        // covariance pass
+    int kp = 1, pw_nsplit = 1, tcp = 4, nb = 1;   // power pass
+    CovGeom stg{};                 // projection-back statistics (the single-problem plan's geometry for F bins)
+    bool have_x = false, have_cx = false, have_w = false;
+    std::vector<std::pair<int, hipGraphExec_t>> graphs;
+    hipEvent_t ev[5] = {};
+};
+
+namespace {
+
+size_t nbins(const oiva_batch* b) { return (size_t)b->B * b->F; }
+
+int drop_graphs(oiva_batch* b) {
+    while (!b->graphs.empty()) {
+        HIP_TRY(hipGraphExecDestroy(b->graphs.back().second));
+        b->graphs.pop_back();
+    }
+    return OIVA_OK;
+}
+
+UpdateArgs update_args(oiva_batch* b, bool init_only) {
+    UpdateArgs a;
+    a.What = b->What;
+    a.What64 = b->What64;
+    a.Cx = b->Cx;
+    a.Vpart = b->Vpart;
+    a.vpart_f64 = 1;
+    a.wscale = init_only ? nullptr : b->wscale;
+    a.nsplit = b->nsplit;
+    a.T = b->T;
+    a.F = (int)nbins(b);
+    a.M = b->M;
+    a.K = b->K;
+    a.init_only = init_only ? 1 : 0;
+    a.use_double = 1;
+    a.layout = 0;
+    a.wscale_bins = b->F;
+    return a;
+}
+
+// the four launches of one iteration (overiva.py:138-190)
+int stage(oiva_batch* b, int s) {
+    switch (s) {
+        case 0:
+            HIP_TRY(launch_batch_power(b->stream, b->X, b->What, b->Ppart, b->B, b->T, b->F, b->M, b->K, b->kp, b->pw_nsplit, b->tcp));
+            break;
+        case 1:
+            HIP_TRY(launch_batch_activation(b->stream, b->Ppart, b->nb, b->R, b->r_stride, b->B, b->T, b->K, b->model, b->F));
+            break;
+        case 2:
+            HIP_TRY(launch_batch_cov(b->stream, b->X, b->R, b->r_stride, b->wscale, b->model, b->Vpart, b->B, b->T, b->F, b->M, b->K,
+                                     b->nsplit, b->tc));
+            break;
+        default:
+            HIP_TRY(launch_update(b->stream, update_args(b, false)));
+    }
+    return OIVA_OK;
+}
+
+int one_iteration(oiva_batch* b) {
+    for (int s = 0; s < 4; ++s) {
+        const int rc = stage(b, s);
+        if (rc) return rc;
+    }
+    return OIVA_OK;
+}
+
+// the executable graph of `iters` iterations on the batch's stream: one linear chain of 4 * iters kernel nodes
+int graph_for(oiva_batch* b, int iters, hipGraphExec_t* out) {
+    for (auto& g : b->graphs)
+        if (g.first == iters) {
+            *out = g.second;
+            return OIVA_OK;
+        }
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    HIP_TRY(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
+    int r = OIVA_OK;
+    for (int i = 0; i < iters && r == OIVA_OK; ++i) r = one_iteration(b);
+    hipError_t e = hipStreamEndCapture(b->stream, &graph);
+    if (r) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return r;
+    }
+    HIP_TRY(e);
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    HIP_TRY(e);
+    HIP_TRY(hipGraphUpload(exec, b->stream));
+    if ((int)b->graphs.size() >= kGraphCache) {
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        HIP_TRY(hipGraphExecDestroy(b->graphs.front().second));
+        b->graphs.erase(b->graphs.begin());
+    }
+    b->graphs.emplace_back(iters, exec);
+    *out = exec;
+    return OIVA_OK;
+}
+
+int check_ready(oiva_batch* b) {
+    NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    NEED(b->have_x, OIVA_ERR_STATE, "X not set (oiva_batch_set_x_host/_dev)");
+    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
+    NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set (oiva_batch_set_w)");
+    return OIVA_OK;
+}
+
+// W_hat of every bin in complex128, and the problems whose W (the first K columns) holds a non-finite value
+int download_w(oiva_batch* b, std::vector<double2>& wh, std::vector<int>& bad) {
+    const size_t MM = (size_t)b->M * b->M;
+    wh.resize(nbins(b) * MM);
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(wh.data(), b->What64, wh.size() * sizeof(double2), hipMemcpyDeviceToHost));
+    bad.assign(b->B, 0);
+    for (int p = 0; p < b->B; ++p)
+        for (size_t f = 0; f < (size_t)b->F && !bad[p]; ++f)
+            for (int r = 0; r < b->M; ++r)
+                for (int k = 0; k < b->K; ++k) {
+                    const double2 v = wh[(((size_t)p * b->F + f) * b->M + r) * b->M + k];
+                    if (!std::isfinite(v.x) || !std::isfinite(v.y)) bad[p] = 1;
+                }
+    return OIVA_OK;
+}
+
+void free_all(oiva_batch* b) {
+    (void)drop_graphs(b);
+    for (void* q : {(void*)b->X_owned, (void*)b->What, (void*)b->What64, (void*)b->Cx, (void*)b->Vpart, (void*)b->Ppart, (void*)b->R,
+                    (void*)b->wscale, (void*)b->Spart, (void*)b->Y, (void*)b->Y128})
+        if (q) (void)hipFree(q);
+    for (hipEvent_t& e : b->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int oiva_batch_create(oiva_batch** out, int device, int B, int T, int F, int M, int K, int model, void* stream) {
+    NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
+    *out = nullptr;
+    NEED(B >= 1 && T >= 1 && F >= 1, OIVA_ERR_ARG, "B, T and F must be >= 1");
+    NEED(M >= 1 && M <= kBatchMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
+    NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "number of sources must be in 1..M");
+    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
+    NEED((double)B * T * F * M < 4e9, OIVA_ERR_ARG, "batch too large");
+    DeviceGuard guard(device);
+    oiva_batch* b = new oiva_batch;
+    b->device = device;
+    b->B = B, b->T = T, b->F = F, b->M = M, b->K = K, b->model = model;
+    auto bail = [&](int rc) {
+        free_all(b);
+        delete b;
+        return rc;
+    };
+#define TRY_CREATE(expr)                                                                                          \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess) return bail(fail_with(OIVA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); \
+    } while (0)
+    if (stream) {
+        b->stream = static_cast<hipStream_t>(stream);
+    } else {
+        TRY_CREATE(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        b->own_stream = true;
+    }
+    for (hipEvent_t& e : b->ev) TRY_CREATE(hipEventCreate(&e));
+    // geometry: functions of T, F, M, K alone (never of B)
+    b->nsplit = ceil_div(T, kCovFramesPerSplit);
+    b->tc = ceil_div(T, b->nsplit);
+    b->nsplit = ceil_div(T, b->tc);
+    b->kp = pow_sources_per_pass(M, K);
+    b->tcp = round_up(ceil_div(T, ceil_div(T, kPowFramesPerSplit)), 4);
+    b->pw_nsplit = ceil_div(T, b->tcp);
+    b->nb = ceil_div(F, kBinsPerWave * kWaves);
+    b->r_stride = r_buffer_bytes(T, K) / sizeof(float);
+    int n_cu = 256;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
+    {   // the single-problem plan's statistics geometry (plan.hip, choose_stats_geom) for F bins: Y as overiva() writes it
+        CovGeom g;
+        g.nbg = ceil_div(F, kBinsPerWave);
+        g.kc = 2;
+        const int blocks = g.nbg * ceil_div(K, g.kc);
+        int ns = std::max(1, n_cu * 4 / std::max(1, blocks));
+        ns = std::min(ns, std::max(1, T / 128));
+        ns = std::min(16, ns);
+        g.tc = round_up(ceil_div(T, ns), 16);
+        g.nsplit = ceil_div(T, g.tc);
+        b->stg = g;
+    }
+    const size_t MM = (size_t)M * M;
+    TRY_CREATE(hipMalloc((void**)&b->What, nbins(b) * MM * sizeof(float2)));
+    TRY_CREATE(hipMalloc((void**)&b->What64, nbins(b) * MM * sizeof(double2)));
+    TRY_CREATE(hipMalloc((void**)&b->Cx, nbins(b) * MM * sizeof(double)));
+    TRY_CREATE(hipMalloc((void**)&b->Vpart, ((size_t)b->nsplit * nbins(b) * K * MM + 2) * sizeof(double)));   // sum_vpart reads idx + 1
+    TRY_CREATE(hipMalloc((void**)&b->Ppart, (size_t)B * b->nb * T * K * sizeof(float)));
+    TRY_CREATE(hipMalloc((void**)&b->R, (size_t)B * b->r_stride * sizeof(float)));
+    TRY_CREATE(hipMemset(b->R, 0, (size_t)B * b->r_stride * sizeof(float)));      // (the pad rows behind every problem's r)
+    TRY_CREATE(hipMalloc((void**)&b->wscale, (size_t)B * K * sizeof(float)));
+    TRY_CREATE(hipMalloc((void**)&b->Spart, (size_t)b->stg.nsplit * F * K * 3 * sizeof(float)));
+#undef TRY_CREATE
+    *out = b;
+    return OIVA_OK;
+}
+
+int oiva_batch_destroy(oiva_batch* b) {
+    if (!b) return OIVA_OK;
+    DeviceGuard guard(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    free_all(b);
+    delete b;
+    return OIVA_OK;
+}
+
+int oiva_batch_set_x_host(oiva_batch* b, const void* X, int f64) {
+    NEED(b && X, OIVA_ERR_ARG, "null argument");
+    DeviceGuard guard(b->device);
+    const size_t n = (size_t)b->B * b->T * b->F * b->M;
+    if (!b->X_owned) HIP_TRY(hipMalloc((void**)&b->X_owned, n * sizeof(float2)));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (f64) {
+        // converted on the device, through a bounded staging buffer
+        const size_t chunk = std::min(n, kStageBytes / sizeof(double2));
+        double2* stage_buf = nullptr;
+        HIP_TRY(hipMalloc((void**)&stage_buf, chunk * sizeof(double2)));
+        hipError_t e = hipSuccess;
+        for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += chunk) {
+            const size_t m = std::min(chunk, n - i0);
+            e = hipMemcpy(stage_buf, static_cast<const double2*>(X) + i0, m * sizeof(double2), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = launch_cast_c128_to_c64(b->stream, stage_buf, b->X_owned + i0, (long long)m);
+            if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+        }
+        (void)hipFree(stage_buf);
+        HIP_TRY(e);
+    } else {
+        HIP_TRY(hipMemcpy(b->X_owned, X, n * sizeof(float2), hipMemcpyHostToDevice));
+    }
+    if (b->X != b->X_owned) {          // captured graphs hold the pointer of X
+        const int rc = drop_graphs(b);
+        if (rc) return rc;
+    }
+    b->X = b->X_owned;
+    b->have_x = true;
+    b->have_cx = false;
+    return OIVA_OK;
+}
+
+int oiva_batch_set_x_dev(oiva_batch* b, const void* X_dev) {
+    NEED(b && X_dev, OIVA_ERR_ARG, "null argument");
+    DeviceGuard guard(b->device);
+    if (b->X != X_dev) {
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        const int rc = drop_graphs(b);
+        if (rc) return rc;
+    }
+    b->X = static_cast<const float2*>(X_dev);
+    b->have_x = true;
+    b->have_cx = false;
+    return OIVA_OK;
+}
+
+int oiva_batch_covariance(oiva_batch* b) {
+    NEED(b, OIVA_ERR_ARG, "null batch");
+    NEED(b->have_x, OIVA_ERR_STATE, "X not set");
+    DeviceGuard guard(b->device);
+    // unit weights, one "source": partials [nsplit][B*F][1][M*M], added in split order and divided by T (overiva.py:87)
+    HIP_TRY(launch_batch_cov(b->stream, b->X, nullptr, 0, nullptr, b->model, b->Vpart, b->B, b->T, b->F, b->M, 1, b->nsplit, b->tc));
+    HIP_TRY(launch_sum_parts(b->stream, b->Vpart, true, b->nsplit, b->Cx, (long long)nbins(b) * b->M * b->M, 1. / (double)b->T));
+    b->have_cx = true;
+    return OIVA_OK;
+}
+
+int oiva_batch_set_w(oiva_batch* b, const void* W0, int f64) {
+    NEED(b, OIVA_ERR_ARG, "null batch");
+    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (needed for the orthogonality constraint)");
+    DeviceGuard guard(b->device);
+    const int M = b->M, K = b->K;
+    const size_t nb = nbins(b);
+    std::vector<double2> wh(nb * M * M, make_double2(0., 0.));
+    for (size_t f = 0; f < nb; ++f) {
+        double2* m = wh.data() + f * M * M;
+        for (int r = 0; r < M; ++r)
+            for (int k = 0; k < K; ++k) {
+                const size_t i = (f * M + r) * K + k;
+                if (!W0)
+                    m[r * M + k] = make_double2(r == k ? 1. : 0., 0.);               // overiva.py:113-114
+                else if (f64)
+                    m[r * M + k] = static_cast<const double2*>(W0)[i];                // overiva.py:116-117
+                else
+                    m[r * M + k] = make_double2(static_cast<const float2*>(W0)[i].x, static_cast<const float2*>(W0)[i].y);
+            }
+        for (int r = K; r < M; ++r) m[r * M + r] = make_double2(-1., 0.);           // overiva.py:122-123
+    }
+    std::vector<float2> w32(wh.size());
+    for (size_t i = 0; i < wh.size(); ++i) w32[i] = make_float2((float)wh[i].x, (float)wh[i].y);
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->What, w32.data(), w32.size() * sizeof(float2), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->What64, wh.data(), wh.size() * sizeof(double2), hipMemcpyHostToDevice));
+    b->have_w = true;
+    if (K < M) HIP_TRY(launch_update(b->stream, update_args(b, true)));   // J from the orthogonality constraint, overiva.py:120-121
+    return OIVA_OK;
+}
+
+int oiva_batch_set_w_eig(oiva_batch* b) {
+    NEED(b, OIVA_ERR_ARG, "null batch");
+    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
+    DeviceGuard guard(b->device);
+    // overiva.py:106-109 per bin, the device eigensolver on B*F bins
+    HIP_TRY(launch_pca_subspace(b->stream, b->Cx, b->What, b->What64, nullptr, (int)nbins(b), b->M, b->K, true));
+    b->have_w = true;
+    if (b->K < b->M) HIP_TRY(launch_update(b->stream, update_args(b, true)));
+    return OIVA_OK;
+}
+
+int oiva_batch_iterate(oiva_batch* b, int n) {
+    int rc = check_ready(b);
+    if (rc) return rc;
+    NEED(n >= 0, OIVA_ERR_ARG, "n must be >= 0");
+    DeviceGuard guard(b->device);
+    while (n > 0) {
+        const int it = std::min(n, kGraphMaxIters);
+        hipGraphExec_t g = nullptr;
+        rc = graph_for(b, it, &g);
+        if (rc) return rc;
+        HIP_TRY(hipGraphLaunch(g, b->stream));
+        n -= it;
+    }
+    return OIVA_OK;
+}
+
+int oiva_batch_demix(oiva_batch* b, void* Y_host, int f64, int proj_back) {
+    NEED(Y_host, OIVA_ERR_ARG, "null argument");
+    int rc = check_ready(b);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    const int T = b->T, F = b->F, M = b->M, K = b->K;
+    const size_t ny = (size_t)b->B * T * F * K;
+    if (!b->Y) HIP_TRY(hipMalloc((void**)&b->Y, ny * sizeof(float2)));
+    // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0])
+    for (int p = 0; p < b->B; ++p) {
+        const float2* Xb = b->X + (size_t)p * T * F * M;
+        const float2* Wb = b->What + (size_t)p * F * M * M;
+        if (proj_back) HIP_TRY(launch_demix_stats(b->stream, Xb, Wb, b->Spart, T, F, M, K, b->stg));
+        HIP_TRY(launch_demix_write(b->stream, Xb, Wb, proj_back ? b->Spart : nullptr, b->stg.nsplit, b->Y + (size_t)p * T * F * K, T, F,
+                                   M, K));
+    }
+    if (f64) {
+        if (!b->Y128) HIP_TRY(hipMalloc((void**)&b->Y128, ny * sizeof(double2)));
+        HIP_TRY(launch_cast_c64_to_c128(b->stream, b->Y, b->Y128, (long long)ny));
+    }
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(Y_host, f64 ? (const void*)b->Y128 : (const void*)b->Y, ny * (f64 ? sizeof(double2) : sizeof(float2)),
+                      hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+int oiva_batch_get_w(oiva_batch* b, void* W_host, int f64) {
+    NEED(b && W_host, OIVA_ERR_ARG, "null argument");
+    NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set");
+    DeviceGuard guard(b->device);
+    std::vector<double2> wh;
+    std::vector<int> bad;
+    const int rc = download_w(b, wh, bad);
+    if (rc) return rc;
+    const int M = b->M, K = b->K;
+    const size_t nb = nbins(b);
+    for (size_t f = 0; f < nb; ++f)
+        for (int r = 0; r < M; ++r)
+            for (int k = 0; k < K; ++k) {
+                const double2 v = wh[(f * M + r) * M + k];
+                const size_t i = (f * M + r) * K + k;
+                if (f64)
+                    static_cast<double2*>(W_host)[i] = v;
+                else
+                    static_cast<float2*>(W_host)[i] = make_float2((float)v.x, (float)v.y);
+            }
+    std::string which;
+    for (int p = 0; p < b->B; ++p)
+        if (bad[p]) which += (which.empty() ? "" : ", ") + std::to_string(p);
+    if (!which.empty())
+        return fail_with(OIVA_ERR_NUMERIC, "demixing matrix holds non-finite values (singular W_hat^H V) in problem(s) " + which);
+    return OIVA_OK;
+}
+
+int oiva_batch_status(oiva_batch* b, int* status) {
+    NEED(b && status, OIVA_ERR_ARG, "null argument");
+    NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set");
+    DeviceGuard guard(b->device);
+    std::vector<double2> wh;
+    std::vector<int> bad;
+    const int rc = download_w(b, wh, bad);
+    if (rc) return rc;
+    std::copy(bad.begin(), bad.end(), status);
+    return OIVA_OK;
+}
+
+int oiva_batch_time_stages(oiva_batch* b, int n, float* total_ms, float* per_stage_ms) {
+    int rc = check_ready(b);
+    if (rc) return rc;
+    NEED(n >= 1 && total_ms, OIVA_ERR_ARG, "n must be >= 1");
+    DeviceGuard guard(b->device);
+    if (per_stage_ms) {
+        double acc[4] = {0., 0., 0., 0.};
+        for (int i = 0; i < n; ++i) {
+            HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+            for (int s = 0; s < 4; ++s) {
+                rc = stage(b, s);
+                if (rc) return rc;
+                HIP_TRY(hipEventRecord(b->ev[s + 1], b->stream));
+            }
+            HIP_TRY(hipEventSynchronize(b->ev[4]));
+            for (int s = 0; s < 4; ++s) {
+                float ms = 0.f;
+                HIP_TRY(hipEventElapsedTime(&ms, b->ev[s], b->ev[s + 1]));
+                acc[s] += ms;
+            }
+        }
+        for (int s = 0; s < 4; ++s) per_stage_ms[s] = (float)(acc[s] / n);
+    }
+    hipGraphExec_t g = nullptr;
+    rc = graph_for(b, std::min(n, kGraphMaxIters), &g);
+    if (rc) return rc;
+    HIP_TRY(hipGraphLaunch(g, b->stream));          // (warm)
+    HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+    HIP_TRY(hipGraphLaunch(g, b->stream));
+    HIP_TRY(hipEventRecord(b->ev[1], b->stream));
+    HIP_TRY(hipEventSynchronize(b->ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+    *total_ms = ms / (float)std::min(n, kGraphMaxIters);
+    return OIVA_OK;
+}
+
+}  // extern "C"

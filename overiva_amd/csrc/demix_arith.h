@@ -51,4 +51,71 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
+// Power pass of one workgroup of batch_power_kernel (kernels_batch.hip): power_kernel's lanes and sums (kernels_demix.hip), so a
+// problem's partial powers are those of its single-problem plan.  (power_kernel keeps its own copy of this body: the code the
+// compiler makes of the shared form differs from the single-problem kernel's, and that kernel is timed by the benchmarks.)
+// 4 waves x 16 bins =
+// the 64-bin batch `bx`, 4 frame phases per wave, frames [by * tcp, by * tcp + tcp), sources [k0, k0 + KP);
+// Ppart[bx][t][k] = sum over the batch's bins of |w_{f,k}^H x_{t,f}|^2 (each wave's 16 bins by row16_sum, then the waves in
+// order).  sp: kWaves * tcp * KP floats of LDS.
+constexpr int kBatchPowUnroll = 2;
+
+template <int M, int KP>
+__device__ __forceinline__ void power_block(const float2* __restrict__ X, const float2* __restrict__ What,
+                                            float* __restrict__ Ppart, int T, int F, int K, int tcp, unsigned bx, unsigned by, int k0,
+                                            float* sp) {
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int b = lane & 15;
+    const int q = lane >> 4;
+    const int f = (bx * kWaves + wave) * kBinsPerWave + b;
+    const bool fvalid = f < F;
+    const int fc = fvalid ? f : F - 1;
+    const int t_begin = by * tcp;
+    const int t_end = min(T, t_begin + tcp);
+    const int len = t_end - t_begin;
+    const int nsteps = (len + 3) >> 2;
+
+    float wr[KP][M], wi[KP][M];
+    load_wconj<M, KP>(What, fc, k0, K, wr, wi);
+
+    // kBatchPowUnroll steps are loaded before any of them is consumed: a wave keeps kBatchPowUnroll * 64 * M * 8
+    // bytes in flight, which is what hides HBM latency here (more resident waves only thrash the L1,
+    // because a lane's M*8 bytes arrive through M/2 separate dwordx4 requests to the same lines).
+    const size_t frame_stride = (size_t)F * M;
+    const float2* pbase = X + (size_t)fc * M;
+    for (int i = 0; i < nsteps; i += kBatchPowUnroll) {
+        float xr[kBatchPowUnroll][M], xi[kBatchPowUnroll][M];
+#pragma unroll
+        for (int u = 0; u < kBatchPowUnroll; ++u) {
+            const int tl = 4 * (i + u) + q;
+            const int t = tl < len ? t_begin + tl : T - 1;      // clamped: legal address, result unused
+            load_x<M>(pbase + (size_t)t * frame_stride, xr[u], xi[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kBatchPowUnroll; ++u) {
+            const int tl = 4 * (i + u) + q;
+            const bool live = tl < len;
+#pragma unroll
+            for (int kk = 0; kk < KP; ++kk) {
+                float yr, yi;
+                demix_one<M>(wr[kk], wi[kk], xr[u], xi[u], yr, yi);
+                float pw = fmaf(yr, yr, yi * yi);
+                pw = fvalid ? pw : 0.f;
+                pw = row16_sum(pw);
+                if (b == 0 && live) sp[(wave * tcp + tl) * KP + kk] = pw;
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < len * KP; e += kBlock) {
+        const int tl = e / KP, kk = e - tl * KP;
+        float s = sp[(0 * tcp + tl) * KP + kk];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) s += sp[(w * tcp + tl) * KP + kk];
+        if (k0 + kk < K) Ppart[((size_t)bx * T + t_begin + tl) * K + k0 + kk] = s;
+    }
+}
+
 }  // namespace oiva

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kBlock) void update_kernel(UpdateArgs a) {
         }
     }
     if (a.wscale != nullptr && i < K) {  // overiva.py:163 / :167
-        const R s = R(1) / R(a.wscale[i]);
+        const R s = R(1) / R(wscale_at(a, f, i));
 #pragma unroll
         for (int m = 0; m < SG; ++m) {
             B[m].re *= s;
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void update_sq_kernel(UpdateArgs a) {
         B = {vr, -vi};
     }
     if (a.wscale != nullptr && i < K) {  // overiva.py:163 / :167
-        const R s = R(1) / R(a.wscale[i]);
+        const R s = R(1) / R(wscale_at(a, f, i));
         B.re *= s;
         B.im *= s;
     }
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(kBlock) void update_bg_kernel(UpdateArgs a) {
         B = {vr, -vi};
     }
     if (a.wscale != nullptr && i < K) {  // overiva.py:163 / :167
-        const R sc = R(1) / R(a.wscale[i]);
+        const R sc = R(1) / R(wscale_at(a, f, i));
         B.re *= sc;
         B.im *= sc;
     }
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(kBlock) void update_det_kernel(UpdateArgs a) {
         B = {vr, -vi};
     }
     if (a.wscale != nullptr && i < M) {  // overiva.py:163 / :167
-        const R sc = R(1) / R(a.wscale[i]);
+        const R sc = R(1) / R(wscale_at(a, f, i));
         B.re *= sc;
         B.im *= sc;
     }
@@ -546,7 +546,7 @@ __global__ __launch_bounds__(kBlock) void update_gram_kernel(UpdateArgs a) {
         B = {vr, -vi};
     }
     if (a.wscale != nullptr && i < K) {  // overiva.py:163 / :167
-        const R sc = R(1) / R(a.wscale[i]);
+        const R sc = R(1) / R(wscale_at(a, f, i));
         B.re *= sc;
         B.im *= sc;
     }

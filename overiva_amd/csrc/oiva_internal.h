@@ -183,7 +183,12 @@ struct UpdateArgs {
     int init_only;        // 1: only (re)compute J from W and Cx
     int use_double;       // per-bin algebra in fp64
     int layout;           // 0: one lane per matrix element (M <= 8), 1: one lane per matrix row
+    int wscale_bins = 0;  // batched plans (kernels_batch.hip): F is B problems of this many bins each and wscale is (B, K); 0: (K)
 };
+// the pending scale of column i of bin f (overiva.py:163 / :167): the bin's problem's row of wscale
+__device__ __forceinline__ float wscale_at(const UpdateArgs& a, int f, int i) {
+    return a.wscale[(a.wscale_bins > 0 ? (size_t)(f / a.wscale_bins) * a.K : 0) + i];
+}
 // W_hat element idx: the float64 variants keep their own complex128 copy so that nothing is rounded to
 // float32 between iterations; the complex64 array is always written (the streaming kernels read it)
 template <typename R>
@@ -314,6 +319,16 @@ hipError_t launch_demix_stats_wide(hipStream_t s, const float2* X, const float2*
 hipError_t launch_demix_write_wide(hipStream_t s, const float2* X, const float2* What, const float* Spart, int nsplit, float2* Y, int T,
                                    int F, int M, int K);
 hipError_t launch_update_wide(hipStream_t s, const UpdateArgs& a);
+
+// The batched iteration (kernels_batch.hip, batch.hip): B problems of one shape, <= 8 channels, `precise` arithmetic.
+//   X (B, T, F, M); What (B*F, M, M); Ppart [B][nb][T][K]; R: B buffers of r_stride floats (r_buffer_bytes(T, K) / 4);
+//   wscale (B, K); Vpart [nsplit][B*F][K][M*M] float64 (K = 1 with R == nullptr: unit weights, the input covariance)
+hipError_t launch_batch_power(hipStream_t s, const float2* X, const float2* What, float* Ppart, int B, int T, int F, int M, int K,
+                              int kp, int nsplit, int tcp);
+hipError_t launch_batch_activation(hipStream_t s, const float* parts, int nparts, float* R, size_t r_stride, int B, int T, int K,
+                                   int model, int F);
+hipError_t launch_batch_cov(hipStream_t s, const float2* X, const float* R, size_t r_stride, float* wscale, int model, double* Vpart,
+                            int B, int T, int F, int M, int K, int nsplit, int tc);
 
 // dense complex128 <-> complex64 conversion on the device
 hipError_t launch_cast_c128_to_c64(hipStream_t s, const double2* in, float2* out, long long n);
