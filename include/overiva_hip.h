@@ -388,6 +388,29 @@ int oiva_batch_status(oiva_batch *b, int *status);
 int oiva_batch_time_stages(oiva_batch *b, int n, float *total_ms, float *per_stage_ms);
 
 /*
+ * Batched OGIVE: ive.py::ogive on B problems of one shape (M <= 8 channels) per set of launches, each problem with its own
+ * stopping rule (kernels_ogive_batch.hip).  Runs on a batch created with K = 1, after oiva_batch_covariance and
+ * oiva_batch_set_w (w = column 0: identity, W0, or the principal eigenvector from the host, read through oiva_batch_get_cx):
+ *   oiva_batch_get_cx        : the input covariance Cx (B, F, M, M), complex64 or (f64) complex128                ive.py:96
+ *   oiva_batch_ogive_begin   : Cx^-1, ||Cx||, a from w, step selection on every bin; every problem running,
+ *                              0 epochs                                                        ive.py:100-102,136-139,173-180
+ *   oiva_batch_ogive_iterate : up to n epochs of ive.py:190-246 starting at epoch index first_epoch (the switching criterion
+ *                              runs when the index is a multiple of 10), replayed from one linear captured graph.  Problem p
+ *                              stops at the first epoch whose max ||delta|| < tol; its state is then frozen and later epochs
+ *                              skip it.  Synchronous; fills, per problem, epochs_run[B] (epochs of this call that changed its
+ *                              state), converged[B] (rule met) and max_delta[B] (max ||delta|| of its last epoch).
+ * Arithmetic: OIVA_PREC_PRECISE.  x_psi is formed from float64 frame sums of rinv x conj(y) (ive.py:221-227), so a problem
+ * matches oiva_plan_ogive_* to rounding; its bits and its epoch count do not depend on B, on its place in the batch or on
+ * which other problems have stopped.  The result is read with oiva_batch_demix / oiva_batch_get_w / oiva_batch_status.
+ * oiva_status is int, the status code every entry point returns.
+ */
+typedef int oiva_status;
+oiva_status oiva_batch_get_cx(oiva_batch *b, void *Cx_host, int f64);
+oiva_status oiva_batch_ogive_begin(oiva_batch *b, int update_mode, int model);
+oiva_status oiva_batch_ogive_iterate(oiva_batch *b, int first_epoch, int n, double step_size, double tol, int *epochs_run,
+                                     int *converged, double *max_delta);
+
+/*
  * STFT analysis / synthesis on the GPU (hipFFT): time-domain audio in and out next to the solver.
  * Replaces, in the reference's drivers, pra.transform.analysis(mics_signals.T, framesize, framesize // 2, win=win_a)
  * (overiva_oneshot.py:293-295, overiva_sim.py:206-207) and pra.transform.synthesis(Y, framesize, framesize // 2,

@@ -1,4 +1,5 @@
-"""``overiva_batch()``: many same-shape OverIVA problems per set of launches (``oiva_batch``, csrc/kernels_batch.hip).
+"""``overiva_batch()``: many same-shape OverIVA problems per set of launches (``oiva_batch``, csrc/kernels_batch.hip), and
+``ogive_batch()``, the same for OGIVE with a stopping rule per problem (csrc/kernels_ogive_batch.hip).
 
 The reference's own calls separate 10-second rooms -- 2049 bins x 160-235 frames x 2-8 microphones -- one ``overiva()`` call
 each, and a single call of that size leaves the GPU mostly idle (every kernel is a few workgroup lifetimes long, and a launch
@@ -17,6 +18,7 @@ import sys
 import numpy as np
 
 from . import _lib, sharded
+from . import ive as _ive
 from .overiva import _complex_dtype, get_device
 
 _overiva_module = sys.modules[__package__ + ".overiva"]   # (the package's attribute `overiva` is the function)
@@ -25,7 +27,8 @@ _info = {}
 
 
 def last_batch_info():
-    """what the last ``overiva_batch()`` call ran: ``{"precision": "precise", "batched": B, ...}``"""
+    """what the last ``overiva_batch()`` or ``ogive_batch()`` call ran: ``{"precision": "precise", "batched": B, ...}``; after
+    ``ogive_batch()`` also ``epochs`` (B ints: epochs each problem ran) and ``converged`` (B bools: its stopping rule fired)"""
     return dict(_info)
 
 
@@ -33,7 +36,8 @@ class BatchPlan:
     """Owns the device state of B problems of shape (T, F, M) with K sources (``oiva_batch``).
 
     Stages as ``Plan``'s: ``set_x``, ``covariance``, ``set_w`` / ``set_w_eig``, ``iterate``, ``demix``, ``get_w``; ``status``
-    reports which problems hold a non-finite W."""
+    reports which problems hold a non-finite W.  With K = 1, ``ogive_begin`` / ``ogive_iterate`` run OGIVE instead of
+    ``iterate`` (``get_cx`` reads the input covariance for the host's ``init_eig``)."""
 
     def __init__(self, B, T, F, M, K, model="laplace", device=None, stream=None):
         if model not in _lib.MODEL_IDS:
@@ -88,6 +92,12 @@ class BatchPlan:
     def covariance(self):
         _lib.check(self.lib.oiva_batch_covariance(self.h))
 
+    def get_cx(self, dtype=np.complex128):
+        """input covariance (B, F, M, M); the device holds it in float64"""
+        out = np.empty((self.B, self.F, self.M, self.M), dtype)
+        _lib.check(self.lib.oiva_batch_get_cx(self.h, _lib.ptr(out), 1 if out.dtype == np.complex128 else 0))
+        return out
+
     def set_w(self, W0=None):
         """W0: None (identity), broadcastable to (F, M, K) (one start for every problem), or (B, F, M, K)"""
         if W0 is None:
@@ -103,6 +113,16 @@ class BatchPlan:
 
     def iterate(self, n=1):
         _lib.check(self.lib.oiva_batch_iterate(self.h, int(n)))
+
+    def ogive_begin(self, update="demix", model="laplace"):
+        _lib.check(self.lib.oiva_batch_ogive_begin(self.h, _ive.UPDATE_IDS[update], _lib.MODEL_IDS[model]))
+
+    def ogive_iterate(self, first_epoch, n, step_size=0.1, tol=1e-3):
+        """up to n epochs; returns, per problem, (epochs of this call that changed its state, stopping rule met, max ||delta|| of
+        its last epoch) as (B,) arrays"""
+        ran, conv, md = (C.c_int * self.B)(), (C.c_int * self.B)(), (C.c_double * self.B)()
+        _lib.check(self.lib.oiva_batch_ogive_iterate(self.h, int(first_epoch), int(n), float(step_size), float(tol), ran, conv, md))
+        return np.array(list(ran), dtype=int), np.array(list(conv), dtype=bool), np.array(list(md))
 
     def demix(self, proj_back=True, dtype=np.complex64):
         """Y (B, T, F, K) in complex64 or complex128"""
@@ -206,4 +226,91 @@ def overiva_batch(X, n_src=None, n_iter=20, proj_back=True, W0=None, model="lapl
         W = plan.get_w(np.complex128)               # (raises LinAlgError naming the non-finite problems, overiva.py:182)
         if return_filters:
             return Y, W.astype(dtype, copy=False)
+        return Y
+
+
+def _check_ogive_args(X, update, model, W0, n_iter):
+    X = np.asarray(X)
+    if X.ndim != 4:
+        raise ValueError("X must have shape (batch, n_frames, n_freq, n_chan)")
+    dtype = _complex_dtype(X)
+    B, T, F, M = X.shape
+    if B < 1 or T < 1 or F < 1:
+        raise ValueError(f"X has shape {X.shape}: every dimension must be >= 1")
+    if not 1 <= M <= MAX_CHANNELS:
+        raise ValueError(f"ogive_batch runs on 1..{MAX_CHANNELS} channels, X has {M}")
+    if model not in ("laplace", "gauss"):
+        raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
+    if update not in _ive.UPDATE_IDS:
+        raise ValueError(f"update must be one of {sorted(_ive.UPDATE_IDS)}, got {update!r}")
+    if n_iter < 0:
+        raise ValueError("n_iter must be >= 0")
+    if W0 is not None:
+        W0 = np.asarray(W0)
+        try:
+            shared = np.broadcast_shapes(W0.shape, (F, M, 1)) == (F, M, 1)
+        except ValueError:
+            shared = False
+        if not shared and W0.shape != (B, F, M, 1):
+            raise ValueError(f"W0 has shape {W0.shape}: expected one broadcastable to {(F, M, 1)} or {(B, F, M, 1)}")
+    if sharded.active_group() is not None:
+        raise ValueError("ogive_batch does not run under enable_bin_sharding(): disable bin sharding for batched calls")
+    return X, dtype
+
+
+def ogive_batch(X, n_iter=4000, step_size=0.1, tol=1e-3, update="demix", proj_back=True, W0=None, model="laplace", init_eig=False,
+                return_filters=False, callback=None):
+    """
+    ``ogive()`` (reference ive.py:33-256) on B problems of one shape at once, each with its own stopping rule.
+
+    Parameters
+    ----------
+    X: ndarray (batch, nframes, nfrequencies, nchannels), complex
+        STFT representations, 1..8 channels
+    n_iter, step_size, tol, update, proj_back, model, init_eig, return_filters:
+        as ``ogive()``, the same for every problem
+    W0: ndarray broadcastable to (nfrequencies, nchannels, 1) (one start for all), or (batch, nfrequencies, nchannels, 1)
+    callback: func
+        Called with the current (batch, nframes, nfrequencies, 1) estimate every 100 epochs while any problem is running;
+        problems that have stopped appear with their final state
+
+    Returns
+    -------
+    Y (batch, nframes, nfrequencies, 1) in the dtype of X, or ``(Y, w)`` with w (batch, nfrequencies, nchannels, 1).
+    Problem b gets what ``ogive(X[b], ...)`` gives in the ``precise`` arithmetic, including the epoch at which its stopping rule
+    fires (``last_batch_info()["epochs"]``).  A problem whose w ends non-finite raises ``numpy.linalg.LinAlgError`` naming every
+    such problem.
+    """
+    global _info
+    X, dtype = _check_ogive_args(X, update, model, W0, n_iter)
+    B, T, F, M = X.shape
+    with BatchPlan(B, T, F, M, 1, model) as plan:
+        plan.set_x(X)
+        plan.covariance()                                                   # ive.py:100
+        if W0 is None and init_eig:                                         # ive.py:111-126 per problem (host LAPACK; not conjugated)
+            cx = plan.get_cx(np.complex128)
+            W0 = np.empty((B, F, M, 1), np.complex128)
+            for b in range(B):
+                vals, vecs = np.linalg.eig(cx[b])
+                W0[b, :, :, 0] = np.stack([vecs[f][:, np.argmax(vals[f])] for f in range(F)])
+        plan.set_w(None if W0 is None else np.asarray(W0))
+        plan.ogive_begin(update, model)
+        epochs = np.zeros(B, dtype=int)
+        converged = np.zeros(B, dtype=bool)
+        epoch = 0
+        while epoch < n_iter and not converged.all():
+            if callback is not None and epoch % 100 == 0:                  # ive.py:199-205
+                callback(plan.demix(proj_back, dtype))
+            step = min(n_iter - epoch, _ive.CHUNK)
+            if callback is not None:
+                step = min(step, 100 - epoch % 100)
+            ran, converged, _ = plan.ogive_iterate(epoch, step, step_size, tol)
+            epochs += ran
+            epoch += step
+        Y = plan.demix(proj_back, dtype)                                    # ive.py:249-256
+        _info = {"precision": "precise", "batched": B, "sharded": False, "shape": (T, F, M, 1), "algorithm": "ogive",
+                 "epochs": [int(e) for e in epochs], "converged": [bool(c) for c in converged]}
+        w = plan.get_w(np.complex128)               # (raises LinAlgError naming the non-finite problems)
+        if return_filters:
+            return Y, w.astype(dtype, copy=False)
         return Y

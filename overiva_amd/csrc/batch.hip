@@ -1,6 +1,7 @@
 // C ABI of the batched iteration (oiva_batch_*, include/overiva_hip.h): B problems of one shape, up to 8 channels, in the
 // `precise` arithmetic.  Host code only; the kernels that read X or the activations live in kernels_batch.hip, the per-bin
-// stages are the single-problem kernels run on B*F bins.
+// stages are the single-problem kernels run on B*F bins.  Batched OGIVE (oiva_batch_ogive_*) runs on a batch created with
+// K = 1, with its own kernels (kernels_ogive_batch.hip) and a stopping rule per problem.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -33,6 +34,8 @@ constexpr int kPowFramesPerSplit = 64;    // frame splits of the power pass (eac
 constexpr int kGraphMaxIters = 32;        // longest captured graph: an iterate(n) call is ceil(n / 32) replays
 constexpr int kGraphCache = 4;
 constexpr size_t kStageBytes = (size_t)256 << 20;   // staging of complex128 input
+constexpr int kOgFramesPerSplit = 64;     // frame splits of the OGIVE frame sums: ceil(T / 64), a function of T alone
+constexpr int kOgMinGraphEpochs = 8;      // shorter OGIVE chunks run eagerly
 
 struct DeviceGuard {
     int prev = -1;
@@ -73,6 +76,17 @@ struct oiva_batch {
     bool have_x = false, have_cx = false, have_w = false;
     std::vector<std::pair<int, hipGraphExec_t>> graphs;
     hipEvent_t ev[5] = {};
+    // batched OGIVE (ive.py:33-256): per-bin state of B*F bins and the per-problem stopping rule, allocated by ogive_begin
+    OgiveBatchState og{};
+    std::vector<void*> og_bufs;
+    double* Opart = nullptr;       // [osplit][B*F][2M+1] frame-sum partials
+    int osplit = 1, otc = 1;
+    bool og_ready = false;
+    int og_mode = 0, og_model = 0;
+    // captured chunk of epochs, cached on (n, phase in the 10-epoch switching cycle, step size, tol) as the single plan's
+    hipGraphExec_t og_graph = nullptr;
+    int og_graph_n = 0, og_graph_phase = -1;
+    double og_graph_mu = 0., og_graph_tol = 0.;
 };
 
 namespace {
@@ -83,6 +97,11 @@ int drop_graphs(oiva_batch* b) {
     while (!b->graphs.empty()) {
         HIP_TRY(hipGraphExecDestroy(b->graphs.back().second));
         b->graphs.pop_back();
+    }
+    if (b->og_graph) {
+        hipGraphExec_t g = b->og_graph;
+        b->og_graph = nullptr;
+        HIP_TRY(hipGraphExecDestroy(g));
     }
     return OIVA_OK;
 }
@@ -196,6 +215,7 @@ void free_all(oiva_batch* b) {
     for (void* q : {(void*)b->X_owned, (void*)b->What, (void*)b->What64, (void*)b->Cx, (void*)b->Vpart, (void*)b->Ppart, (void*)b->R,
                     (void*)b->wscale, (void*)b->Spart, (void*)b->Y, (void*)b->Y128})
         if (q) (void)hipFree(q);
+    for (void* q : b->og_bufs) (void)hipFree(q);
     for (hipEvent_t& e : b->ev)
         if (e) (void)hipEventDestroy(e);
     if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
@@ -243,6 +263,9 @@ int oiva_batch_create(oiva_batch** out, int device, int B, int T, int F, int M, 
     b->pw_nsplit = ceil_div(T, b->tcp);
     b->nb = ceil_div(F, kBinsPerWave * kWaves);
     b->r_stride = r_buffer_bytes(T, K) / sizeof(float);
+    b->osplit = ceil_div(T, kOgFramesPerSplit);
+    b->otc = ceil_div(T, b->osplit);
+    b->osplit = ceil_div(T, b->otc);
     int n_cu = 256;
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
     {   // the single-problem plan's statistics geometry (plan.hip, choose_stats_geom) for F bins: Y as overiva() writes it
@@ -497,6 +520,142 @@ int oiva_batch_time_stages(oiva_batch* b, int n, float* total_ms, float* per_sta
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
     *total_ms = ms / (float)std::min(n, kGraphMaxIters);
+    return OIVA_OK;
+}
+
+// ---- batched OGIVE (reference ive.py:33-256, one problem per batch entry) -------------------------------------------------
+oiva_status oiva_batch_get_cx(oiva_batch* b, void* Cx_host, int f64) {
+    NEED(b && Cx_host, OIVA_ERR_ARG, "null argument");
+    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
+    DeviceGuard guard(b->device);
+    const size_t n = nbins(b) * b->M * b->M;
+    const size_t bytes = n * (f64 ? sizeof(double2) : sizeof(float2));
+    void* full = nullptr;
+    HIP_TRY(hipMalloc(&full, bytes));
+    hipError_t e = launch_unpack_herm(b->stream, b->Cx, full, f64 != 0, (long long)nbins(b), b->M);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(Cx_host, full, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(full);
+    HIP_TRY(e);
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_ogive_begin(oiva_batch* b, int update_mode, int model) {
+    int rc = check_ready(b);
+    if (rc) return rc;
+    NEED(b->K == 1, OIVA_ERR_ARG, "OGIVE extracts one source: create the batch with K = 1");
+    NEED(update_mode >= OIVA_OGIVE_DEMIX && update_mode <= OIVA_OGIVE_SWITCHING, OIVA_ERR_ARG, "unknown update mode");
+    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
+    DeviceGuard guard(b->device);
+    const size_t nb = nbins(b), M = b->M, B = b->B;
+    if (b->og_bufs.empty()) {
+        hipError_t e = hipSuccess;
+        auto alloc = [&](size_t bytes) -> void* {
+            void* ptr = nullptr;
+            if (e == hipSuccess) e = hipMalloc(&ptr, bytes);
+            if (ptr) b->og_bufs.push_back(ptr);
+            return ptr;
+        };
+        OgiveState& st = b->og.bin;
+        st.CxInv = (double2*)alloc(nb * M * M * sizeof(double2));
+        st.CxNorm = (double*)alloc(nb * sizeof(double));
+        st.A = (double2*)alloc(nb * M * sizeof(double2));
+        st.Delta = (double2*)alloc(nb * M * sizeof(double2));
+        st.Lambda = (double*)alloc(nb * sizeof(double));
+        st.DoA = (int*)alloc(nb * sizeof(int));
+        st.DoW = (int*)alloc(nb * sizeof(int));
+        st.Dnorm = (double*)alloc(nb * sizeof(double));
+        st.ctrl = (int*)alloc(4 * sizeof(int));                 // (reset by ogive_init_kernel; the batch keeps its own per problem)
+        st.maxdelta = (double*)alloc(2 * sizeof(double));
+        b->og.done = (int*)alloc(B * sizeof(int));
+        b->og.epochs = (int*)alloc(B * sizeof(int));
+        b->og.maxdelta = (double*)alloc(B * sizeof(double));
+        b->og.runmax = (unsigned long long*)alloc(B * sizeof(unsigned long long));
+        b->og.ticket = (unsigned*)alloc(B * sizeof(unsigned));
+        b->Opart = (double*)alloc((size_t)b->osplit * nb * (2 * M + 1) * sizeof(double));
+        if (e != hipSuccess) return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(e));
+    }
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (b->og_graph) {                   // captured for the previous update mode / model
+        HIP_TRY(hipGraphExecDestroy(b->og_graph));
+        b->og_graph = nullptr;
+    }
+    b->og.bin.Cx = b->Cx;
+    b->og.bin.What = b->What;
+    b->og.bin.What64 = b->What64;
+    b->og_mode = update_mode;
+    b->og_model = model;
+    // Cx^-1, ||Cx||, a from w, the step selection (ive.py:100-102,136-139,173-180) on all B*F bins
+    HIP_TRY(launch_ogive_init(b->stream, b->og.bin, (int)nb, b->M, update_mode));
+    HIP_TRY(hipMemsetAsync(b->og.done, 0, B * sizeof(int), b->stream));
+    HIP_TRY(hipMemsetAsync(b->og.epochs, 0, B * sizeof(int), b->stream));
+    HIP_TRY(hipMemsetAsync(b->og.maxdelta, 0, B * sizeof(double), b->stream));
+    HIP_TRY(hipMemsetAsync(b->og.runmax, 0, B * sizeof(unsigned long long), b->stream));
+    HIP_TRY(hipMemsetAsync(b->og.ticket, 0, B * sizeof(unsigned), b->stream));
+    b->og_ready = true;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_ogive_iterate(oiva_batch* b, int first_epoch, int n, double step_size, double tol, int* epochs_run, int* converged,
+                                 double* max_delta) {
+    int rc = check_ready(b);
+    if (rc) return rc;
+    NEED(b->og_ready, OIVA_ERR_STATE, "call oiva_batch_ogive_begin first");
+    NEED(n >= 0 && first_epoch >= 0, OIVA_ERR_ARG, "negative epoch count");
+    DeviceGuard guard(b->device);
+    const int B = b->B;
+    std::vector<int> before(B), after(B);
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(before.data(), b->og.epochs, B * sizeof(int), hipMemcpyDeviceToHost));
+    const int amodel = b->og_model == OIVA_MODEL_LAPLACE ? kModelOgiveLaplace : OIVA_MODEL_GAUSS;
+    // one epoch is five launches on the batch's stream (four when the switching criterion does not run)
+    auto epochs = [&](int e0, int count) -> int {
+        for (int e = e0; e < e0 + count; ++e) {
+            if (b->og_mode == OIVA_OGIVE_SWITCHING && e % 10 == 0)
+                HIP_TRY(launch_batch_ogive_switch(b->stream, b->og, B, b->F, b->M));                     // ive.py:192-193
+            HIP_TRY(launch_batch_ogive_power(b->stream, b->X, b->What, b->Ppart, b->og.done, B, b->T, b->F, b->M, b->pw_nsplit,
+                                             b->tcp));                                                    // ive.py:196, :210/:213
+            HIP_TRY(launch_batch_ogive_activation(b->stream, b->Ppart, b->nb, b->R, b->r_stride, b->og.done, B, b->T, amodel,
+                                                  b->F));                                                 // ive.py:209-217
+            HIP_TRY(launch_batch_ogive_framesum(b->stream, b->X, b->What64, b->R, b->r_stride, b->og.done, b->Opart, B, b->T, b->F,
+                                                b->M, b->osplit, b->otc));                                // ive.py:218-227
+            HIP_TRY(launch_batch_ogive_step(b->stream, b->og, b->Opart, b->osplit, B, b->F, b->M, step_size, tol));   // ive.py:228-246
+        }
+        return OIVA_OK;
+    };
+    if (n >= kOgMinGraphEpochs) {
+        // n epochs as one linear graph on the batch's stream, cached while (n, phase, step size, tol) stay the same
+        const int phase = first_epoch % 10;
+        if (!b->og_graph || b->og_graph_n != n || b->og_graph_phase != phase || b->og_graph_mu != step_size || b->og_graph_tol != tol) {
+            if (b->og_graph) HIP_TRY(hipGraphExecDestroy(b->og_graph));
+            b->og_graph = nullptr;
+            hipGraph_t graph = nullptr;
+            HIP_TRY(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
+            rc = epochs(phase, n);
+            hipError_t e = hipStreamEndCapture(b->stream, &graph);
+            if (rc) {
+                if (graph) (void)hipGraphDestroy(graph);
+                return rc;
+            }
+            HIP_TRY(e);
+            e = hipGraphInstantiate(&b->og_graph, graph, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(graph);
+            HIP_TRY(e);
+            b->og_graph_n = n;
+            b->og_graph_phase = phase;
+            b->og_graph_mu = step_size;
+            b->og_graph_tol = tol;
+        }
+        HIP_TRY(hipGraphLaunch(b->og_graph, b->stream));
+    } else if ((rc = epochs(first_epoch, n))) {
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(after.data(), b->og.epochs, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (epochs_run)
+        for (int p = 0; p < B; ++p) epochs_run[p] = after[p] - before[p];
+    if (converged) HIP_TRY(hipMemcpy(converged, b->og.done, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (max_delta) HIP_TRY(hipMemcpy(max_delta, b->og.maxdelta, B * sizeof(double), hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 

@@ -330,6 +330,28 @@ hipError_t launch_batch_activation(hipStream_t s, const float* parts, int nparts
 hipError_t launch_batch_cov(hipStream_t s, const float2* X, const float* R, size_t r_stride, float* wscale, int model, double* Vpart,
                             int B, int T, int F, int M, int K, int nsplit, int tc);
 
+// Batched OGIVE (kernels_ogive_batch.hip, batch.hip): B problems of one shape, <= 8 channels, K = 1, `precise` arithmetic.
+//   bin: OgiveState of the B*F bins (bin index = problem * F + bin; its ctrl / maxdelta are only the scratch ogive_init_kernel
+//   resets); done, epochs, maxdelta (B): the per-problem stopping rule; runmax, ticket (B): the step kernel's hand-off.
+//   Opart [osplit][B*F][2M+1] float64: per frame split, s = sum_t rinv_t x_t conj(y_t) (M complex) and zeta = sum_t rinv_t |y_t|^2
+struct OgiveBatchState {
+    OgiveState bin;
+    int* done;
+    int* epochs;
+    double* maxdelta;
+    unsigned long long* runmax;
+    unsigned* ticket;
+};
+hipError_t launch_batch_ogive_switch(hipStream_t s, const OgiveBatchState& st, int B, int F, int M);
+hipError_t launch_batch_ogive_power(hipStream_t s, const float2* X, const float2* What, float* Ppart, const int* done, int B, int T, int F,
+                                    int M, int nsplit, int tcp);
+hipError_t launch_batch_ogive_activation(hipStream_t s, const float* parts, int nparts, float* R, size_t r_stride, const int* done, int B,
+                                         int T, int amodel, int F);
+hipError_t launch_batch_ogive_framesum(hipStream_t s, const float2* X, const double2* What64, const float* R, size_t r_stride,
+                                       const int* done, double* Opart, int B, int T, int F, int M, int osplit, int otc);
+hipError_t launch_batch_ogive_step(hipStream_t s, const OgiveBatchState& st, const double* Opart, int osplit, int B, int F, int M, double mu,
+                                   double tol);
+
 // dense complex128 <-> complex64 conversion on the device
 hipError_t launch_cast_c128_to_c64(hipStream_t s, const double2* in, float2* out, long long n);
 hipError_t launch_cast_c64_to_c128(hipStream_t s, const float2* in, double2* out, long long n);
