@@ -411,6 +411,22 @@ oiva_status oiva_batch_ogive_iterate(oiva_batch *b, int first_epoch, int n, doub
                                      int *converged, double *max_delta);
 
 /*
+ * Ragged batch: B problems of one F, M <= 8 and K but of frames[b] = T_b >= 1 frames each (rooms of different lengths).
+ * oiva_batch_create_ragged checks its arguments before any device call (OIVA_ERR_ARG: null frames, B < 1, a T_b < 1, F < 1,
+ * M outside 1..8, K outside 1..M, sizes that overflow) and returns an ordinary oiva_batch: every oiva_batch_* entry above
+ * works on it, with these layouts:
+ *   X (sum T_b, F, M) PACKED: problem b holds frames [off_b, off_b + T_b), off_b = T_0 + ... + T_{b-1}; host complex64 /
+ *   complex128 (oiva_batch_set_x_host) or a borrowed packed complex64 device array (oiva_batch_set_x_dev).
+ *   Y (sum T_b, F, K) packed the same way (oiva_batch_demix).
+ *   W0, W (B, F, M, K), Cx (B, F, M, M), status[B]: as a dense batch's.
+ * Problem b gets the bits of a dense batch of its own T_b frames (oiva_batch_create with B = 1, T = T_b): every order of summation
+ * and every split is a function of (bin, frame, T_b).  The iteration is still four launches whatever B, replayed from one
+ * linear captured graph.  oiva_batch_ogive_begin and oiva_batch_ogive_iterate return OIVA_ERR_ARG on a ragged batch.
+ */
+oiva_status oiva_batch_create_ragged(oiva_batch **out, int device, int B, const int *frames, int F, int M, int K, int model,
+                                     void *stream);
+
+/*
  * STFT analysis / synthesis on the GPU (hipFFT): time-domain audio in and out next to the solver.
  * Replaces, in the reference's drivers, pra.transform.analysis(mics_signals.T, framesize, framesize // 2, win=win_a)
  * (overiva_oneshot.py:293-295, overiva_sim.py:206-207) and pra.transform.synthesis(Y, framesize, framesize // 2,

@@ -1,5 +1,6 @@
-"""``overiva_batch()``: many same-shape OverIVA problems per set of launches (``oiva_batch``, csrc/kernels_batch.hip), and
-``ogive_batch()``, the same for OGIVE with a stopping rule per problem (csrc/kernels_ogive_batch.hip).
+"""``overiva_batch()``: many same-shape OverIVA problems per set of launches (``oiva_batch``, csrc/kernels_batch.hip),
+``ogive_batch()``, the same for OGIVE with a stopping rule per problem (csrc/kernels_ogive_batch.hip), and
+``overiva_batch_ragged()``, OverIVA on problems of different frame counts in one batch (csrc/kernels_ragged.hip).
 
 The reference's own calls separate 10-second rooms -- 2049 bins x 160-235 frames x 2-8 microphones -- one ``overiva()`` call
 each, and a single call of that size leaves the GPU mostly idle (every kernel is a few workgroup lifetimes long, and a launch
@@ -28,7 +29,8 @@ _info = {}
 
 def last_batch_info():
     """what the last ``overiva_batch()`` or ``ogive_batch()`` call ran: ``{"precision": "precise", "batched": B, ...}``; after
-    ``ogive_batch()`` also ``epochs`` (B ints: epochs each problem ran) and ``converged`` (B bools: its stopping rule fired)"""
+    ``ogive_batch()`` also ``epochs`` (B ints: epochs each problem ran) and ``converged`` (B bools: its stopping rule fired); after
+    ``overiva_batch_ragged()`` also ``ragged`` (True) and ``frames`` (B ints), ``shape`` then holding the largest T"""
     return dict(_info)
 
 
@@ -314,3 +316,150 @@ def ogive_batch(X, n_iter=4000, step_size=0.1, tol=1e-3, update="demix", proj_ba
         if return_filters:
             return Y, w.astype(dtype, copy=False)
         return Y
+
+
+class RaggedBatchPlan(BatchPlan):
+    """Owns the device state of B problems of ``frames[b]`` x F x M with K sources (``oiva_batch_create_ragged``).
+
+    The stages are ``BatchPlan``'s.  X is packed: problem b's frames follow problem b - 1's, (sum T_b, F, M); ``set_x`` takes
+    the list of B (T_b, F, M) arrays or the packed array, ``set_x_device`` borrows a packed complex64 device array, and
+    ``demix`` returns the list of B (T_b, F, K) arrays.  W, ``set_w``'s W0 and ``status`` are (B, ...) as for a dense batch.
+    OGIVE does not run on a ragged batch: ``ogive_begin`` / ``ogive_iterate`` raise."""
+
+    def __init__(self, frames, F, M, K, model="laplace", device=None, stream=None):
+        if model not in _lib.MODEL_IDS:
+            raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
+        self.frames = [int(t) for t in frames]
+        self.lib = _lib.load()
+        self.B, self.F, self.M, self.K = len(self.frames), int(F), int(M), int(K)
+        self.T = max(self.frames) if self.frames else 0
+        self.model = model
+        self.device = get_device() if device is None else int(device)
+        self.offsets = np.concatenate([[0], np.cumsum(self.frames)]).astype(int)
+        fr = (C.c_int * self.B)(*self.frames)
+        h = C.c_void_p()
+        _lib.check(self.lib.oiva_batch_create_ragged(C.byref(h), self.device, self.B, fr, self.F, self.M, self.K,
+                                                     _lib.MODEL_IDS[model], C.c_void_p(stream) if stream else None))
+        self.h = h
+        self._keep = None
+
+    @property
+    def shape(self):
+        """shape of the packed X"""
+        return (int(self.offsets[-1]), self.F, self.M)
+
+    def set_x(self, X):
+        """X: the list of B (T_b, F, M) arrays or the packed (sum T_b, F, M) array, complex64 or complex128 (complex128 is
+        converted on the device)"""
+        if isinstance(X, (list, tuple)):
+            if len(X) != self.B or any(np.shape(x) != (t, self.F, self.M) for x, t in zip(X, self.frames)):
+                raise ValueError(f"X must be {self.B} arrays of shapes (T_b, {self.F}, {self.M}), T_b = {self.frames}")
+            dt = np.complex128 if any(np.asarray(x).dtype == np.complex128 for x in X) else np.complex64
+            X = np.concatenate([np.asarray(x, dtype=dt) for x in X], axis=0)
+        BatchPlan.set_x(self, X)
+
+    def ogive_begin(self, *args, **kwargs):
+        raise ValueError("OGIVE does not run on a ragged batch (use ogive_batch on same-length problems)")
+
+    def ogive_iterate(self, *args, **kwargs):
+        raise ValueError("OGIVE does not run on a ragged batch (use ogive_batch on same-length problems)")
+
+    def demix(self, proj_back=True, dtype=np.complex64):
+        """the list of B arrays Y_b (T_b, F, K), complex64 or complex128"""
+        out = np.empty((int(self.offsets[-1]), self.F, self.K), dtype)
+        _lib.check(self.lib.oiva_batch_demix(self.h, _lib.ptr(out), 1 if out.dtype == np.complex128 else 0, 1 if proj_back else 0))
+        return [out[self.offsets[b]:self.offsets[b + 1]] for b in range(self.B)]
+
+
+def _check_ragged_args(Xs, n_src, model, W0, n_iter):
+    if not hasattr(Xs, "__len__"):
+        raise ValueError("Xs must be a sequence of (n_frames, n_freq, n_chan) arrays")
+    Xs = [np.asarray(x) for x in Xs]
+    if not Xs:
+        raise ValueError("Xs is empty: overiva_batch_ragged needs at least one problem")
+    for b, x in enumerate(Xs):
+        if x.ndim != 3:
+            raise ValueError(f"Xs[{b}] has shape {x.shape}: every problem must be (n_frames, n_freq, n_chan)")
+    dtypes = {x.dtype for x in Xs}
+    if len(dtypes) != 1:
+        raise ValueError(f"the problems have mixed dtypes {sorted(str(d) for d in dtypes)}: give them one complex dtype")
+    dtype = _complex_dtype(Xs[0])
+    F, M = Xs[0].shape[1:]
+    for b, x in enumerate(Xs):
+        if x.shape[1:] != (F, M):
+            raise ValueError(f"Xs[{b}] has {x.shape[1]} bins and {x.shape[2]} channels, Xs[0] {F} and {M}: F and M must agree")
+        if x.shape[0] < 1:
+            raise ValueError(f"Xs[{b}] has {x.shape[0]} frames: every problem needs at least one")
+    if F < 1:
+        raise ValueError("every problem needs at least one frequency bin")
+    if not 1 <= M <= MAX_CHANNELS:
+        raise ValueError(f"overiva_batch_ragged runs on 1..{MAX_CHANNELS} channels, the problems have {M}")
+    B = len(Xs)
+    K = M if n_src is None else n_src
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= M:
+        raise ValueError(f"n_src must be in 1..{M}")
+    if model not in ("laplace", "gauss"):
+        raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
+    if n_iter < 0:
+        raise ValueError("n_iter must be >= 0")
+    if W0 is not None:
+        W0 = np.asarray(W0)
+        try:
+            shared = np.broadcast_shapes(W0.shape, (F, M, K)) == (F, M, K)
+        except ValueError:
+            shared = False
+        if not shared and W0.shape != (B, F, M, K):
+            raise ValueError(f"W0 has shape {W0.shape}: expected one broadcastable to {(F, M, K)} or {(B, F, M, K)}")
+    if sharded.active_group() is not None:
+        raise ValueError("overiva_batch_ragged does not run under enable_bin_sharding(): disable bin sharding for batched calls")
+    return Xs, dtype, int(K)
+
+
+def overiva_batch_ragged(Xs, n_src=None, n_iter=20, proj_back=True, W0=None, model="laplace", init_eig=False, return_filters=False,
+                         callback=None):
+    """
+    ``overiva()`` (reference overiva.py:28-204) on B problems of different frame counts at once.
+
+    Parameters
+    ----------
+    Xs: sequence of B ndarrays (nframes_b, nfrequencies, nchannels), complex
+        STFT representations; nfrequencies, nchannels (1..8) and the dtype are the same for all, nframes_b >= 1 may differ
+    n_src, n_iter, proj_back, model, init_eig, return_filters:
+        as ``overiva()``, the same for every problem
+    W0: ndarray broadcastable to (nfrequencies, nchannels, nsrc) (one start for all), or (batch, nfrequencies, nchannels, nsrc)
+    callback: func
+        Called with the list of current estimates Y_b (nframes_b, nfrequencies, nsrc) at epochs 0, 10, 20, ...
+
+    Returns
+    -------
+    The list of B arrays Y_b (nframes_b, nfrequencies, nsrc) in the dtype of the inputs, or ``(Ys, W)`` with W (batch,
+    nfrequencies, nchannels, nsrc).  Problem b gets exactly the bits of ``overiva_batch(Xs[b][None], ...)`` with the same
+    arguments, whatever the other problems.  A problem whose W ends non-finite raises ``numpy.linalg.LinAlgError`` naming
+    every such problem.
+    """
+    global _info
+    Xs, dtype, K = _check_ragged_args(Xs, n_src, model, W0, n_iter)
+    frames = [x.shape[0] for x in Xs]
+    F, M = Xs[0].shape[1:]
+    with RaggedBatchPlan(frames, F, M, K, model) as plan:
+        plan.set_x(Xs)
+        plan.covariance()
+        if W0 is None and init_eig:
+            plan.set_w_eig()                      # overiva.py:106-109, the device eigensolver per bin
+        else:
+            plan.set_w(W0)
+        epoch = 0
+        while epoch < n_iter:
+            if callback is not None and epoch % 10 == 0:      # overiva.py:142-148
+                callback(plan.demix(proj_back, dtype))
+            step = n_iter - epoch if callback is None else min(n_iter - epoch, 10 - epoch % 10)
+            plan.iterate(step)
+            epoch += step
+        Ys = plan.demix(proj_back, dtype)
+        _info = {"precision": "precise", "batched": len(Xs), "sharded": False, "shape": (max(frames), F, M, K), "ragged": True,
+                 "frames": frames}
+        _overiva_module._last_info = dict(_info)        # (what last_solver_info() reports)
+        W = plan.get_w(np.complex128)               # (raises LinAlgError naming the non-finite problems, overiva.py:182)
+        if return_filters:
+            return Ys, W.astype(dtype, copy=False)
+        return Ys

@@ -1,7 +1,8 @@
 // C ABI of the batched iteration (oiva_batch_*, include/overiva_hip.h): B problems of one shape, up to 8 channels, in the
 // `precise` arithmetic.  Host code only; the kernels that read X or the activations live in kernels_batch.hip, the per-bin
 // stages are the single-problem kernels run on B*F bins.  Batched OGIVE (oiva_batch_ogive_*) runs on a batch created with
-// K = 1, with its own kernels (kernels_ogive_batch.hip) and a stopping rule per problem.
+// K = 1, with its own kernels (kernels_ogive_batch.hip) and a stopping rule per problem.  A ragged batch
+// (oiva_batch_create_ragged) holds problems of different frame counts, packed, and runs the kernels of kernels_ragged.hip.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -37,6 +38,35 @@ constexpr size_t kStageBytes = (size_t)256 << 20;   // staging of complex128 inp
 constexpr int kOgFramesPerSplit = 64;     // frame splits of the OGIVE frame sums: ceil(T / 64), a function of T alone
 constexpr int kOgMinGraphEpochs = 8;      // shorter OGIVE chunks run eagerly
 
+// geometry of the frame-split passes of a problem of T frames: a function of T alone (never of B or of other problems)
+struct FrameGeom {
+    int nsplit, tc;          // covariance pass
+    int tcp, pw_nsplit;      // power pass
+};
+FrameGeom frame_geom(int T) {
+    FrameGeom g;
+    g.nsplit = ceil_div(T, kCovFramesPerSplit);
+    g.tc = ceil_div(T, g.nsplit);
+    g.nsplit = ceil_div(T, g.tc);
+    g.tcp = round_up(ceil_div(T, ceil_div(T, kPowFramesPerSplit)), 4);
+    g.pw_nsplit = ceil_div(T, g.tcp);
+    return g;
+}
+
+// the single-problem plan's statistics geometry (plan.hip, choose_stats_geom) for F bins: Y as overiva() writes it
+CovGeom stats_geom(int T, int F, int K, int n_cu) {
+    CovGeom g{};
+    g.nbg = ceil_div(F, kBinsPerWave);
+    g.kc = 2;
+    const int blocks = g.nbg * ceil_div(K, g.kc);
+    int ns = std::max(1, n_cu * 4 / std::max(1, blocks));
+    ns = std::min(ns, std::max(1, T / 128));
+    ns = std::min(16, ns);
+    g.tc = round_up(ceil_div(T, ns), 16);
+    g.nsplit = ceil_div(T, g.tc);
+    return g;
+}
+
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(int dev) {
@@ -57,7 +87,7 @@ struct oiva_batch {
     int B = 0, T = 0, F = 0, M = 0, K = 0, model = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    const float2* X = nullptr;     // (B, T, F, M)
+    const float2* X = nullptr;     // (B, T, F, M); ragged: (sum T_b, F, M)
     float2* X_owned = nullptr;
     float2* What = nullptr;        // (B*F, M, M) complex64: what the streaming kernels read
     double2* What64 = nullptr;     // (B*F, M, M) complex128: carried between iterations by the float64 update
@@ -68,11 +98,19 @@ struct oiva_batch {
     size_t r_stride = 0;
     float* wscale = nullptr;       // (B, K)
     float* Spart = nullptr;        // [stg.nsplit][F][K][3]: projection-back sums of one problem at a time
-    float2* Y = nullptr;           // (B, T, F, K), allocated on first demix
+    float2* Y = nullptr;           // (B, T, F, K), allocated on first demix; ragged: (sum T_b, F, K)
     double2* Y128 = nullptr;
     int nsplit = 1, tc = 1;        // covariance pass
     int kp = 1, pw_nsplit = 1, tcp = 4, nb = 1;   // power pass
     CovGeom stg{};                 // projection-back statistics (the single-problem plan's geometry for F bins)
+    // ragged batch: T is the largest T_b, nsplit / pw_nsplit / tcp the largest over the problems (the grids); every problem's
+    // own geometry is in its record (host copy `probs`, device copy `probs_dev`) and stgs[p] is its statistics geometry
+    bool ragged = false;
+    size_t frames_total = 0;       // sum of T_b (B * T for a dense batch)
+    int rblocks = 1;               // largest rsum_blocks(T_b)
+    std::vector<RaggedProblem> probs;
+    std::vector<CovGeom> stgs;
+    RaggedProblem* probs_dev = nullptr;
     bool have_x = false, have_cx = false, have_w = false;
     std::vector<std::pair<int, hipGraphExec_t>> graphs;
     hipEvent_t ev[5] = {};
@@ -123,6 +161,7 @@ UpdateArgs update_args(oiva_batch* b, bool init_only) {
     a.use_double = 1;
     a.layout = 0;
     a.wscale_bins = b->F;
+    a.ragged = b->probs_dev;           // (nullptr for a dense batch)
     return a;
 }
 
@@ -130,12 +169,26 @@ UpdateArgs update_args(oiva_batch* b, bool init_only) {
 int stage(oiva_batch* b, int s) {
     switch (s) {
         case 0:
+            if (b->ragged) {
+                HIP_TRY(launch_ragged_power(b->stream, b->X, b->What, b->Ppart, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit,
+                                            b->tcp));
+                break;
+            }
             HIP_TRY(launch_batch_power(b->stream, b->X, b->What, b->Ppart, b->B, b->T, b->F, b->M, b->K, b->kp, b->pw_nsplit, b->tcp));
             break;
         case 1:
+            if (b->ragged) {
+                HIP_TRY(launch_ragged_activation(b->stream, b->Ppart, b->nb, b->R, b->probs_dev, b->B, b->K, b->model, b->F, b->rblocks));
+                break;
+            }
             HIP_TRY(launch_batch_activation(b->stream, b->Ppart, b->nb, b->R, b->r_stride, b->B, b->T, b->K, b->model, b->F));
             break;
         case 2:
+            if (b->ragged) {
+                HIP_TRY(launch_ragged_cov(b->stream, b->X, b->R, b->probs_dev, b->wscale, b->model, b->Vpart, b->B, b->F, b->M, b->K,
+                                          b->nsplit));
+                break;
+            }
             HIP_TRY(launch_batch_cov(b->stream, b->X, b->R, b->r_stride, b->wscale, b->model, b->Vpart, b->B, b->T, b->F, b->M, b->K,
                                      b->nsplit, b->tc));
             break;
@@ -213,7 +266,7 @@ int download_w(oiva_batch* b, std::vector<double2>& wh, std::vector<int>& bad) {
 void free_all(oiva_batch* b) {
     (void)drop_graphs(b);
     for (void* q : {(void*)b->X_owned, (void*)b->What, (void*)b->What64, (void*)b->Cx, (void*)b->Vpart, (void*)b->Ppart, (void*)b->R,
-                    (void*)b->wscale, (void*)b->Spart, (void*)b->Y, (void*)b->Y128})
+                    (void*)b->wscale, (void*)b->Spart, (void*)b->Y, (void*)b->Y128, (void*)b->probs_dev})
         if (q) (void)hipFree(q);
     for (void* q : b->og_bufs) (void)hipFree(q);
     for (hipEvent_t& e : b->ev)
@@ -221,18 +274,8 @@ void free_all(oiva_batch* b) {
     if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
 }
 
-}  // namespace
-
-extern "C" {
-
-int oiva_batch_create(oiva_batch** out, int device, int B, int T, int F, int M, int K, int model, void* stream) {
-    NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
-    *out = nullptr;
-    NEED(B >= 1 && T >= 1 && F >= 1, OIVA_ERR_ARG, "B, T and F must be >= 1");
-    NEED(M >= 1 && M <= kBatchMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
-    NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "number of sources must be in 1..M");
-    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
-    NEED((double)B * T * F * M < 4e9, OIVA_ERR_ARG, "batch too large");
+// a dense batch of T frames (frames == nullptr), or a ragged one of frames[p] frames per problem (T = the largest); arguments checked
+int create_batch(oiva_batch** out, int device, int B, int T, const int* frames, int F, int M, int K, int model, void* stream) {
     DeviceGuard guard(device);
     oiva_batch* b = new oiva_batch;
     b->device = device;
@@ -255,12 +298,12 @@ int oiva_batch_create(oiva_batch** out, int device, int B, int T, int F, int M, 
     }
     for (hipEvent_t& e : b->ev) TRY_CREATE(hipEventCreate(&e));
     // geometry: functions of T, F, M, K alone (never of B)
-    b->nsplit = ceil_div(T, kCovFramesPerSplit);
-    b->tc = ceil_div(T, b->nsplit);
-    b->nsplit = ceil_div(T, b->tc);
+    const FrameGeom fg = frame_geom(T);
+    b->nsplit = fg.nsplit;
+    b->tc = fg.tc;
     b->kp = pow_sources_per_pass(M, K);
-    b->tcp = round_up(ceil_div(T, ceil_div(T, kPowFramesPerSplit)), 4);
-    b->pw_nsplit = ceil_div(T, b->tcp);
+    b->tcp = fg.tcp;
+    b->pw_nsplit = fg.pw_nsplit;
     b->nb = ceil_div(F, kBinsPerWave * kWaves);
     b->r_stride = r_buffer_bytes(T, K) / sizeof(float);
     b->osplit = ceil_div(T, kOgFramesPerSplit);
@@ -268,31 +311,90 @@ int oiva_batch_create(oiva_batch** out, int device, int B, int T, int F, int M, 
     b->osplit = ceil_div(T, b->otc);
     int n_cu = 256;
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
-    {   // the single-problem plan's statistics geometry (plan.hip, choose_stats_geom) for F bins: Y as overiva() writes it
-        CovGeom g;
-        g.nbg = ceil_div(F, kBinsPerWave);
-        g.kc = 2;
-        const int blocks = g.nbg * ceil_div(K, g.kc);
-        int ns = std::max(1, n_cu * 4 / std::max(1, blocks));
-        ns = std::min(ns, std::max(1, T / 128));
-        ns = std::min(16, ns);
-        g.tc = round_up(ceil_div(T, ns), 16);
-        g.nsplit = ceil_div(T, g.tc);
-        b->stg = g;
+    b->stg = stats_geom(T, F, K, n_cu);
+    b->frames_total = (size_t)B * T;
+    size_t ppart_floats = (size_t)B * b->nb * T * K, r_floats = (size_t)B * b->r_stride;
+    int spart_splits = b->stg.nsplit;
+    if (frames) {
+        // ragged: every problem's record from its own T_b; the grids (nsplit, pw_nsplit, tcp, rblocks) take the largest
+        b->ragged = true;
+        b->r_stride = 0;
+        b->probs.resize(B);
+        b->stgs.resize(B);
+        b->nsplit = b->pw_nsplit = b->tcp = b->rblocks = 1;
+        size_t x_off = 0, p_off = 0, r_off = 0;
+        for (int p = 0; p < B; ++p) {
+            const int Tb = frames[p];
+            const FrameGeom g = frame_geom(Tb);
+            RaggedProblem& d = b->probs[p];
+            d.x_off = x_off, d.p_off = p_off, d.r_off = r_off;
+            d.inv_T = 1. / (double)Tb;
+            d.T = Tb;
+            d.tcp = g.tcp, d.pw_nsplit = g.pw_nsplit, d.nsplit = g.nsplit, d.tc = g.tc;
+            x_off += Tb;
+            p_off += (size_t)b->nb * Tb * K;
+            r_off += r_buffer_bytes(Tb, K) / sizeof(float);
+            b->stgs[p] = stats_geom(Tb, F, K, n_cu);
+            b->nsplit = std::max(b->nsplit, g.nsplit);
+            b->pw_nsplit = std::max(b->pw_nsplit, g.pw_nsplit);
+            b->tcp = std::max(b->tcp, g.tcp);
+            b->rblocks = std::max(b->rblocks, rsum_blocks(Tb));
+            spart_splits = std::max(spart_splits, b->stgs[p].nsplit);
+        }
+        b->frames_total = x_off;
+        ppart_floats = p_off;
+        r_floats = r_off;
+        TRY_CREATE(hipMalloc((void**)&b->probs_dev, (size_t)B * sizeof(RaggedProblem)));
+        TRY_CREATE(hipMemcpy(b->probs_dev, b->probs.data(), (size_t)B * sizeof(RaggedProblem), hipMemcpyHostToDevice));
     }
     const size_t MM = (size_t)M * M;
     TRY_CREATE(hipMalloc((void**)&b->What, nbins(b) * MM * sizeof(float2)));
     TRY_CREATE(hipMalloc((void**)&b->What64, nbins(b) * MM * sizeof(double2)));
     TRY_CREATE(hipMalloc((void**)&b->Cx, nbins(b) * MM * sizeof(double)));
     TRY_CREATE(hipMalloc((void**)&b->Vpart, ((size_t)b->nsplit * nbins(b) * K * MM + 2) * sizeof(double)));   // sum_vpart reads idx + 1
-    TRY_CREATE(hipMalloc((void**)&b->Ppart, (size_t)B * b->nb * T * K * sizeof(float)));
-    TRY_CREATE(hipMalloc((void**)&b->R, (size_t)B * b->r_stride * sizeof(float)));
-    TRY_CREATE(hipMemset(b->R, 0, (size_t)B * b->r_stride * sizeof(float)));      // (the pad rows behind every problem's r)
+    TRY_CREATE(hipMalloc((void**)&b->Ppart, ppart_floats * sizeof(float)));
+    TRY_CREATE(hipMalloc((void**)&b->R, r_floats * sizeof(float)));
+    TRY_CREATE(hipMemset(b->R, 0, r_floats * sizeof(float)));      // (the pad rows behind every problem's r)
     TRY_CREATE(hipMalloc((void**)&b->wscale, (size_t)B * K * sizeof(float)));
-    TRY_CREATE(hipMalloc((void**)&b->Spart, (size_t)b->stg.nsplit * F * K * 3 * sizeof(float)));
+    TRY_CREATE(hipMalloc((void**)&b->Spart, (size_t)spart_splits * F * K * 3 * sizeof(float)));
 #undef TRY_CREATE
     *out = b;
     return OIVA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int oiva_batch_create(oiva_batch** out, int device, int B, int T, int F, int M, int K, int model, void* stream) {
+    NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
+    *out = nullptr;
+    NEED(B >= 1 && T >= 1 && F >= 1, OIVA_ERR_ARG, "B, T and F must be >= 1");
+    NEED(M >= 1 && M <= kBatchMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
+    NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "number of sources must be in 1..M");
+    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
+    NEED((double)B * T * F * M < 4e9, OIVA_ERR_ARG, "batch too large");
+    return create_batch(out, device, B, T, nullptr, F, M, K, model, stream);
+}
+
+oiva_status oiva_batch_create_ragged(oiva_batch** out, int device, int B, const int* frames, int F, int M, int K, int model,
+                                     void* stream) {
+    NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
+    *out = nullptr;
+    NEED(frames != nullptr, OIVA_ERR_ARG, "null frames");
+    NEED(B >= 1 && F >= 1, OIVA_ERR_ARG, "B and F must be >= 1");
+    NEED(M >= 1 && M <= kBatchMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
+    NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "number of sources must be in 1..M");
+    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
+    double total = 0.;
+    int tmax = 0;
+    for (int p = 0; p < B; ++p) {
+        NEED(frames[p] >= 1, OIVA_ERR_ARG, "every problem needs T >= 1 frames (problem " + std::to_string(p) + ")");
+        total += frames[p];
+        tmax = std::max(tmax, frames[p]);
+    }
+    NEED(total * F * M < 4e9 && (double)B * F * M * M * K * ceil_div(tmax, kCovFramesPerSplit) < 4e9, OIVA_ERR_ARG, "batch too large");
+    return create_batch(out, device, B, tmax, frames, F, M, K, model, stream);
 }
 
 int oiva_batch_destroy(oiva_batch* b) {
@@ -307,7 +409,7 @@ int oiva_batch_destroy(oiva_batch* b) {
 int oiva_batch_set_x_host(oiva_batch* b, const void* X, int f64) {
     NEED(b && X, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(b->device);
-    const size_t n = (size_t)b->B * b->T * b->F * b->M;
+    const size_t n = b->frames_total * b->F * b->M;
     if (!b->X_owned) HIP_TRY(hipMalloc((void**)&b->X_owned, n * sizeof(float2)));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (f64) {
@@ -356,6 +458,12 @@ int oiva_batch_covariance(oiva_batch* b) {
     NEED(b->have_x, OIVA_ERR_STATE, "X not set");
     DeviceGuard guard(b->device);
     // unit weights, one "source": partials [nsplit][B*F][1][M*M], added in split order and divided by T (overiva.py:87)
+    if (b->ragged) {       // (problem b: its own nsplit_b partials and 1 / T_b)
+        HIP_TRY(launch_ragged_cov(b->stream, b->X, nullptr, b->probs_dev, nullptr, b->model, b->Vpart, b->B, b->F, b->M, 1, b->nsplit));
+        HIP_TRY(launch_ragged_sum_parts(b->stream, b->Vpart, b->probs_dev, b->Cx, b->B, b->F, b->M));
+        b->have_cx = true;
+        return OIVA_OK;
+    }
     HIP_TRY(launch_batch_cov(b->stream, b->X, nullptr, 0, nullptr, b->model, b->Vpart, b->B, b->T, b->F, b->M, 1, b->nsplit, b->tc));
     HIP_TRY(launch_sum_parts(b->stream, b->Vpart, true, b->nsplit, b->Cx, (long long)nbins(b) * b->M * b->M, 1. / (double)b->T));
     b->have_cx = true;
@@ -425,16 +533,19 @@ int oiva_batch_demix(oiva_batch* b, void* Y_host, int f64, int proj_back) {
     int rc = check_ready(b);
     if (rc) return rc;
     DeviceGuard guard(b->device);
-    const int T = b->T, F = b->F, M = b->M, K = b->K;
-    const size_t ny = (size_t)b->B * T * F * K;
+    const int F = b->F, M = b->M, K = b->K;
+    const size_t ny = b->frames_total * F * K;
     if (!b->Y) HIP_TRY(hipMalloc((void**)&b->Y, ny * sizeof(float2)));
-    // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0])
+    // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0]);
+    // a ragged batch's problem at its packed frame offset with the statistics geometry of its own T_b
     for (int p = 0; p < b->B; ++p) {
-        const float2* Xb = b->X + (size_t)p * T * F * M;
+        const int T = b->ragged ? b->probs[p].T : b->T;
+        const size_t t0 = b->ragged ? b->probs[p].x_off : (size_t)p * T;
+        const CovGeom& stg = b->ragged ? b->stgs[p] : b->stg;
+        const float2* Xb = b->X + t0 * F * M;
         const float2* Wb = b->What + (size_t)p * F * M * M;
-        if (proj_back) HIP_TRY(launch_demix_stats(b->stream, Xb, Wb, b->Spart, T, F, M, K, b->stg));
-        HIP_TRY(launch_demix_write(b->stream, Xb, Wb, proj_back ? b->Spart : nullptr, b->stg.nsplit, b->Y + (size_t)p * T * F * K, T, F,
-                                   M, K));
+        if (proj_back) HIP_TRY(launch_demix_stats(b->stream, Xb, Wb, b->Spart, T, F, M, K, stg));
+        HIP_TRY(launch_demix_write(b->stream, Xb, Wb, proj_back ? b->Spart : nullptr, stg.nsplit, b->Y + t0 * F * K, T, F, M, K));
     }
     if (f64) {
         if (!b->Y128) HIP_TRY(hipMalloc((void**)&b->Y128, ny * sizeof(double2)));
@@ -541,6 +652,8 @@ oiva_status oiva_batch_get_cx(oiva_batch* b, void* Cx_host, int f64) {
 }
 
 oiva_status oiva_batch_ogive_begin(oiva_batch* b, int update_mode, int model) {
+    NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    NEED(!b->ragged, OIVA_ERR_ARG, "OGIVE is not supported on a ragged batch");
     int rc = check_ready(b);
     if (rc) return rc;
     NEED(b->K == 1, OIVA_ERR_ARG, "OGIVE extracts one source: create the batch with K = 1");
@@ -598,6 +711,8 @@ oiva_status oiva_batch_ogive_begin(oiva_batch* b, int update_mode, int model) {
 
 oiva_status oiva_batch_ogive_iterate(oiva_batch* b, int first_epoch, int n, double step_size, double tol, int* epochs_run, int* converged,
                                  double* max_delta) {
+    NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    NEED(!b->ragged, OIVA_ERR_ARG, "OGIVE is not supported on a ragged batch");
     int rc = check_ready(b);
     if (rc) return rc;
     NEED(b->og_ready, OIVA_ERR_STATE, "call oiva_batch_ogive_begin first");

@@ -288,13 +288,14 @@ __global__ __launch_bounds__(kBlock) void update_sq_kernel(UpdateArgs a) {
     if (K < M) Tm = sq.matmul(B, C, M);
 
     const int nsrc = a.init_only ? 0 : K;
-    const R invT = R(1) / R(a.T);
+    const R invT = R(1) / R(update_frames(a, f));      // (a ragged batch: T and split count of the bin's own problem)
+    const int nsplit = update_nsplit(a, f);
     // V_s[i][j] = (1/T) * fixed-order fp64 sum of the frame-split partials (reduction tail of overiva.py:179)
     auto load_v = [&](int s) {
         Cx<R> V = zero;
         if (in) {
             double sr, si;
-            sum_vpart(a.Vpart, a.vpart_f64, ((size_t)f * K + s) * NA + off, (size_t)a.F * K * NA, a.nsplit, sgn != 0.f, sr, si);
+            sum_vpart(a.Vpart, a.vpart_f64, ((size_t)f * K + s) * NA + off, (size_t)a.F * K * NA, nsplit, sgn != 0.f, sr, si);
             V.re = R(sr) * invT;
             V.im = R(si) * R(sgn) * invT;
         }
@@ -411,14 +412,15 @@ __global__ __launch_bounds__(kBlock) void update_bg_kernel(UpdateArgs a) {
         if (sgn != 0.f) C.im = R(sgn * p[1]);
     }
     // V_s and V_s^-1 for all sources (off the chain); V_s[i][j] = (1/T) * fixed-order fp64 sum of the partials
-    const R invT = R(1) / R(a.T);
+    const R invT = R(1) / R(update_frames(a, f));      // (a ragged batch: T and split count of the bin's own problem)
+    const int nsplit = update_nsplit(a, f);
     Cx<R> V[K];
 #pragma unroll
     for (int s = 0; s < K; ++s) {
         V[s] = eye;
         if (in) {
             double sr, si;
-            sum_vpart(a.Vpart, a.vpart_f64, ((size_t)f * K + s) * NA + off, (size_t)a.F * K * NA, a.nsplit, sgn != 0.f, sr, si);
+            sum_vpart(a.Vpart, a.vpart_f64, ((size_t)f * K + s) * NA + off, (size_t)a.F * K * NA, nsplit, sgn != 0.f, sr, si);
             V[s] = {R(sr) * invT, R(si) * R(sgn) * invT};
         }
     }
@@ -464,12 +466,13 @@ __global__ __launch_bounds__(kBlock) void update_det_kernel(UpdateArgs a) {
     int off = 0;
     float sgn = 0.f;
     if (in) herm_offsets(M, i, j, off, sgn);
-    const R invT = R(1) / R(a.T);
+    const R invT = R(1) / R(update_frames(a, f));      // (a ragged batch: T and split count of the bin's own problem)
+    const int nsplit = update_nsplit(a, f);
     auto load_v = [&](int s) {
         Cx<R> V = eye;
         if (in) {
             double sr, si;
-            sum_vpart(a.Vpart, a.vpart_f64, ((size_t)f * M + s) * NA + off, (size_t)a.F * M * NA, a.nsplit, sgn != 0.f, sr, si);
+            sum_vpart(a.Vpart, a.vpart_f64, ((size_t)f * M + s) * NA + off, (size_t)a.F * M * NA, nsplit, sgn != 0.f, sr, si);
             V = {R(sr) * invT, R(si) * R(sgn) * invT};
         }
         return V;
@@ -559,12 +562,13 @@ __global__ __launch_bounds__(kBlock) void update_gram_kernel(UpdateArgs a) {
         C.re = R(p[0]);
         if (sgn != 0.f) C.im = R(sgn * p[1]);
     }
-    const R invT = R(1) / R(a.T);
+    const R invT = R(1) / R(update_frames(a, f));      // (a ragged batch: T and split count of the bin's own problem)
+    const int nsplit = update_nsplit(a, f);
     auto load_v = [&](int s) {
         Cx<R> V = eye;
         if (in) {
             double sr, si;
-            sum_vpart(a.Vpart, a.vpart_f64, ((size_t)f * K + s) * NA + off, (size_t)a.F * K * NA, a.nsplit, sgn != 0.f, sr, si);
+            sum_vpart(a.Vpart, a.vpart_f64, ((size_t)f * K + s) * NA + off, (size_t)a.F * K * NA, nsplit, sgn != 0.f, sr, si);
             V = {R(sr) * invT, R(si) * R(sgn) * invT};
         }
         return V;

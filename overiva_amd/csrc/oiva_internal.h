@@ -170,6 +170,19 @@ hipError_t launch_activation(hipStream_t s, const float* parts, int nparts, floa
 // fixed-order float64 sum of partial buffers (float32, or float64 when f64): out[e] = scale * sum_i parts[i][e]
 hipError_t launch_sum_parts(hipStream_t s, const void* parts, bool f64, int nparts, double* out, long long n, double scale);
 
+// One problem of a ragged batch (oiva_batch_create_ragged, kernels_ragged.hip): where its data lie in the packed buffers and
+// the geometry of its passes.  Every field is a function of the problem's own frame count T (and of F, M, K), never of B or
+// of the other problems: the same numbers as a dense batch of T frames uses (batch.hip, frame_geom).
+struct RaggedProblem {
+    size_t x_off;     // first frame of the problem in the packed (sum T, F, M) X / (sum T, F, K) Y
+    size_t p_off;     // its partial powers [nb][T][K] in Ppart (floats)
+    size_t r_off;     // its activation buffer of r_buffer_bytes(T, K) in R (floats; even, so the float64 sums stay aligned)
+    double inv_T;     // 1 / T as the host forms it (the scale of the input covariance)
+    int T;
+    int tcp, pw_nsplit;   // power pass: frames per split, splits
+    int nsplit, tc;       // covariance pass: splits, frames per split
+};
+
 // Per-bin sequential update, overiva.py:181-190 (+ :161-167 W scaling, + :96-98 J init when init_only).
 struct UpdateArgs {
     float2* What;         // (F,M,M) in/out (complex64: what the streaming kernels read)
@@ -184,7 +197,15 @@ struct UpdateArgs {
     int use_double;       // per-bin algebra in fp64
     int layout;           // 0: one lane per matrix element (M <= 8), 1: one lane per matrix row
     int wscale_bins = 0;  // batched plans (kernels_batch.hip): F is B problems of this many bins each and wscale is (B, K); 0: (K)
+    // ragged batches (kernels_ragged.hip): the (B) problem records; bin f belongs to problem f / wscale_bins, whose V is the sum of
+    // ITS nsplit partials scaled by 1 / ITS T (T and nsplit above are then the batch's largest).  nullptr on every other path.
+    const RaggedProblem* ragged = nullptr;
 };
+// frame count and covariance split count behind bin f's V (the M <= 8 float64 update forms the batches dispatch)
+__device__ __forceinline__ int update_frames(const UpdateArgs& a, int f) { return a.ragged ? a.ragged[f / a.wscale_bins].T : a.T; }
+__device__ __forceinline__ int update_nsplit(const UpdateArgs& a, int f) {
+    return a.ragged ? a.ragged[f / a.wscale_bins].nsplit : a.nsplit;
+}
 // the pending scale of column i of bin f (overiva.py:163 / :167): the bin's problem's row of wscale
 __device__ __forceinline__ float wscale_at(const UpdateArgs& a, int f, int i) {
     return a.wscale[(a.wscale_bins > 0 ? (size_t)(f / a.wscale_bins) * a.K : 0) + i];
@@ -329,6 +350,19 @@ hipError_t launch_batch_activation(hipStream_t s, const float* parts, int nparts
                                    int model, int F);
 hipError_t launch_batch_cov(hipStream_t s, const float2* X, const float* R, size_t r_stride, float* wscale, int model, double* Vpart,
                             int B, int T, int F, int M, int K, int nsplit, int tc);
+
+// The ragged batch (kernels_ragged.hip, batch.hip): B problems of T_b frames each, one F, M <= 8, K.  X packed (sum T, F, M);
+// What, Cx, Vpart, wscale as the dense batch's (Vpart [max nsplit][B*F][K][M*M]: problem b writes and the update reads its
+// first nsplit_b splits only); Ppart and R at the records' offsets.  Grids are sized by the largest problem; the workgroups
+// past a problem's own extent return at entry.
+hipError_t launch_ragged_power(hipStream_t s, const float2* X, const float2* What, float* Ppart, const RaggedProblem* prob, int B, int F,
+                               int M, int K, int kp, int max_pw_nsplit, int max_tcp);
+hipError_t launch_ragged_activation(hipStream_t s, const float* parts, int nparts, float* R, const RaggedProblem* prob, int B, int K,
+                                    int model, int F, int max_rblocks);
+hipError_t launch_ragged_cov(hipStream_t s, const float2* X, const float* R, const RaggedProblem* prob, float* wscale, int model,
+                             double* Vpart, int B, int F, int M, int K, int max_nsplit);
+// Cx [B*F][M*M] = (1 / T_b) * the sum of problem b's own nsplit_b unit-weight partials (as launch_sum_parts for one problem)
+hipError_t launch_ragged_sum_parts(hipStream_t s, const double* parts, const RaggedProblem* prob, double* Cx, int B, int F, int M);
 
 // Batched OGIVE (kernels_ogive_batch.hip, batch.hip): B problems of one shape, <= 8 channels, K = 1, `precise` arithmetic.
 //   bin: OgiveState of the B*F bins (bin index = problem * F + bin; its ctrl / maxdelta are only the scratch ogive_init_kernel
