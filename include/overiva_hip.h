@@ -448,6 +448,38 @@ int oiva_stft_shape(oiva_stft *p, int *n_frames, int *n_freq);
 int oiva_stft_analysis(oiva_stft *p, const float *x_host, void *X_host, void **X_dev);
 int oiva_stft_synthesis(oiva_stft *p, const void *Y_host, int n_chan, float *y_host);
 
+/*
+ * Audio in, audio out for a batch (overiva_amd/separate.py, separate_batch): the STFT of B rooms of different lengths in one
+ * set of launches, X written on the device in the layout of the batched solvers, Y read from the batch's device array.
+ *   packed audio x (sum n_b, M) float32, host: room b holds samples [s_b, s_b + n_b), s_b = n_0 + ... + n_{b-1}
+ *   X (sum T_b, F, M) complex64, device, T_b = n_b / hop, F = frame / 2 + 1: the packed layout oiva_batch_set_x_dev borrows for a
+ *     ragged batch of frames T_b, and a dense batch's (B, T, F, M) when all T_b agree
+ *   packed y (sum T_b * hop, K) float32, host
+ * Framing convention and arithmetic are oiva_stft's, room by room: zeros before EACH room's first sample, no frame and no
+ * overlap-add across a room boundary.  win_a / win_s: `frame` floats or NULL (rectangular).  stream: NULL (the handle owns one) or
+ * a hipStream_t to run on.  Every entry checks its arguments before any device call (OIVA_ERR_ARG: null pointers, B < 1, a room
+ * shorter than one hop, odd frame, hop outside 1..frame, M outside 1..8, K outside 1..M, 2^31 elements or more in a room's
+ * buffers, 2^63 bytes or more in all) and is synchronous.
+ *   oiva_bstft_analysis      : upload, framing + window, one batched R2C, transpose; *X_dev is valid until the next analysis on
+ *                              the handle or its destruction
+ *   oiva_bstft_synthesis_dev : Y_dev (sum T_b, F, K) complex64 on the device -> packed y on the host
+ *   oiva_bstft_phase_ms      : ms[8] of the last analysis (upload, framing, R2C, transpose) and the last synthesis (transpose, C2R,
+ *                              overlap-add, download), from events on the handle's stream; 0 for a call not made yet
+ *   oiva_batch_demix_dev     : oiva_batch_demix with Y left on the device, (B, T, F, K) or packed (sum T_b, F, K) complex64;
+ *                              *Y_dev is valid until the next demix on the batch or its destruction
+ *   oiva_device_to_host      : plain copy of `bytes` bytes of a device array of this process (tests read X and Y with it)
+ */
+typedef struct oiva_bstft oiva_bstft;
+oiva_status oiva_bstft_create(oiva_bstft **out, int device, int B, const int *n_samples, int M, int frame, int hop,
+                              const float *win_a, const float *win_s, void *stream);
+oiva_status oiva_bstft_destroy(oiva_bstft *p);
+oiva_status oiva_bstft_shape(oiva_bstft *p, int *frames, int *n_freq);
+oiva_status oiva_bstft_analysis(oiva_bstft *p, const float *x_host_packed, void **X_dev);
+oiva_status oiva_bstft_synthesis_dev(oiva_bstft *p, const void *Y_dev, int K, float *y_host_packed);
+oiva_status oiva_bstft_phase_ms(oiva_bstft *p, float *ms);
+oiva_status oiva_batch_demix_dev(oiva_batch *b, int proj_back, void **Y_dev);
+oiva_status oiva_device_to_host(void *host, const void *dev, long long bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,14 @@ SIGNATURES = {
     "oiva_stft_shape": [_vp, C.POINTER(_i), C.POINTER(_i)],
     "oiva_stft_analysis": [_vp, _vp, _vp, C.POINTER(_vp)],
     "oiva_stft_synthesis": [_vp, _vp, _i, _vp],
+    "oiva_bstft_create": [C.POINTER(_vp), _i, _i, C.POINTER(_i), _i, _i, _i, _vp, _vp, _vp],
+    "oiva_bstft_destroy": [_vp],
+    "oiva_bstft_shape": [_vp, C.POINTER(_i), C.POINTER(_i)],
+    "oiva_bstft_analysis": [_vp, _vp, C.POINTER(_vp)],
+    "oiva_bstft_synthesis_dev": [_vp, _vp, _i, _vp],
+    "oiva_bstft_phase_ms": [_vp, _fp],
+    "oiva_batch_demix_dev": [_vp, _i, C.POINTER(_vp)],
+    "oiva_device_to_host": [_vp, _vp, _ll],
 }
 
 

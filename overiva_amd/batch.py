@@ -34,6 +34,30 @@ def last_batch_info():
     return dict(_info)
 
 
+class DeviceBatch:
+    """A complex64 array in the memory of this process's GPU in the layout of a batch plan: ``shape`` (B, T, F, C) when ``dense``,
+    else packed (sum T_b, F, C); ``frames`` the B frame counts, ``n_freq`` F, ``ptr`` the device address, ``owner`` whatever
+    keeps it alive.  ``get_x()`` copies it to the host."""
+
+    def __init__(self, ptr, frames, n_freq, n_chan, dense, owner=None):
+        self.ptr = int(ptr)
+        self.frames = [int(t) for t in frames]
+        self.n_freq, self.n_chan, self.dense = int(n_freq), int(n_chan), bool(dense)
+        self.owner = owner
+        total = sum(self.frames)
+        self.shape = (len(self.frames), self.frames[0], self.n_freq, self.n_chan) if dense else (total, self.n_freq, self.n_chan)
+        self.dtype = np.dtype(np.complex64)
+
+    def get_x(self):
+        """the (B, T, F, C) host array of a dense batch, or the list of B (T_b, F, C) arrays"""
+        out = np.empty(self.shape, np.complex64)
+        _lib.check(_lib.load().oiva_device_to_host(_lib.ptr(out), C.c_void_p(self.ptr), out.nbytes))
+        if self.dense:
+            return out
+        off = np.concatenate([[0], np.cumsum(self.frames)]).astype(int)
+        return [out[off[b]:off[b + 1]] for b in range(len(self.frames))]
+
+
 class BatchPlan:
     """Owns the device state of B problems of shape (T, F, M) with K sources (``oiva_batch``).
 
@@ -131,6 +155,14 @@ class BatchPlan:
         out = np.empty((self.B, self.T, self.F, self.K), dtype)
         _lib.check(self.lib.oiva_batch_demix(self.h, _lib.ptr(out), 1 if out.dtype == np.complex128 else 0, 1 if proj_back else 0))
         return out
+
+    def demix_device(self, proj_back=True):
+        """Y stays on the device: a ``DeviceBatch`` (B, T, F, K), or packed (sum T_b, F, K) on a ragged plan; valid until the next
+        call on the plan (the contract of ``Plan.demix_device``)"""
+        dev = C.c_void_p()
+        _lib.check(self.lib.oiva_batch_demix_dev(self.h, 1 if proj_back else 0, C.byref(dev)))
+        frames = getattr(self, "frames", None)
+        return DeviceBatch(dev.value, [self.T] * self.B if frames is None else frames, self.F, self.K, frames is None, owner=self)
 
     def get_w(self, dtype=np.complex128, check=True):
         """W (B, F, M, K); with ``check`` a non-finite W of any problem raises ``LinAlgError`` naming them"""

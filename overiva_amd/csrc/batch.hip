@@ -263,6 +263,25 @@ int download_w(oiva_batch* b, std::vector<double2>& wh, std::vector<int>& bad) {
     return OIVA_OK;
 }
 
+// Y of every problem into the batch's own device array (allocated on first use), on the batch's stream
+int demix_on_device(oiva_batch* b, int proj_back) {
+    const int F = b->F, M = b->M, K = b->K;
+    const size_t ny = b->frames_total * F * K;
+    if (!b->Y) HIP_TRY(hipMalloc((void**)&b->Y, ny * sizeof(float2)));
+    // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0]);
+    // a ragged batch's problem at its packed frame offset with the statistics geometry of its own T_b
+    for (int p = 0; p < b->B; ++p) {
+        const int T = b->ragged ? b->probs[p].T : b->T;
+        const size_t t0 = b->ragged ? b->probs[p].x_off : (size_t)p * T;
+        const CovGeom& stg = b->ragged ? b->stgs[p] : b->stg;
+        const float2* Xb = b->X + t0 * F * M;
+        const float2* Wb = b->What + (size_t)p * F * M * M;
+        if (proj_back) HIP_TRY(launch_demix_stats(b->stream, Xb, Wb, b->Spart, T, F, M, K, stg));
+        HIP_TRY(launch_demix_write(b->stream, Xb, Wb, proj_back ? b->Spart : nullptr, stg.nsplit, b->Y + t0 * F * K, T, F, M, K));
+    }
+    return OIVA_OK;
+}
+
 void free_all(oiva_batch* b) {
     (void)drop_graphs(b);
     for (void* q : {(void*)b->X_owned, (void*)b->What, (void*)b->What64, (void*)b->Cx, (void*)b->Vpart, (void*)b->Ppart, (void*)b->R,
@@ -533,20 +552,9 @@ int oiva_batch_demix(oiva_batch* b, void* Y_host, int f64, int proj_back) {
     int rc = check_ready(b);
     if (rc) return rc;
     DeviceGuard guard(b->device);
-    const int F = b->F, M = b->M, K = b->K;
-    const size_t ny = b->frames_total * F * K;
-    if (!b->Y) HIP_TRY(hipMalloc((void**)&b->Y, ny * sizeof(float2)));
-    // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0]);
-    // a ragged batch's problem at its packed frame offset with the statistics geometry of its own T_b
-    for (int p = 0; p < b->B; ++p) {
-        const int T = b->ragged ? b->probs[p].T : b->T;
-        const size_t t0 = b->ragged ? b->probs[p].x_off : (size_t)p * T;
-        const CovGeom& stg = b->ragged ? b->stgs[p] : b->stg;
-        const float2* Xb = b->X + t0 * F * M;
-        const float2* Wb = b->What + (size_t)p * F * M * M;
-        if (proj_back) HIP_TRY(launch_demix_stats(b->stream, Xb, Wb, b->Spart, T, F, M, K, stg));
-        HIP_TRY(launch_demix_write(b->stream, Xb, Wb, proj_back ? b->Spart : nullptr, stg.nsplit, b->Y + t0 * F * K, T, F, M, K));
-    }
+    rc = demix_on_device(b, proj_back);
+    if (rc) return rc;
+    const size_t ny = b->frames_total * b->F * b->K;
     if (f64) {
         if (!b->Y128) HIP_TRY(hipMalloc((void**)&b->Y128, ny * sizeof(double2)));
         HIP_TRY(launch_cast_c64_to_c128(b->stream, b->Y, b->Y128, (long long)ny));
@@ -554,6 +562,19 @@ int oiva_batch_demix(oiva_batch* b, void* Y_host, int f64, int proj_back) {
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipMemcpy(Y_host, f64 ? (const void*)b->Y128 : (const void*)b->Y, ny * (f64 ? sizeof(double2) : sizeof(float2)),
                       hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_demix_dev(oiva_batch* b, int proj_back, void** Y_dev) {
+    NEED(Y_dev != nullptr, OIVA_ERR_ARG, "null argument");
+    *Y_dev = nullptr;
+    int rc = check_ready(b);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    rc = demix_on_device(b, proj_back);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    *Y_dev = b->Y;
     return OIVA_OK;
 }
 

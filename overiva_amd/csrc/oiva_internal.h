@@ -386,6 +386,25 @@ hipError_t launch_batch_ogive_framesum(hipStream_t s, const float2* X, const dou
 hipError_t launch_batch_ogive_step(hipStream_t s, const OgiveBatchState& st, const double* Opart, int osplit, int B, int F, int M, double mu,
                                    double tol);
 
+// The batched STFT (kernels_bstft.hip, bstft.hip): the passes around hipFFT for B rooms at once.  One record per room; a dense
+// batch is the special case of equal records.
+struct BstftRoom {
+    long long s_off;   // first sample of the room in the packed (sum n_b, M) audio
+    long long t_off;   // first frame of the room in the packed frame axis (its output starts at sample t_off * hop)
+    int T;             // frames, n / hop
+    int n;             // samples
+};
+int bstft_lds_stride(int C);
+//   frames[(t * C + c) * L + i] = win[i] * x_room[(t_local * hop - (L - hop) + i), c], zero before the room's first sample
+hipError_t launch_bstft_frame(hipStream_t s, const float* x, const float* win, float* frames, const BstftRoom* rooms, int B,
+                              long long frames_total, int C, int L, int hop);
+//   spec (frames_total * C, F) <-> X (frames_total, F, C), tiled through the LDS
+hipError_t launch_bstft_to_tfc(hipStream_t s, const float2* spec, float2* X, long long frames_total, int F, int C);
+hipError_t launch_bstft_from_tfc(hipStream_t s, const float2* Y, float2* spec, long long frames_total, int F, int C);
+//   y packed (n_out = sum T_b * hop, C): per-room overlap-add in increasing t, * 1 / L
+hipError_t launch_bstft_overlap_add(hipStream_t s, const float* frames, const float* win, float* y, const BstftRoom* rooms, int B,
+                                    long long n_out, int C, int L, int hop);
+
 // dense complex128 <-> complex64 conversion on the device
 hipError_t launch_cast_c128_to_c64(hipStream_t s, const double2* in, float2* out, long long n);
 hipError_t launch_cast_c64_to_c128(hipStream_t s, const float2* in, double2* out, long long n);
