@@ -1,6 +1,7 @@
 """``overiva_batch()``: many same-shape OverIVA problems per set of launches (``oiva_batch``, csrc/kernels_batch.hip),
-``ogive_batch()``, the same for OGIVE with a stopping rule per problem (csrc/kernels_ogive_batch.hip), and
-``overiva_batch_ragged()``, OverIVA on problems of different frame counts in one batch (csrc/kernels_ragged.hip).
+``overiva_batch_ragged()``, the same on problems of different frame counts (one path: a same-shape batch is the case of equal
+frame counts), and ``ogive_batch()``, OGIVE on same-shape problems with a stopping rule per problem
+(csrc/kernels_ogive_batch.hip).
 
 The reference's own calls separate 10-second rooms -- 2049 bins x 160-235 frames x 2-8 microphones -- one ``overiva()`` call
 each, and a single call of that size leaves the GPU mostly idle (every kernel is a few workgroup lifetimes long, and a launch
@@ -63,20 +64,33 @@ class BatchPlan:
 
     Stages as ``Plan``'s: ``set_x``, ``covariance``, ``set_w`` / ``set_w_eig``, ``iterate``, ``demix``, ``get_w``; ``status``
     reports which problems hold a non-finite W.  With K = 1, ``ogive_begin`` / ``ogive_iterate`` run OGIVE instead of
-    ``iterate`` (``get_cx`` reads the input covariance for the host's ``init_eig``)."""
+    ``iterate`` (``get_cx`` reads the input covariance for the host's ``init_eig``).
+
+    On the device X and Y are packed along the frames, (sum T_b, F, .): ``frames`` holds the B frame counts (here B times T)
+    and ``offsets`` every problem's first frame."""
+
+    dense = True          # X and Y are handed over as one (B, T, F, .) array
 
     def __init__(self, B, T, F, M, K, model="laplace", device=None, stream=None):
+        self._open([int(T)] * int(B), int(T), F, M, K, model, device, stream)
+
+    def _open(self, frames, T, F, M, K, model, device, stream):
         if model not in _lib.MODEL_IDS:
             raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
         self.lib = _lib.load()
-        self.B, self.T, self.F, self.M, self.K = int(B), int(T), int(F), int(M), int(K)
+        self.frames = frames
+        self.offsets = np.concatenate([[0], np.cumsum(frames)]).astype(int)
+        self.B, self.T, self.F, self.M, self.K = len(frames), T, int(F), int(M), int(K)
         self.model = model
         self.device = get_device() if device is None else int(device)
         h = C.c_void_p()
-        _lib.check(self.lib.oiva_batch_create(C.byref(h), self.device, self.B, self.T, self.F, self.M, self.K,
-                                              _lib.MODEL_IDS[model], C.c_void_p(stream) if stream else None))
+        _lib.check(self._create(h, C.c_void_p(stream) if stream else None))
         self.h = h
         self._keep = None
+
+    def _create(self, h, stream):
+        return self.lib.oiva_batch_create(C.byref(h), self.device, self.B, self.T, self.F, self.M, self.K,
+                                          _lib.MODEL_IDS[self.model], stream)
 
     def close(self):
         if getattr(self, "h", None):
@@ -99,6 +113,10 @@ class BatchPlan:
     def shape(self):
         return (self.B, self.T, self.F, self.M)
 
+    def info(self):
+        """what ``last_batch_info()`` reports after a run on this plan"""
+        return {"precision": "precise", "batched": self.B, "sharded": False, "shape": (self.T, self.F, self.M, self.K)}
+
     def set_x(self, X):
         """X: (B, T, F, M) complex64 or complex128 host array (complex128 is converted on the device)"""
         X = np.asarray(X)
@@ -111,7 +129,7 @@ class BatchPlan:
         _lib.check(self.lib.oiva_batch_set_x_host(self.h, _lib.ptr(X), 1 if X.dtype == np.complex128 else 0))
 
     def set_x_device(self, dev_ptr, keepalive=None):
-        """borrow a dense (B, T, F, M) complex64 device array (e.g. a torch tensor's data_ptr())"""
+        """borrow a complex64 device array of ``shape`` (e.g. a torch tensor's data_ptr())"""
         self._keep = keepalive
         _lib.check(self.lib.oiva_batch_set_x_dev(self.h, C.c_void_p(int(dev_ptr))))
 
@@ -150,19 +168,21 @@ class BatchPlan:
         _lib.check(self.lib.oiva_batch_ogive_iterate(self.h, int(first_epoch), int(n), float(step_size), float(tol), ran, conv, md))
         return np.array(list(ran), dtype=int), np.array(list(conv), dtype=bool), np.array(list(md))
 
-    def demix(self, proj_back=True, dtype=np.complex64):
-        """Y (B, T, F, K) in complex64 or complex128"""
-        out = np.empty((self.B, self.T, self.F, self.K), dtype)
+    def _demix_packed(self, proj_back, dtype):
+        out = np.empty((int(self.offsets[-1]), self.F, self.K), dtype)
         _lib.check(self.lib.oiva_batch_demix(self.h, _lib.ptr(out), 1 if out.dtype == np.complex128 else 0, 1 if proj_back else 0))
         return out
+
+    def demix(self, proj_back=True, dtype=np.complex64):
+        """Y (B, T, F, K) in complex64 or complex128"""
+        return self._demix_packed(proj_back, dtype).reshape(self.B, self.T, self.F, self.K)
 
     def demix_device(self, proj_back=True):
         """Y stays on the device: a ``DeviceBatch`` (B, T, F, K), or packed (sum T_b, F, K) on a ragged plan; valid until the next
         call on the plan (the contract of ``Plan.demix_device``)"""
         dev = C.c_void_p()
         _lib.check(self.lib.oiva_batch_demix_dev(self.h, 1 if proj_back else 0, C.byref(dev)))
-        frames = getattr(self, "frames", None)
-        return DeviceBatch(dev.value, [self.T] * self.B if frames is None else frames, self.F, self.K, frames is None, owner=self)
+        return DeviceBatch(dev.value, self.frames, self.F, self.K, self.dense, owner=self)
 
     def get_w(self, dtype=np.complex128, check=True):
         """W (B, F, M, K); with ``check`` a non-finite W of any problem raises ``LinAlgError`` naming them"""
@@ -187,21 +207,19 @@ class BatchPlan:
         return total.value, dict(zip(_lib.STAGE_NAMES, list(arr)))
 
 
-def _check_args(X, n_src, model, W0, n_iter):
-    X = np.asarray(X)
-    if X.ndim != 4:
-        raise ValueError("X must have shape (batch, n_frames, n_freq, n_chan)")
-    dtype = _complex_dtype(X)
-    B, T, F, M = X.shape
-    if B < 1 or T < 1 or F < 1:
-        raise ValueError(f"X has shape {X.shape}: every dimension must be >= 1")
+def _check_common(name, found, B, F, M, n_src, model, W0, n_iter, update=None, bool_counts=True):
+    """what the three entry points check once the shapes are known (``name`` of the entry point, ``found``: how its message
+    names the channel count it met; ``bool_counts``: ``n_src=True`` is one source, as ``overiva_batch`` has always taken it);
+    returns K"""
     if not 1 <= M <= MAX_CHANNELS:
-        raise ValueError(f"overiva_batch runs on 1..{MAX_CHANNELS} channels, X has {M}")
+        raise ValueError(f"{name} runs on 1..{MAX_CHANNELS} channels, {found} {M}")
     K = M if n_src is None else n_src
-    if not isinstance(K, (int, np.integer)) or not 1 <= K <= M:
+    if (isinstance(K, bool) and not bool_counts) or not isinstance(K, (int, np.integer)) or not 1 <= K <= M:
         raise ValueError(f"n_src must be in 1..{M}")
     if model not in ("laplace", "gauss"):
         raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
+    if update is not None and update not in _ive.UPDATE_IDS:
+        raise ValueError(f"update must be one of {sorted(_ive.UPDATE_IDS)}, got {update!r}")
     if n_iter < 0:
         raise ValueError("n_iter must be >= 0")
     if W0 is not None:
@@ -213,8 +231,82 @@ def _check_args(X, n_src, model, W0, n_iter):
         if not shared and W0.shape != (B, F, M, K):
             raise ValueError(f"W0 has shape {W0.shape}: expected one broadcastable to {(F, M, K)} or {(B, F, M, K)}")
     if sharded.active_group() is not None:
-        raise ValueError("overiva_batch does not run under enable_bin_sharding(): disable bin sharding for batched calls")
-    return X, dtype, int(K)
+        raise ValueError(f"{name} does not run under enable_bin_sharding(): disable bin sharding for batched calls")
+    return int(K)
+
+
+def _check_dense_x(X):
+    X = np.asarray(X)
+    if X.ndim != 4:
+        raise ValueError("X must have shape (batch, n_frames, n_freq, n_chan)")
+    dtype = _complex_dtype(X)
+    B, T, F, M = X.shape
+    if B < 1 or T < 1 or F < 1:
+        raise ValueError(f"X has shape {X.shape}: every dimension must be >= 1")
+    return X, dtype
+
+
+def _check_args(X, n_src, model, W0, n_iter):
+    X, dtype = _check_dense_x(X)
+    B, T, F, M = X.shape
+    return X, dtype, _check_common("overiva_batch", "X has", B, F, M, n_src, model, W0, n_iter)
+
+
+def _check_ogive_args(X, update, model, W0, n_iter):
+    X, dtype = _check_dense_x(X)
+    B, T, F, M = X.shape
+    _check_common("ogive_batch", "X has", B, F, M, 1, model, W0, n_iter, update=update)
+    return X, dtype
+
+
+def _check_ragged_args(Xs, n_src, model, W0, n_iter):
+    if not hasattr(Xs, "__len__"):
+        raise ValueError("Xs must be a sequence of (n_frames, n_freq, n_chan) arrays")
+    Xs = [np.asarray(x) for x in Xs]
+    if not Xs:
+        raise ValueError("Xs is empty: overiva_batch_ragged needs at least one problem")
+    for b, x in enumerate(Xs):
+        if x.ndim != 3:
+            raise ValueError(f"Xs[{b}] has shape {x.shape}: every problem must be (n_frames, n_freq, n_chan)")
+    dtypes = {x.dtype for x in Xs}
+    if len(dtypes) != 1:
+        raise ValueError(f"the problems have mixed dtypes {sorted(str(d) for d in dtypes)}: give them one complex dtype")
+    dtype = _complex_dtype(Xs[0])
+    F, M = Xs[0].shape[1:]
+    for b, x in enumerate(Xs):
+        if x.shape[1:] != (F, M):
+            raise ValueError(f"Xs[{b}] has {x.shape[1]} bins and {x.shape[2]} channels, Xs[0] {F} and {M}: F and M must agree")
+        if x.shape[0] < 1:
+            raise ValueError(f"Xs[{b}] has {x.shape[0]} frames: every problem needs at least one")
+    if F < 1:
+        raise ValueError("every problem needs at least one frequency bin")
+    return Xs, dtype, _check_common("overiva_batch_ragged", "the problems have", len(Xs), F, M, n_src, model, W0, n_iter,
+                                    bool_counts=False)
+
+
+def _run_overiva(plan, X, dtype, n_iter, proj_back, W0, init_eig, return_filters, callback):
+    """the stages of ``overiva()`` (overiva.py:87-199) on a plan: ``overiva_batch()`` and ``overiva_batch_ragged()``"""
+    global _info
+    plan.set_x(X)
+    plan.covariance()
+    if W0 is None and init_eig:
+        plan.set_w_eig()                      # overiva.py:106-109, the device eigensolver per bin
+    else:
+        plan.set_w(W0)
+    epoch = 0
+    while epoch < n_iter:
+        if callback is not None and epoch % 10 == 0:      # overiva.py:142-148
+            callback(plan.demix(proj_back, dtype))
+        step = n_iter - epoch if callback is None else min(n_iter - epoch, 10 - epoch % 10)
+        plan.iterate(step)
+        epoch += step
+    Y = plan.demix(proj_back, dtype)
+    _info = plan.info()
+    _overiva_module._last_info = dict(_info)        # (what last_solver_info() reports)
+    W = plan.get_w(np.complex128)               # (raises LinAlgError naming the non-finite problems, overiva.py:182)
+    if return_filters:
+        return Y, W.astype(dtype, copy=False)
+    return Y
 
 
 def overiva_batch(X, n_src=None, n_iter=20, proj_back=True, W0=None, model="laplace", init_eig=False, return_filters=False,
@@ -237,59 +329,10 @@ def overiva_batch(X, n_src=None, n_iter=20, proj_back=True, W0=None, model="lapl
     Y (batch, nframes, nfrequencies, nsrc) in the dtype of X, or ``(Y, W)`` with W (batch, nfrequencies, nchannels, nsrc).
     A problem whose W ends non-finite raises ``numpy.linalg.LinAlgError`` naming every such problem.
     """
-    global _info
     X, dtype, K = _check_args(X, n_src, model, W0, n_iter)
     B, T, F, M = X.shape
     with BatchPlan(B, T, F, M, K, model) as plan:
-        plan.set_x(X)
-        plan.covariance()
-        if W0 is None and init_eig:
-            plan.set_w_eig()                      # overiva.py:106-109, the device eigensolver per bin
-        else:
-            plan.set_w(W0)
-        epoch = 0
-        while epoch < n_iter:
-            if callback is not None and epoch % 10 == 0:      # overiva.py:142-148
-                callback(plan.demix(proj_back, dtype))
-            step = n_iter - epoch if callback is None else min(n_iter - epoch, 10 - epoch % 10)
-            plan.iterate(step)
-            epoch += step
-        Y = plan.demix(proj_back, dtype)
-        _info = {"precision": "precise", "batched": B, "sharded": False, "shape": (T, F, M, K)}
-        _overiva_module._last_info = dict(_info)        # (what last_solver_info() reports)
-        W = plan.get_w(np.complex128)               # (raises LinAlgError naming the non-finite problems, overiva.py:182)
-        if return_filters:
-            return Y, W.astype(dtype, copy=False)
-        return Y
-
-
-def _check_ogive_args(X, update, model, W0, n_iter):
-    X = np.asarray(X)
-    if X.ndim != 4:
-        raise ValueError("X must have shape (batch, n_frames, n_freq, n_chan)")
-    dtype = _complex_dtype(X)
-    B, T, F, M = X.shape
-    if B < 1 or T < 1 or F < 1:
-        raise ValueError(f"X has shape {X.shape}: every dimension must be >= 1")
-    if not 1 <= M <= MAX_CHANNELS:
-        raise ValueError(f"ogive_batch runs on 1..{MAX_CHANNELS} channels, X has {M}")
-    if model not in ("laplace", "gauss"):
-        raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
-    if update not in _ive.UPDATE_IDS:
-        raise ValueError(f"update must be one of {sorted(_ive.UPDATE_IDS)}, got {update!r}")
-    if n_iter < 0:
-        raise ValueError("n_iter must be >= 0")
-    if W0 is not None:
-        W0 = np.asarray(W0)
-        try:
-            shared = np.broadcast_shapes(W0.shape, (F, M, 1)) == (F, M, 1)
-        except ValueError:
-            shared = False
-        if not shared and W0.shape != (B, F, M, 1):
-            raise ValueError(f"W0 has shape {W0.shape}: expected one broadcastable to {(F, M, 1)} or {(B, F, M, 1)}")
-    if sharded.active_group() is not None:
-        raise ValueError("ogive_batch does not run under enable_bin_sharding(): disable bin sharding for batched calls")
-    return X, dtype
+        return _run_overiva(plan, X, dtype, n_iter, proj_back, W0, init_eig, return_filters, callback)
 
 
 def ogive_batch(X, n_iter=4000, step_size=0.1, tol=1e-3, update="demix", proj_back=True, W0=None, model="laplace", init_eig=False,
@@ -342,8 +385,7 @@ def ogive_batch(X, n_iter=4000, step_size=0.1, tol=1e-3, update="demix", proj_ba
             epochs += ran
             epoch += step
         Y = plan.demix(proj_back, dtype)                                    # ive.py:249-256
-        _info = {"precision": "precise", "batched": B, "sharded": False, "shape": (T, F, M, 1), "algorithm": "ogive",
-                 "epochs": [int(e) for e in epochs], "converged": [bool(c) for c in converged]}
+        _info = dict(plan.info(), algorithm="ogive", epochs=[int(e) for e in epochs], converged=[bool(c) for c in converged])
         w = plan.get_w(np.complex128)               # (raises LinAlgError naming the non-finite problems)
         if return_filters:
             return Y, w.astype(dtype, copy=False)
@@ -353,32 +395,28 @@ def ogive_batch(X, n_iter=4000, step_size=0.1, tol=1e-3, update="demix", proj_ba
 class RaggedBatchPlan(BatchPlan):
     """Owns the device state of B problems of ``frames[b]`` x F x M with K sources (``oiva_batch_create_ragged``).
 
-    The stages are ``BatchPlan``'s.  X is packed: problem b's frames follow problem b - 1's, (sum T_b, F, M); ``set_x`` takes
-    the list of B (T_b, F, M) arrays or the packed array, ``set_x_device`` borrows a packed complex64 device array, and
-    ``demix`` returns the list of B (T_b, F, K) arrays.  W, ``set_w``'s W0 and ``status`` are (B, ...) as for a dense batch.
-    OGIVE does not run on a ragged batch: ``ogive_begin`` / ``ogive_iterate`` raise."""
+    The stages are ``BatchPlan``'s, and so is the device state: the two differ in what the caller hands over and gets back.
+    ``set_x`` takes the list of B (T_b, F, M) arrays or the packed (sum T_b, F, M) array, ``set_x_device`` borrows a packed
+    complex64 device array, and ``demix`` returns the list of B (T_b, F, K) arrays.  W, ``set_w``'s W0 and ``status`` are
+    (B, ...).  OGIVE does not run on a ragged batch: ``ogive_begin`` / ``ogive_iterate`` raise."""
+
+    dense = False
 
     def __init__(self, frames, F, M, K, model="laplace", device=None, stream=None):
-        if model not in _lib.MODEL_IDS:
-            raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
-        self.frames = [int(t) for t in frames]
-        self.lib = _lib.load()
-        self.B, self.F, self.M, self.K = len(self.frames), int(F), int(M), int(K)
-        self.T = max(self.frames) if self.frames else 0
-        self.model = model
-        self.device = get_device() if device is None else int(device)
-        self.offsets = np.concatenate([[0], np.cumsum(self.frames)]).astype(int)
-        fr = (C.c_int * self.B)(*self.frames)
-        h = C.c_void_p()
-        _lib.check(self.lib.oiva_batch_create_ragged(C.byref(h), self.device, self.B, fr, self.F, self.M, self.K,
-                                                     _lib.MODEL_IDS[model], C.c_void_p(stream) if stream else None))
-        self.h = h
-        self._keep = None
+        frames = [int(t) for t in frames]
+        self._open(frames, max(frames) if frames else 0, F, M, K, model, device, stream)
+
+    def _create(self, h, stream):
+        return self.lib.oiva_batch_create_ragged(C.byref(h), self.device, self.B, (C.c_int * self.B)(*self.frames), self.F, self.M,
+                                                 self.K, _lib.MODEL_IDS[self.model], stream)
 
     @property
     def shape(self):
         """shape of the packed X"""
         return (int(self.offsets[-1]), self.F, self.M)
+
+    def info(self):
+        return dict(BatchPlan.info(self), ragged=True, frames=list(self.frames))
 
     def set_x(self, X):
         """X: the list of B (T_b, F, M) arrays or the packed (sum T_b, F, M) array, complex64 or complex128 (complex128 is
@@ -393,58 +431,12 @@ class RaggedBatchPlan(BatchPlan):
     def ogive_begin(self, *args, **kwargs):
         raise ValueError("OGIVE does not run on a ragged batch (use ogive_batch on same-length problems)")
 
-    def ogive_iterate(self, *args, **kwargs):
-        raise ValueError("OGIVE does not run on a ragged batch (use ogive_batch on same-length problems)")
+    ogive_iterate = ogive_begin
 
     def demix(self, proj_back=True, dtype=np.complex64):
         """the list of B arrays Y_b (T_b, F, K), complex64 or complex128"""
-        out = np.empty((int(self.offsets[-1]), self.F, self.K), dtype)
-        _lib.check(self.lib.oiva_batch_demix(self.h, _lib.ptr(out), 1 if out.dtype == np.complex128 else 0, 1 if proj_back else 0))
+        out = self._demix_packed(proj_back, dtype)
         return [out[self.offsets[b]:self.offsets[b + 1]] for b in range(self.B)]
-
-
-def _check_ragged_args(Xs, n_src, model, W0, n_iter):
-    if not hasattr(Xs, "__len__"):
-        raise ValueError("Xs must be a sequence of (n_frames, n_freq, n_chan) arrays")
-    Xs = [np.asarray(x) for x in Xs]
-    if not Xs:
-        raise ValueError("Xs is empty: overiva_batch_ragged needs at least one problem")
-    for b, x in enumerate(Xs):
-        if x.ndim != 3:
-            raise ValueError(f"Xs[{b}] has shape {x.shape}: every problem must be (n_frames, n_freq, n_chan)")
-    dtypes = {x.dtype for x in Xs}
-    if len(dtypes) != 1:
-        raise ValueError(f"the problems have mixed dtypes {sorted(str(d) for d in dtypes)}: give them one complex dtype")
-    dtype = _complex_dtype(Xs[0])
-    F, M = Xs[0].shape[1:]
-    for b, x in enumerate(Xs):
-        if x.shape[1:] != (F, M):
-            raise ValueError(f"Xs[{b}] has {x.shape[1]} bins and {x.shape[2]} channels, Xs[0] {F} and {M}: F and M must agree")
-        if x.shape[0] < 1:
-            raise ValueError(f"Xs[{b}] has {x.shape[0]} frames: every problem needs at least one")
-    if F < 1:
-        raise ValueError("every problem needs at least one frequency bin")
-    if not 1 <= M <= MAX_CHANNELS:
-        raise ValueError(f"overiva_batch_ragged runs on 1..{MAX_CHANNELS} channels, the problems have {M}")
-    B = len(Xs)
-    K = M if n_src is None else n_src
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= M:
-        raise ValueError(f"n_src must be in 1..{M}")
-    if model not in ("laplace", "gauss"):
-        raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
-    if n_iter < 0:
-        raise ValueError("n_iter must be >= 0")
-    if W0 is not None:
-        W0 = np.asarray(W0)
-        try:
-            shared = np.broadcast_shapes(W0.shape, (F, M, K)) == (F, M, K)
-        except ValueError:
-            shared = False
-        if not shared and W0.shape != (B, F, M, K):
-            raise ValueError(f"W0 has shape {W0.shape}: expected one broadcastable to {(F, M, K)} or {(B, F, M, K)}")
-    if sharded.active_group() is not None:
-        raise ValueError("overiva_batch_ragged does not run under enable_bin_sharding(): disable bin sharding for batched calls")
-    return Xs, dtype, int(K)
 
 
 def overiva_batch_ragged(Xs, n_src=None, n_iter=20, proj_back=True, W0=None, model="laplace", init_eig=False, return_filters=False,
@@ -469,29 +461,7 @@ def overiva_batch_ragged(Xs, n_src=None, n_iter=20, proj_back=True, W0=None, mod
     arguments, whatever the other problems.  A problem whose W ends non-finite raises ``numpy.linalg.LinAlgError`` naming
     every such problem.
     """
-    global _info
     Xs, dtype, K = _check_ragged_args(Xs, n_src, model, W0, n_iter)
-    frames = [x.shape[0] for x in Xs]
     F, M = Xs[0].shape[1:]
-    with RaggedBatchPlan(frames, F, M, K, model) as plan:
-        plan.set_x(Xs)
-        plan.covariance()
-        if W0 is None and init_eig:
-            plan.set_w_eig()                      # overiva.py:106-109, the device eigensolver per bin
-        else:
-            plan.set_w(W0)
-        epoch = 0
-        while epoch < n_iter:
-            if callback is not None and epoch % 10 == 0:      # overiva.py:142-148
-                callback(plan.demix(proj_back, dtype))
-            step = n_iter - epoch if callback is None else min(n_iter - epoch, 10 - epoch % 10)
-            plan.iterate(step)
-            epoch += step
-        Ys = plan.demix(proj_back, dtype)
-        _info = {"precision": "precise", "batched": len(Xs), "sharded": False, "shape": (max(frames), F, M, K), "ragged": True,
-                 "frames": frames}
-        _overiva_module._last_info = dict(_info)        # (what last_solver_info() reports)
-        W = plan.get_w(np.complex128)               # (raises LinAlgError naming the non-finite problems, overiva.py:182)
-        if return_filters:
-            return Ys, W.astype(dtype, copy=False)
-        return Ys
+    with RaggedBatchPlan([x.shape[0] for x in Xs], F, M, K, model) as plan:
+        return _run_overiva(plan, Xs, dtype, n_iter, proj_back, W0, init_eig, return_filters, callback)

@@ -1,8 +1,12 @@
-// C ABI of the batched iteration (oiva_batch_*, include/overiva_hip.h): B problems of one shape, up to 8 channels, in the
-// `precise` arithmetic.  Host code only; the kernels that read X or the activations live in kernels_batch.hip, the per-bin
-// stages are the single-problem kernels run on B*F bins.  Batched OGIVE (oiva_batch_ogive_*) runs on a batch created with
-// K = 1, with its own kernels (kernels_ogive_batch.hip) and a stopping rule per problem.  A ragged batch
-// (oiva_batch_create_ragged) holds problems of different frame counts, packed, and runs the kernels of kernels_ragged.hip.
+// C ABI of the batched iteration (oiva_batch_*, include/overiva_hip.h): B problems of one F, M <= 8 and K and of T_b frames each,
+// packed along the frames, in the `precise` arithmetic.  Host code only.  Every batch is described by one table of per-problem
+// records (RaggedProblem): oiva_batch_create makes the table of B equal lengths, oiva_batch_create_ragged that of the lengths it
+// is given, and allocation, X, demix and the grid maxima follow from the table alone.  The two entries differ in the kernels
+// of the iteration: a batch of oiva_batch_create runs those of kernels_batch.hip, which take T and the splits of record 0 as
+// launch arguments (measured 1-4 % faster per stage than reading the table, CHANGELOG), a batch of oiva_batch_create_ragged
+// those of kernels_ragged.hip, which read the table on the device.  The per-bin stages are the single-problem kernels run on
+// B*F bins.  Batched OGIVE (oiva_batch_ogive_*) runs on a batch of oiva_batch_create with K = 1, with its own kernels
+// (kernels_ogive_batch.hip) and a stopping rule per problem.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -38,7 +42,8 @@ constexpr size_t kStageBytes = (size_t)256 << 20;   // staging of complex128 inp
 constexpr int kOgFramesPerSplit = 64;     // frame splits of the OGIVE frame sums: ceil(T / 64), a function of T alone
 constexpr int kOgMinGraphEpochs = 8;      // shorter OGIVE chunks run eagerly
 
-// geometry of the frame-split passes of a problem of T frames: a function of T alone (never of B or of other problems)
+// geometry of the frame-split passes of a problem of T frames: a function of T alone (never of B or of other problems), so a
+// problem gets the same bits whatever batch it is in
 struct FrameGeom {
     int nsplit, tc;          // covariance pass
     int tcp, pw_nsplit;      // power pass
@@ -87,30 +92,29 @@ struct oiva_batch {
     int B = 0, T = 0, F = 0, M = 0, K = 0, model = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    const float2* X = nullptr;     // (B, T, F, M); ragged: (sum T_b, F, M)
+    const float2* X = nullptr;     // (sum T_b, F, M) packed: (B, T, F, M) when the lengths are equal
     float2* X_owned = nullptr;
     float2* What = nullptr;        // (B*F, M, M) complex64: what the streaming kernels read
     double2* What64 = nullptr;     // (B*F, M, M) complex128: carried between iterations by the float64 update
     double* Cx = nullptr;          // [B*F][M*M] packed, / T
     double* Vpart = nullptr;       // [nsplit][B*F][K][M*M]
-    float* Ppart = nullptr;        // [B][nb][T][K]
-    float* R = nullptr;            // B activation buffers of r_stride floats
-    size_t r_stride = 0;
+    float* Ppart = nullptr;        // problem b's [nb][T_b][K] at probs[b].p_off
+    float* R = nullptr;            // problem b's activation buffer of r_buffer_bytes(T_b, K) at probs[b].r_off
     float* wscale = nullptr;       // (B, K)
-    float* Spart = nullptr;        // [stg.nsplit][F][K][3]: projection-back sums of one problem at a time
-    float2* Y = nullptr;           // (B, T, F, K), allocated on first demix; ragged: (sum T_b, F, K)
+    float* Spart = nullptr;        // [max stgs nsplit][F][K][3]: projection-back sums of one problem at a time
+    float2* Y = nullptr;           // (sum T_b, F, K), allocated on first demix
     double2* Y128 = nullptr;
-    int nsplit = 1, tc = 1;        // covariance pass
+    // T is the largest T_b, and nsplit / pw_nsplit / tcp / rblocks the largest over the problems (the grids); every problem's own
+    // geometry is in its record (host copy `probs`, device copy `probs_dev`) and stgs[p] is its projection-back statistics
+    // geometry (the single-problem plan's for F bins)
+    int nsplit = 1;                // covariance pass
     int kp = 1, pw_nsplit = 1, tcp = 4, nb = 1;   // power pass
-    CovGeom stg{};                 // projection-back statistics (the single-problem plan's geometry for F bins)
-    // ragged batch: T is the largest T_b, nsplit / pw_nsplit / tcp the largest over the problems (the grids); every problem's
-    // own geometry is in its record (host copy `probs`, device copy `probs_dev`) and stgs[p] is its statistics geometry
-    bool ragged = false;
-    size_t frames_total = 0;       // sum of T_b (B * T for a dense batch)
-    int rblocks = 1;               // largest rsum_blocks(T_b)
+    int rblocks = 1;               // activation: largest rsum_blocks(T_b)
+    size_t frames_total = 0;       // sum of T_b
     std::vector<RaggedProblem> probs;
     std::vector<CovGeom> stgs;
     RaggedProblem* probs_dev = nullptr;
+    bool ragged = false;           // made by oiva_batch_create_ragged: the kernels that read the table (dense_args otherwise)
     bool have_x = false, have_cx = false, have_w = false;
     std::vector<std::pair<int, hipGraphExec_t>> graphs;
     hipEvent_t ev[5] = {};
@@ -161,39 +165,43 @@ UpdateArgs update_args(oiva_batch* b, bool init_only) {
     a.use_double = 1;
     a.layout = 0;
     a.wscale_bins = b->F;
-    a.ragged = b->probs_dev;           // (nullptr for a dense batch)
+    a.ragged = b->ragged ? b->probs_dev : nullptr;
     return a;
+}
+
+// what the kernels of equal lengths take as launch arguments: record 0's frame count and splits, and the stride of the
+// activation buffers
+struct DenseArgs {
+    int T, tc, tcp, pw_nsplit, nsplit;
+    size_t r_stride;
+};
+DenseArgs dense_args(const oiva_batch* b) {
+    const RaggedProblem& d = b->probs[0];
+    return {d.T, d.tc, d.tcp, d.pw_nsplit, d.nsplit, r_buffer_bytes(d.T, b->K) / sizeof(float)};
 }
 
 // the four launches of one iteration (overiva.py:138-190)
 int stage(oiva_batch* b, int s) {
-    switch (s) {
-        case 0:
-            if (b->ragged) {
-                HIP_TRY(launch_ragged_power(b->stream, b->X, b->What, b->Ppart, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit,
-                                            b->tcp));
-                break;
-            }
-            HIP_TRY(launch_batch_power(b->stream, b->X, b->What, b->Ppart, b->B, b->T, b->F, b->M, b->K, b->kp, b->pw_nsplit, b->tcp));
-            break;
-        case 1:
-            if (b->ragged) {
-                HIP_TRY(launch_ragged_activation(b->stream, b->Ppart, b->nb, b->R, b->probs_dev, b->B, b->K, b->model, b->F, b->rblocks));
-                break;
-            }
-            HIP_TRY(launch_batch_activation(b->stream, b->Ppart, b->nb, b->R, b->r_stride, b->B, b->T, b->K, b->model, b->F));
-            break;
-        case 2:
-            if (b->ragged) {
-                HIP_TRY(launch_ragged_cov(b->stream, b->X, b->R, b->probs_dev, b->wscale, b->model, b->Vpart, b->B, b->F, b->M, b->K,
-                                          b->nsplit));
-                break;
-            }
-            HIP_TRY(launch_batch_cov(b->stream, b->X, b->R, b->r_stride, b->wscale, b->model, b->Vpart, b->B, b->T, b->F, b->M, b->K,
-                                     b->nsplit, b->tc));
-            break;
-        default:
-            HIP_TRY(launch_update(b->stream, update_args(b, false)));
+    if (s == 3) {
+        HIP_TRY(launch_update(b->stream, update_args(b, false)));
+    } else if (b->ragged) {
+        if (s == 0)
+            HIP_TRY(launch_ragged_power(b->stream, b->X, b->What, b->Ppart, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit,
+                                        b->tcp));
+        else if (s == 1)
+            HIP_TRY(launch_ragged_activation(b->stream, b->Ppart, b->nb, b->R, b->probs_dev, b->B, b->K, b->model, b->F, b->rblocks));
+        else
+            HIP_TRY(launch_ragged_cov(b->stream, b->X, b->R, b->probs_dev, b->wscale, b->model, b->Vpart, b->B, b->F, b->M, b->K,
+                                      b->nsplit));
+    } else {
+        const DenseArgs d = dense_args(b);
+        if (s == 0)
+            HIP_TRY(launch_batch_power(b->stream, b->X, b->What, b->Ppart, b->B, d.T, b->F, b->M, b->K, b->kp, d.pw_nsplit, d.tcp));
+        else if (s == 1)
+            HIP_TRY(launch_batch_activation(b->stream, b->Ppart, b->nb, b->R, d.r_stride, b->B, d.T, b->K, b->model, b->F));
+        else
+            HIP_TRY(launch_batch_cov(b->stream, b->X, b->R, d.r_stride, b->wscale, b->model, b->Vpart, b->B, d.T, b->F, b->M, b->K,
+                                     d.nsplit, d.tc));
     }
     return OIVA_OK;
 }
@@ -268,12 +276,12 @@ int demix_on_device(oiva_batch* b, int proj_back) {
     const int F = b->F, M = b->M, K = b->K;
     const size_t ny = b->frames_total * F * K;
     if (!b->Y) HIP_TRY(hipMalloc((void**)&b->Y, ny * sizeof(float2)));
-    // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0]);
-    // a ragged batch's problem at its packed frame offset with the statistics geometry of its own T_b
+    // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0]):
+    // every problem at its packed frame offset with the statistics geometry of its own T_b
     for (int p = 0; p < b->B; ++p) {
-        const int T = b->ragged ? b->probs[p].T : b->T;
-        const size_t t0 = b->ragged ? b->probs[p].x_off : (size_t)p * T;
-        const CovGeom& stg = b->ragged ? b->stgs[p] : b->stg;
+        const int T = b->probs[p].T;
+        const size_t t0 = b->probs[p].x_off;
+        const CovGeom& stg = b->stgs[p];
         const float2* Xb = b->X + t0 * F * M;
         const float2* Wb = b->What + (size_t)p * F * M * M;
         if (proj_back) HIP_TRY(launch_demix_stats(b->stream, Xb, Wb, b->Spart, T, F, M, K, stg));
@@ -293,8 +301,9 @@ void free_all(oiva_batch* b) {
     if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
 }
 
-// a dense batch of T frames (frames == nullptr), or a ragged one of frames[p] frames per problem (T = the largest); arguments checked
-int create_batch(oiva_batch** out, int device, int B, int T, const int* frames, int F, int M, int K, int model, void* stream) {
+// the batch of frames[p] frames per problem (T = the largest); arguments checked by the callers
+int create_batch(oiva_batch** out, int device, const std::vector<int>& frames, int F, int M, int K, int model, void* stream) {
+    const int B = (int)frames.size(), T = *std::max_element(frames.begin(), frames.end());
     DeviceGuard guard(device);
     oiva_batch* b = new oiva_batch;
     b->device = device;
@@ -316,56 +325,41 @@ int create_batch(oiva_batch** out, int device, int B, int T, const int* frames, 
         b->own_stream = true;
     }
     for (hipEvent_t& e : b->ev) TRY_CREATE(hipEventCreate(&e));
-    // geometry: functions of T, F, M, K alone (never of B)
-    const FrameGeom fg = frame_geom(T);
-    b->nsplit = fg.nsplit;
-    b->tc = fg.tc;
+    // every problem's record from its own T_b: functions of T_b, F, M, K alone (never of B); the grids (nsplit, pw_nsplit, tcp,
+    // rblocks) take the largest
     b->kp = pow_sources_per_pass(M, K);
-    b->tcp = fg.tcp;
-    b->pw_nsplit = fg.pw_nsplit;
     b->nb = ceil_div(F, kBinsPerWave * kWaves);
-    b->r_stride = r_buffer_bytes(T, K) / sizeof(float);
     b->osplit = ceil_div(T, kOgFramesPerSplit);
     b->otc = ceil_div(T, b->osplit);
     b->osplit = ceil_div(T, b->otc);
     int n_cu = 256;
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
-    b->stg = stats_geom(T, F, K, n_cu);
-    b->frames_total = (size_t)B * T;
-    size_t ppart_floats = (size_t)B * b->nb * T * K, r_floats = (size_t)B * b->r_stride;
-    int spart_splits = b->stg.nsplit;
-    if (frames) {
-        // ragged: every problem's record from its own T_b; the grids (nsplit, pw_nsplit, tcp, rblocks) take the largest
-        b->ragged = true;
-        b->r_stride = 0;
-        b->probs.resize(B);
-        b->stgs.resize(B);
-        b->nsplit = b->pw_nsplit = b->tcp = b->rblocks = 1;
-        size_t x_off = 0, p_off = 0, r_off = 0;
-        for (int p = 0; p < B; ++p) {
-            const int Tb = frames[p];
-            const FrameGeom g = frame_geom(Tb);
-            RaggedProblem& d = b->probs[p];
-            d.x_off = x_off, d.p_off = p_off, d.r_off = r_off;
-            d.inv_T = 1. / (double)Tb;
-            d.T = Tb;
-            d.tcp = g.tcp, d.pw_nsplit = g.pw_nsplit, d.nsplit = g.nsplit, d.tc = g.tc;
-            x_off += Tb;
-            p_off += (size_t)b->nb * Tb * K;
-            r_off += r_buffer_bytes(Tb, K) / sizeof(float);
-            b->stgs[p] = stats_geom(Tb, F, K, n_cu);
-            b->nsplit = std::max(b->nsplit, g.nsplit);
-            b->pw_nsplit = std::max(b->pw_nsplit, g.pw_nsplit);
-            b->tcp = std::max(b->tcp, g.tcp);
-            b->rblocks = std::max(b->rblocks, rsum_blocks(Tb));
-            spart_splits = std::max(spart_splits, b->stgs[p].nsplit);
-        }
-        b->frames_total = x_off;
-        ppart_floats = p_off;
-        r_floats = r_off;
-        TRY_CREATE(hipMalloc((void**)&b->probs_dev, (size_t)B * sizeof(RaggedProblem)));
-        TRY_CREATE(hipMemcpy(b->probs_dev, b->probs.data(), (size_t)B * sizeof(RaggedProblem), hipMemcpyHostToDevice));
+    b->probs.resize(B);
+    b->stgs.resize(B);
+    int spart_splits = 1;
+    size_t x_off = 0, p_off = 0, r_off = 0;
+    for (int p = 0; p < B; ++p) {
+        const int Tb = frames[p];
+        const FrameGeom g = frame_geom(Tb);
+        RaggedProblem& d = b->probs[p];
+        d.x_off = x_off, d.p_off = p_off, d.r_off = r_off;
+        d.inv_T = 1. / (double)Tb;
+        d.T = Tb;
+        d.tcp = g.tcp, d.pw_nsplit = g.pw_nsplit, d.nsplit = g.nsplit, d.tc = g.tc;
+        x_off += Tb;
+        p_off += (size_t)b->nb * Tb * K;
+        r_off += r_buffer_bytes(Tb, K) / sizeof(float);
+        b->stgs[p] = stats_geom(Tb, F, K, n_cu);
+        b->nsplit = std::max(b->nsplit, g.nsplit);
+        b->pw_nsplit = std::max(b->pw_nsplit, g.pw_nsplit);
+        b->tcp = std::max(b->tcp, g.tcp);
+        b->rblocks = std::max(b->rblocks, rsum_blocks(Tb));
+        spart_splits = std::max(spart_splits, b->stgs[p].nsplit);
     }
+    b->frames_total = x_off;
+    const size_t ppart_floats = p_off, r_floats = r_off;
+    TRY_CREATE(hipMalloc((void**)&b->probs_dev, (size_t)B * sizeof(RaggedProblem)));
+    TRY_CREATE(hipMemcpy(b->probs_dev, b->probs.data(), (size_t)B * sizeof(RaggedProblem), hipMemcpyHostToDevice));
     const size_t MM = (size_t)M * M;
     TRY_CREATE(hipMalloc((void**)&b->What, nbins(b) * MM * sizeof(float2)));
     TRY_CREATE(hipMalloc((void**)&b->What64, nbins(b) * MM * sizeof(double2)));
@@ -393,7 +387,7 @@ int oiva_batch_create(oiva_batch** out, int device, int B, int T, int F, int M, 
     NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "number of sources must be in 1..M");
     NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
     NEED((double)B * T * F * M < 4e9, OIVA_ERR_ARG, "batch too large");
-    return create_batch(out, device, B, T, nullptr, F, M, K, model, stream);
+    return create_batch(out, device, std::vector<int>((size_t)B, T), F, M, K, model, stream);
 }
 
 oiva_status oiva_batch_create_ragged(oiva_batch** out, int device, int B, const int* frames, int F, int M, int K, int model,
@@ -413,7 +407,9 @@ oiva_status oiva_batch_create_ragged(oiva_batch** out, int device, int B, const 
         tmax = std::max(tmax, frames[p]);
     }
     NEED(total * F * M < 4e9 && (double)B * F * M * M * K * ceil_div(tmax, kCovFramesPerSplit) < 4e9, OIVA_ERR_ARG, "batch too large");
-    return create_batch(out, device, B, tmax, frames, F, M, K, model, stream);
+    const int rc = create_batch(out, device, std::vector<int>(frames, frames + B), F, M, K, model, stream);
+    if (rc == OIVA_OK) (*out)->ragged = true;
+    return rc;
 }
 
 int oiva_batch_destroy(oiva_batch* b) {
@@ -476,15 +472,16 @@ int oiva_batch_covariance(oiva_batch* b) {
     NEED(b, OIVA_ERR_ARG, "null batch");
     NEED(b->have_x, OIVA_ERR_STATE, "X not set");
     DeviceGuard guard(b->device);
-    // unit weights, one "source": partials [nsplit][B*F][1][M*M], added in split order and divided by T (overiva.py:87)
-    if (b->ragged) {       // (problem b: its own nsplit_b partials and 1 / T_b)
+    // unit weights, one "source": partials [nsplit][B*F][1][M*M]; problem b's own nsplit_b partials added in split order and
+    // divided by T_b (overiva.py:87)
+    if (b->ragged) {
         HIP_TRY(launch_ragged_cov(b->stream, b->X, nullptr, b->probs_dev, nullptr, b->model, b->Vpart, b->B, b->F, b->M, 1, b->nsplit));
         HIP_TRY(launch_ragged_sum_parts(b->stream, b->Vpart, b->probs_dev, b->Cx, b->B, b->F, b->M));
-        b->have_cx = true;
-        return OIVA_OK;
+    } else {
+        const DenseArgs d = dense_args(b);
+        HIP_TRY(launch_batch_cov(b->stream, b->X, nullptr, 0, nullptr, b->model, b->Vpart, b->B, d.T, b->F, b->M, 1, d.nsplit, d.tc));
+        HIP_TRY(launch_sum_parts(b->stream, b->Vpart, true, d.nsplit, b->Cx, (long long)nbins(b) * b->M * b->M, 1. / (double)d.T));
     }
-    HIP_TRY(launch_batch_cov(b->stream, b->X, nullptr, 0, nullptr, b->model, b->Vpart, b->B, b->T, b->F, b->M, 1, b->nsplit, b->tc));
-    HIP_TRY(launch_sum_parts(b->stream, b->Vpart, true, b->nsplit, b->Cx, (long long)nbins(b) * b->M * b->M, 1. / (double)b->T));
     b->have_cx = true;
     return OIVA_OK;
 }
@@ -744,16 +741,17 @@ oiva_status oiva_batch_ogive_iterate(oiva_batch* b, int first_epoch, int n, doub
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipMemcpy(before.data(), b->og.epochs, B * sizeof(int), hipMemcpyDeviceToHost));
     const int amodel = b->og_model == OIVA_MODEL_LAPLACE ? kModelOgiveLaplace : OIVA_MODEL_GAUSS;
+    const DenseArgs d = dense_args(b);
     // one epoch is five launches on the batch's stream (four when the switching criterion does not run)
     auto epochs = [&](int e0, int count) -> int {
         for (int e = e0; e < e0 + count; ++e) {
             if (b->og_mode == OIVA_OGIVE_SWITCHING && e % 10 == 0)
                 HIP_TRY(launch_batch_ogive_switch(b->stream, b->og, B, b->F, b->M));                     // ive.py:192-193
-            HIP_TRY(launch_batch_ogive_power(b->stream, b->X, b->What, b->Ppart, b->og.done, B, b->T, b->F, b->M, b->pw_nsplit,
-                                             b->tcp));                                                    // ive.py:196, :210/:213
-            HIP_TRY(launch_batch_ogive_activation(b->stream, b->Ppart, b->nb, b->R, b->r_stride, b->og.done, B, b->T, amodel,
+            HIP_TRY(launch_batch_ogive_power(b->stream, b->X, b->What, b->Ppart, b->og.done, B, d.T, b->F, b->M, d.pw_nsplit,
+                                             d.tcp));                                                     // ive.py:196, :210/:213
+            HIP_TRY(launch_batch_ogive_activation(b->stream, b->Ppart, b->nb, b->R, d.r_stride, b->og.done, B, d.T, amodel,
                                                   b->F));                                                 // ive.py:209-217
-            HIP_TRY(launch_batch_ogive_framesum(b->stream, b->X, b->What64, b->R, b->r_stride, b->og.done, b->Opart, B, b->T, b->F,
+            HIP_TRY(launch_batch_ogive_framesum(b->stream, b->X, b->What64, b->R, d.r_stride, b->og.done, b->Opart, B, d.T, b->F,
                                                 b->M, b->osplit, b->otc));                                // ive.py:218-227
             HIP_TRY(launch_batch_ogive_step(b->stream, b->og, b->Opart, b->osplit, B, b->F, b->M, step_size, tol));   // ive.py:228-246
         }

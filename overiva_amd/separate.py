@@ -258,7 +258,7 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
         with plan:
             plan.set_x_device(Xd.ptr, keepalive=Xd)
             plan.covariance()
-            info = {"precision": "precise", "batched": B, "sharded": False, "shape": (max(st.frames), F, M, K), "audio": True}
+            info = dict(plan.info(), audio=True)
             if algorithm == "ogive":
                 _run_ogive(plan, n_iter, W0, init_eig, model, info, **algo_kwargs)
             else:
@@ -267,8 +267,6 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
                 else:
                     plan.set_w(W0)
                 plan.iterate(n_iter)
-                if ragged:
-                    info.update(ragged=True, frames=list(st.frames))
             y = st.synthesis_device(plan.demix_device(proj_back))
             _batch._info = info
             if algorithm == "overiva":
