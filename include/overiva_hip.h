@@ -240,6 +240,13 @@ int oiva_plan_set_cov_hmfma(oiva_plan *p, int enable);
  * bits as the two launches; measured no faster, so off by default: $OIVA_COV_UPDATE=1 or enable = 1).  enable 1 / 0; -1 only
  * asks.  *active: whether this plan's iterations run it. */
 int oiva_plan_set_fuse_cov_update(oiva_plan *p, int enable, int *active);
+/* Frame order of the demix+power pass at up to 8 channels (and up to 4 sources beyond): 1 (default; $OIVA_POWER_REVERSE=0 at
+ * plan creation: 0) = against the covariance pass -- the frame chunks are handed out from the tail of every covariance split to
+ * its head and each is walked descending, so that each of the two passes over X starts on what the other left in the last-level
+ * cache; 0 = ascending.  Which chunk a row of the grid takes only matters when the grid runs in several rounds of workgroups
+ * (a long frame axis), so only then are the chunks re-ordered; 2 (a test hook, $OIVA_POWER_REVERSE=2) re-orders them in a grid
+ * of one round too.  Same bits in every setting (frames are independent in this pass).  Drops captured graphs. */
+int oiva_plan_set_power_reverse(oiva_plan *p, int enable);
 /* Replay the iteration from a captured hipGraph instead of eager launches (default off). */
 int oiva_plan_use_graph(oiva_plan *p, int enable);
 /* Arithmetic: an OR of OIVA_PREC_* (default OIVA_PREC_FAST).  Call it before oiva_plan_covariance so that the
@@ -335,6 +342,12 @@ int oiva_test_run_update(oiva_plan *p);                       /* overiva.py:181-
 int oiva_test_get_what(oiva_plan *p, void *What_host /* (F,M,M) complex64 | complex128 */, int f64);
 int oiva_test_set_what(oiva_plan *p, const void *What_host, int f64);
 int oiva_test_run_power(oiva_plan *p, float *p_host /* (T,K) summed over this plan's bins */);
+/* the partial powers of the last power pass as they lie on the device: *nparts 64-bin parts of (T, K) floats (parts_host NULL:
+ * only the count) */
+int oiva_test_get_ppart(oiva_plan *p, float *parts_host, int *nparts);
+/* host only: order[y] = the frame chunk that row y of the power pass's grid takes (nsplit chunks of tcp frames) against a
+ * covariance pass of cov_splits splits of cov_tc frames */
+int oiva_test_power_order(int nsplit, int tcp, int cov_splits, int cov_tc, int *order);
 /* average duration of `reps` back-to-back launches of one stage (0 power, 1 activation, 2 covariance,
  * 3 update) on the plan's current state, HIP events on the plan's stream */
 int oiva_test_time_stage(oiva_plan *p, int stage, int reps, float *avg_ms);

@@ -79,6 +79,7 @@ SIGNATURES = {
     "oiva_plan_set_pow_splits": [_vp, _i],
     "oiva_plan_set_cov_hmfma": [_vp, _i],
     "oiva_plan_set_fuse_cov_update": [_vp, _i, C.POINTER(_i)],
+    "oiva_plan_set_power_reverse": [_vp, _i],
     "oiva_plan_use_graph": [_vp, _i],
     "oiva_plan_set_precision": [_vp, _i],
     "oiva_plan_set_resident": [_vp, _i],
@@ -101,6 +102,8 @@ SIGNATURES = {
     "oiva_test_get_what": [_vp, _vp, _i],
     "oiva_test_set_what": [_vp, _vp, _i],
     "oiva_test_run_power": [_vp, _vp],
+    "oiva_test_get_ppart": [_vp, _vp, C.POINTER(_i)],
+    "oiva_test_power_order": [_i, _i, _i, _i, C.POINTER(_i)],
     "oiva_test_time_stage": [_vp, _i, _i, _fp],
     "oiva_plan_ogive_begin": [_vp, _i, _i],
     "oiva_plan_ogive_iterate": [_vp, _i, _i, C.c_double, C.c_double, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double)],

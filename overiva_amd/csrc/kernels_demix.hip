@@ -12,12 +12,16 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------
 // power: block = 4 waves x 16 bins = 64 bins, 4 frame phases per wave, frames [t_begin, t_begin+tcp)
+// rev: the pass runs AGAINST the covariance pass (ord.cs splits, each walked ascending): the rows of the grid take their chunks
+// tail first (power_chunk_tail_first) and every chunk is walked from its last step to its first, so that the launch starts on
+// the X the covariance pass read last and ends on the X it reads first.  Frames are independent of each other (the sums run
+// over bins), so every word of Ppart keeps its place and its bits.  rev == 0: chunk = row, ascending.
 // ---------------------------------------------------------------------------------------------
 constexpr int kPowUnroll = 2;
 
 template <int M, int KP>
 __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict__ X, const float2* __restrict__ What,
-                                                       float* __restrict__ Ppart, int T, int F, int K, int tcp) {
+                                                       float* __restrict__ Ppart, int T, int F, int K, int tcp, int rev, PowOrder ord) {
     extern __shared__ __attribute__((aligned(16))) float sp[];  // [kWaves][tcp][KP]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -28,10 +32,12 @@ __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict_
     const bool fvalid = f < F;
     const int fc = fvalid ? f : F - 1;
     const int k0 = blockIdx.z * KP;
-    const int t_begin = blockIdx.y * tcp;
+    const int chunk = ord.cs > 0 ? power_chunk_tail_first(blockIdx.y, gridDim.y, ord) : (int)blockIdx.y;
+    const int t_begin = chunk * tcp;
     const int t_end = min(T, t_begin + tcp);
     const int len = t_end - t_begin;
     const int nsteps = (len + 3) >> 2;
+    const int ngroups = (nsteps + kPowUnroll - 1) / kPowUnroll;
 
     float wr[KP][M], wi[KP][M];
     load_wconj<M, KP>(What, fc, k0, K, wr, wi);
@@ -41,7 +47,8 @@ __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict_
     // because a lane's M*8 bytes arrive through M/2 separate dwordx4 requests to the same lines).
     const size_t frame_stride = (size_t)F * M;
     const float2* pbase = X + (size_t)fc * M;
-    for (int i = 0; i < nsteps; i += kPowUnroll) {
+    for (int g = 0; g < ngroups; ++g) {
+        const int i = (rev ? ngroups - 1 - g : g) * kPowUnroll;
         float xr[kPowUnroll][M], xi[kPowUnroll][M];
 #pragma unroll
         for (int u = 0; u < kPowUnroll; ++u) {
@@ -201,7 +208,7 @@ hipError_t launch_power_one(hipStream_t s, const float2* X, const float2* What, 
                             const PowGeom& g) {
     dim3 grid(g.nb, g.nsplit, (K + KP - 1) / KP);
     const size_t shmem = (size_t)kWaves * g.tcp * KP * sizeof(float);
-    hipLaunchKernelGGL((power_kernel<M, KP>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, g.tcp);
+    hipLaunchKernelGGL((power_kernel<M, KP>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, g.tcp, g.rev, g.ord);
     return hipGetLastError();
 }
 

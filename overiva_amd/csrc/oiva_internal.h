@@ -79,13 +79,54 @@ struct CovGeom {
     int quad = 0; // 10/12/14/16 channels, few sources, float32: the vector-ALU kernel of kernels_cov_quad.hip (float64 partials)
     int part32 = 0; // hmfma, float32 arithmetic: the partial blocks leave as float32 (each the float64 sum of its chains, rounded once)
 };
+// Which frame chunk the y-th dispatched row of power_kernel's grid takes when the pass runs against the covariance pass
+// (DESIGN §3).  The covariance pass walks `cs` splits of `ctc` frames ascending and side by side, so the X it read last -- what
+// the Infinity Cache still holds -- is the TAIL of every split.  The n chunks of tcp frames are therefore handed out tail
+// first: chunk c belongs to the split that holds its last frame (split s owns chunks [first[s], first[s + 1]), first[s] = the
+// chunk that holds frame s * ctc), row 0 of the order is the last chunk of every split, row 1 the one before it, and so on
+// down to the heads, which the next covariance pass reads first.  A bijection of [0, n) for any n, tcp, cs, ctc >= 1 (a split
+// may own no chunk at all).  The table is made on the host and travels by value in the kernel's arguments (the divisions of the
+// closed form cost every workgroup 1-2 us in front of its first load: measured); uniform scalar work in the kernel.
+constexpr int kPowOrderMaxSplits = 64;
+struct PowOrder {
+    int cs = 0;                              // covariance splits (0: no order, chunk = row)
+    int q = 0;                               // chunks EVERY split owns: the rows of the order that hold all cs splits
+    int first[kPowOrderMaxSplits + 1] = {};  // first chunk of split s; first[cs] = n
+};
+inline PowOrder make_pow_order(int n, int tcp, int cs, int ctc) {
+    PowOrder o;
+    if (cs < 1 || cs > kPowOrderMaxSplits || ctc < 1 || tcp < 1 || n < 1) return o;      // (more splits than the table holds: chunk = row)
+    o.cs = cs;
+    for (int s = 0; s < cs; ++s) {
+        const long long c = (long long)s * ctc / tcp;
+        o.first[s] = c < n ? (int)c : n;
+    }
+    o.first[cs] = n;
+    o.q = n;
+    for (int s = 0; s < cs; ++s) o.q = o.first[s + 1] - o.first[s] < o.q ? o.first[s + 1] - o.first[s] : o.q;
+    return o;
+}
+__host__ __device__ inline int power_chunk_tail_first(int y, int n, const PowOrder& o) {
+    if (y < o.q * o.cs) return o.first[y % o.cs + 1] - 1 - y / o.cs;
+    y -= o.q * o.cs;
+    for (int r = o.q; r < n; ++r)
+        for (int s = 0; s < o.cs; ++s)
+            if (o.first[s + 1] - o.first[s] > r && y-- == 0) return o.first[s + 1] - 1 - r;
+    return n - 1;      // (not reached: the rows hold n chunks in all)
+}
 struct PowGeom {
     int nb;       // bin batches of 64 (grid.x)
     int nsplit;   // frame splits (grid.y)
     int tcp;      // frames per split (multiple of 4, <= kPowMaxFrames)
     int kp;       // sources per pass
+    // the frame order of power_kernel: rev = every chunk from its last step to its first, ord = which chunk a row of the grid
+    // takes (both: against the covariance pass, kernels_demix.hip).  Filled in at launch time (stage_power).
+    int rev = 0;
+    PowOrder ord{};
+    int rounds = 1;   // rounds of resident workgroups the grid of power_kernel takes (choose_pow_geom)
 };
 constexpr int kPowMaxFrames = 512;
+
 
 // ---- launchers (one per kernel family; each .hip file owns its template instantiations) -------
 // Weighted covariance pass, overiva.py:179 (and :87 with unit weights).

@@ -170,6 +170,7 @@ struct oiva_plan {
     bool cov_quad_on = true;      // oiva_plan_set_cov_quad
     bool cov_hmfma_on = true;     // oiva_plan_set_cov_hmfma ($OIVA_COV_HMFMA=0: off)
     bool fuse_cov_update = false; // oiva_plan_set_fuse_cov_update ($OIVA_COV_UPDATE=1: on wherever the shape qualifies)
+    int power_reverse = 1;        // oiva_plan_set_power_reverse ($OIVA_POWER_REVERSE=0: off): the power pass walks X against the covariance pass; 2: and takes its chunks tail first even in a grid of one round
     CovGeom stg{};              // geometry of the projection-back statistics pass (16-bin groups, independent of cov)
     PowGeom pw{};
     int n_cu = 256;
@@ -464,6 +465,11 @@ void choose_pow_geom(oiva_plan* p, int nsplit_req) {
     tcp = std::min(std::max(tcp, 4), kPowMaxFrames);
     g.tcp = tcp;
     g.nsplit = ceil_div(p->T, tcp);
+    // rounds of workgroups the grid runs in (a long frame axis: tcp is capped, so the chunks outnumber the chip's slots)
+    int bpc = 0;
+    if (p->M <= 8 || p->K <= 4)
+        if (pow_blocks_per_cu(p->M, g.kp, g.tcp, &bpc) == hipSuccess && bpc > 0)
+            g.rounds = (int)ceil_div((long long)g.nb * g.nsplit * ceil_div(p->K, g.kp), (long long)bpc * p->n_cu);
     p->pw = g;
 }
 
@@ -494,7 +500,16 @@ int ensure_vpart(oiva_plan* p) {
 
 // ---- the five stages of one iteration -----------------------------------------------------------
 int stage_power(oiva_plan* p) {
-    HIP_TRY(launch_power(p->stream, p->X, p->X_pad && p->pad_valid ? p->X_pad : nullptr, p->What, p->Ppart, p->T, p->F, p->M, p->K, p->pw));
+    // the order follows the covariance geometry of THIS launch (oiva_plan_set_cov_splits and the precision change it after the
+    // power geometry was chosen)
+    PowGeom g = p->pw;
+    if (p->power_reverse) {
+        g.rev = 1;
+        // which chunk a row takes only matters when the rows do not all run at once; in one round the order table measured
+        // as a loss on the 1024-bin shard
+        if (g.rounds > 1 || p->power_reverse > 1) g.ord = make_pow_order(g.nsplit, g.tcp, p->cov.nsplit, p->cov.tc);
+    }
+    HIP_TRY(launch_power(p->stream, p->X, p->X_pad && p->pad_valid ? p->X_pad : nullptr, p->What, p->Ppart, p->T, p->F, p->M, p->K, g));
     return OIVA_OK;
 }
 int stage_activation(oiva_plan* p, const float* parts, int nparts) {
@@ -874,6 +889,8 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
         p->cov_hmfma_on = !(v && v[0] == '0');
         const char* u = std::getenv("OIVA_COV_UPDATE");
         p->fuse_cov_update = u && u[0] == '1';
+        const char* r = std::getenv("OIVA_POWER_REVERSE");      // read here, once: the plan keeps what it was created with
+        p->power_reverse = (r && r[0] == '0') ? 0 : (r && r[0] == '2') ? 2 : 1;
     }
     choose_cov_geom(p, 0);
     choose_pow_geom(p, 0);
@@ -1691,6 +1708,16 @@ int oiva_plan_set_pow_splits(oiva_plan* p, int nsplit) {
     return OIVA_OK;
 }
 
+int oiva_plan_set_power_reverse(oiva_plan* p, int enable) {
+    NEED(p, OIVA_ERR_ARG, "null plan");
+    DeviceGuard guard(p->device);
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    int rc = drop_graph(p);
+    if (rc) return rc;
+    p->power_reverse = enable < 0 ? 0 : enable > 2 ? 2 : enable;
+    return OIVA_OK;
+}
+
 int oiva_plan_use_graph(oiva_plan* p, int enable) {
     NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
@@ -2127,6 +2154,24 @@ int oiva_test_run_power(oiva_plan* p, float* p_host) {
     std::vector<double> sum(n);
     HIP_TRY(hipMemcpy(sum.data(), p->scratch_p, n * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) p_host[i] = (float)sum[i];
+    return OIVA_OK;
+}
+
+int oiva_test_get_ppart(oiva_plan* p, float* parts_host, int* nparts) {
+    NEED(p && nparts, OIVA_ERR_ARG, "null argument");
+    *nparts = p->pw.nb;
+    if (!parts_host) return OIVA_OK;
+    DeviceGuard guard(p->device);
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    HIP_TRY(hipMemcpy(parts_host, p->Ppart, (size_t)p->pw.nb * p->T * p->K * sizeof(float), hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+int oiva_test_power_order(int nsplit, int tcp, int cov_splits, int cov_tc, int* order) {
+    NEED(order && nsplit >= 1 && tcp >= 1 && cov_splits >= 1 && cov_tc >= 1, OIVA_ERR_ARG, "bad arguments");
+    NEED(cov_splits <= kPowOrderMaxSplits, OIVA_ERR_ARG, "more covariance splits than the order table holds");
+    const PowOrder o = make_pow_order(nsplit, tcp, cov_splits, cov_tc);
+    for (int y = 0; y < nsplit; ++y) order[y] = power_chunk_tail_first(y, nsplit, o);
     return OIVA_OK;
 }
 

@@ -242,6 +242,11 @@ class Plan:
     def set_pow_splits(self, n):
         _lib.check(self.lib.oiva_plan_set_pow_splits(self.h, int(n)))
 
+    def set_power_reverse(self, enable=True):
+        """power pass: frames against the covariance pass's order (default; ``$OIVA_POWER_REVERSE=0`` at plan creation: off) or
+        ascending; ``2``: the chunks tail first even in a grid of one round (test hook); same bits, drops captured graphs"""
+        _lib.check(self.lib.oiva_plan_set_power_reverse(self.h, int(enable)))
+
     def use_graph(self, enable=True):
         _lib.check(self.lib.oiva_plan_use_graph(self.h, 1 if enable else 0))
 
@@ -357,6 +362,14 @@ class Plan:
         ms = C.c_float()
         _lib.check(self.lib.oiva_test_time_stage(self.h, _lib.STAGE_NAMES.index(stage), int(reps), C.byref(ms)))
         return ms.value
+
+    def t_get_ppart(self):
+        """the partial powers of the last power pass as they lie on the device: (64-bin parts, T, K) float32"""
+        n = C.c_int()
+        _lib.check(self.lib.oiva_test_get_ppart(self.h, None, C.byref(n)))
+        out = np.empty((n.value, self.T, self.K), np.float32)
+        _lib.check(self.lib.oiva_test_get_ppart(self.h, _lib.ptr(out), C.byref(n)))
+        return out
 
     def t_run_power(self):
         p = np.empty((self.T, self.K), np.float32)
