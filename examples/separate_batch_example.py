@@ -31,3 +31,6 @@ if __name__ == "__main__":
     for x, y in zip(rooms, ys):
         print(f"room of {x.shape[0]} samples x {x.shape[1]} mics -> {y.shape[0]} samples x {y.shape[1]} sources")
     print("filters", W.shape, "info", last_batch_info())
+    # the same rooms through PCA to two channels + determined AuxIVA (the sweep's auxiva_pca column)
+    ys = separate_batch(rooms, FRAME, HOP, n_src=SOURCES, n_iter=30, algorithm="auxiva_pca")
+    print("auxiva_pca:", [y.shape for y in ys], "info", last_batch_info())

@@ -440,6 +440,28 @@ oiva_status oiva_batch_create_ragged(oiva_batch **out, int device, int B, const 
                                      void *stream);
 
 /*
+ * Batched PCA + determined AuxIVA (auxiva_pca.py:63-92 on B problems; overiva_amd/pca_batch.py, auxiva_pca_batch): the outer
+ * batch (M channels, K < M sources) finds every bin's principal subspace and projects X onto it on the device, an inner batch
+ * of the same B, F and frames with M = K runs the determined iteration on the projected X, and the composed filters demix the
+ * original X.  Dense and ragged batches alike: the projection is driven from the problem table.
+ *   oiva_batch_set_w_pca   : after oiva_batch_covariance: W = [the eigenvectors of the K largest eigenvalues of Cx, ascending |
+ *                            [0; -I]] per bin (auxiva_pca.py:75-81, w[:, :, -K:]), as oiva_plan_set_w_pca for one problem;
+ *                            evals_host (B, F, M) ascending, or NULL
+ *   oiva_batch_project_dev : Xr[t,f,k] = sum_m conj(W[b,f,m,k]) X[t,f,m] for all problems in one launch (auxiva_pca.py:79-81),
+ *                            (B, T, F, K) or packed (sum T_b, F, K) complex64 in a device array of the batch that is NOT the one
+ *                            oiva_batch_demix_dev returns; every element is the float32 chain of oiva_batch_demix without
+ *                            projection back.  Synchronous; *Xr_dev is valid until the next projection on the batch or its
+ *                            destruction: hand it to the inner batch's oiva_batch_set_x_dev
+ *   oiva_batch_compose_w   : columns 0..K-1 of the outer W <- P W_red in float64 per (problem, bin), P = those columns and W_red
+ *                            the inner batch's K x K W; OIVA_ERR_ARG unless B and F agree and inner M == inner K == outer K.
+ *                            Waits for the inner batch's stream.  A non-finite W_red propagates: oiva_batch_get_w / _status of the
+ *                            outer batch name the problem.  oiva_batch_demix(outer, proj_back = 1) then gives auxiva_pca.py:89-90
+ */
+oiva_status oiva_batch_set_w_pca(oiva_batch *b, double *evals_host);
+oiva_status oiva_batch_project_dev(oiva_batch *b, void **Xr_dev);
+oiva_status oiva_batch_compose_w(oiva_batch *outer, const oiva_batch *inner);
+
+/*
  * STFT analysis / synthesis on the GPU (hipFFT): time-domain audio in and out next to the solver.
  * Replaces, in the reference's drivers, pra.transform.analysis(mics_signals.T, framesize, framesize // 2, win=win_a)
  * (overiva_oneshot.py:293-295, overiva_sim.py:206-207) and pra.transform.synthesis(Y, framesize, framesize // 2,

@@ -29,7 +29,8 @@ _info = {}
 
 
 def last_batch_info():
-    """what the last ``overiva_batch()`` or ``ogive_batch()`` call ran: ``{"precision": "precise", "batched": B, ...}``; after
+    """what the last batched call ran: ``{"precision": "precise", "batched": B, ...}``; after ``auxiva_pca_batch()`` also
+    ``algorithm`` ("auxiva_pca") and ``reduced`` (the channel count of the inner solve); after
     ``ogive_batch()`` also ``epochs`` (B ints: epochs each problem ran) and ``converged`` (B bools: its stopping rule fired); after
     ``overiva_batch_ragged()`` also ``ragged`` (True) and ``frames`` (B ints), ``shape`` then holding the largest T"""
     return dict(_info)
@@ -63,7 +64,8 @@ class BatchPlan:
     """Owns the device state of B problems of shape (T, F, M) with K sources (``oiva_batch``).
 
     Stages as ``Plan``'s: ``set_x``, ``covariance``, ``set_w`` / ``set_w_eig``, ``iterate``, ``demix``, ``get_w``; ``status``
-    reports which problems hold a non-finite W.  With K = 1, ``ogive_begin`` / ``ogive_iterate`` run OGIVE instead of
+    reports which problems hold a non-finite W.  ``set_w_pca`` / ``project_device`` / ``compose_w`` are the PCA front end of
+    ``auxiva_pca_batch()`` (pca_batch.py).  With K = 1, ``ogive_begin`` / ``ogive_iterate`` run OGIVE instead of
     ``iterate`` (``get_cx`` reads the input covariance for the host's ``init_eig``).
 
     On the device X and Y are packed along the frames, (sum T_b, F, .): ``frames`` holds the B frame counts (here B times T)
@@ -155,6 +157,31 @@ class BatchPlan:
     def set_w_eig(self):
         _lib.check(self.lib.oiva_batch_set_w_eig(self.h))
 
+    def set_w_pca(self, return_eigenvalues=False):
+        """W = the K principal eigenvectors of every bin's input covariance, ascending (the reference's ``w[:, :, -K:]``,
+        auxiva_pca.py:75-81), from the Jacobi eigensolver on the device; optionally returns all eigenvalues (B, F, M), ascending"""
+        ev = np.empty((self.B, self.F, self.M), np.float64) if return_eigenvalues else None
+        _lib.check(self.lib.oiva_batch_set_w_pca(self.h, _lib.ptr(ev) if ev is not None else None))
+        return ev
+
+    def project_device(self):
+        """x -> W^H x for every problem in one launch (auxiva_pca.py:79-81 after ``set_w_pca``): a ``DeviceBatch`` of K channels in
+        a device array of this plan that ``demix`` does not write, valid until the next ``project_device`` on the plan"""
+        dev = C.c_void_p()
+        _lib.check(self.lib.oiva_batch_project_dev(self.h, C.byref(dev)))
+        return DeviceBatch(dev.value, self.frames, self.F, self.K, self.dense, owner=self)
+
+    def compose_w(self, inner):
+        """W[:, :K] <- W[:, :K] @ W_red on the device in float64, W_red the (K, K) matrices of ``inner``, the determined plan that
+        ran on ``project_device()``'s output: y = W_red^H (P^H x) = (P W_red)^H x"""
+        if not isinstance(inner, BatchPlan) or inner is self:
+            raise ValueError("compose_w takes the plan of the reduced problems")
+        if (inner.B, inner.F) != (self.B, self.F):
+            raise ValueError(f"the reduced plan holds {inner.B} problems of {inner.F} bins, this one {self.B} of {self.F}")
+        if not inner.M == inner.K == self.K:
+            raise ValueError(f"the reduced plan must be determined on {self.K} channels, it has {inner.M} channels and {inner.K} sources")
+        _lib.check(self.lib.oiva_batch_compose_w(self.h, inner.h))
+
     def iterate(self, n=1):
         _lib.check(self.lib.oiva_batch_iterate(self.h, int(n)))
 
@@ -207,10 +234,10 @@ class BatchPlan:
         return total.value, dict(zip(_lib.STAGE_NAMES, list(arr)))
 
 
-def _check_common(name, found, B, F, M, n_src, model, W0, n_iter, update=None, bool_counts=True):
-    """what the three entry points check once the shapes are known (``name`` of the entry point, ``found``: how its message
-    names the channel count it met; ``bool_counts``: ``n_src=True`` is one source, as ``overiva_batch`` has always taken it);
-    returns K"""
+def _check_common(name, found, B, F, M, n_src, model, W0, n_iter, update=None, bool_counts=True, w0_reduced=False):
+    """what the batched entry points check once the shapes are known (``name`` of the entry point, ``found``: how its message
+    names the channel count it met; ``bool_counts``: ``n_src=True`` is one source, as ``overiva_batch`` has always taken it;
+    ``w0_reduced``: W0 starts the determined solve on K channels of ``auxiva_pca_batch``, (F, K, K)); returns K"""
     if not 1 <= M <= MAX_CHANNELS:
         raise ValueError(f"{name} runs on 1..{MAX_CHANNELS} channels, {found} {M}")
     K = M if n_src is None else n_src
@@ -222,17 +249,23 @@ def _check_common(name, found, B, F, M, n_src, model, W0, n_iter, update=None, b
         raise ValueError(f"update must be one of {sorted(_ive.UPDATE_IDS)}, got {update!r}")
     if n_iter < 0:
         raise ValueError("n_iter must be >= 0")
-    if W0 is not None:
-        W0 = np.asarray(W0)
-        try:
-            shared = np.broadcast_shapes(W0.shape, (F, M, K)) == (F, M, K)
-        except ValueError:
-            shared = False
-        if not shared and W0.shape != (B, F, M, K):
-            raise ValueError(f"W0 has shape {W0.shape}: expected one broadcastable to {(F, M, K)} or {(B, F, M, K)}")
+    _check_w0(W0, B, F, K if w0_reduced else M, K)
     if sharded.active_group() is not None:
         raise ValueError(f"{name} does not run under enable_bin_sharding(): disable bin sharding for batched calls")
     return int(K)
+
+
+def _check_w0(W0, B, F, M, K):
+    """W0: None, broadcastable to (F, M, K), or (B, F, M, K)"""
+    if W0 is None:
+        return
+    W0 = np.asarray(W0)
+    try:
+        shared = np.broadcast_shapes(W0.shape, (F, M, K)) == (F, M, K)
+    except ValueError:
+        shared = False
+    if not shared and W0.shape != (B, F, M, K):
+        raise ValueError(f"W0 has shape {W0.shape}: expected one broadcastable to {(F, M, K)} or {(B, F, M, K)}")
 
 
 def _check_dense_x(X):
@@ -259,12 +292,13 @@ def _check_ogive_args(X, update, model, W0, n_iter):
     return X, dtype
 
 
-def _check_ragged_args(Xs, n_src, model, W0, n_iter):
+def _check_ragged_xs(Xs, name="overiva_batch_ragged"):
+    """the list of problems as arrays, their common complex dtype"""
     if not hasattr(Xs, "__len__"):
         raise ValueError("Xs must be a sequence of (n_frames, n_freq, n_chan) arrays")
     Xs = [np.asarray(x) for x in Xs]
     if not Xs:
-        raise ValueError("Xs is empty: overiva_batch_ragged needs at least one problem")
+        raise ValueError(f"Xs is empty: {name} needs at least one problem")
     for b, x in enumerate(Xs):
         if x.ndim != 3:
             raise ValueError(f"Xs[{b}] has shape {x.shape}: every problem must be (n_frames, n_freq, n_chan)")
@@ -280,6 +314,12 @@ def _check_ragged_args(Xs, n_src, model, W0, n_iter):
             raise ValueError(f"Xs[{b}] has {x.shape[0]} frames: every problem needs at least one")
     if F < 1:
         raise ValueError("every problem needs at least one frequency bin")
+    return Xs, dtype
+
+
+def _check_ragged_args(Xs, n_src, model, W0, n_iter):
+    Xs, dtype = _check_ragged_xs(Xs)
+    F, M = Xs[0].shape[1:]
     return Xs, dtype, _check_common("overiva_batch_ragged", "the problems have", len(Xs), F, M, n_src, model, W0, n_iter,
                                     bool_counts=False)
 

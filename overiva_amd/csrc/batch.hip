@@ -6,7 +6,8 @@
 // launch arguments (measured 1-4 % faster per stage than reading the table, CHANGELOG), a batch of oiva_batch_create_ragged
 // those of kernels_ragged.hip, which read the table on the device.  The per-bin stages are the single-problem kernels run on
 // B*F bins.  Batched OGIVE (oiva_batch_ogive_*) runs on a batch of oiva_batch_create with K = 1, with its own kernels
-// (kernels_ogive_batch.hip) and a stopping rule per problem.
+// (kernels_ogive_batch.hip) and a stopping rule per problem.  The PCA front end of auxiva_pca_batch (oiva_batch_set_w_pca,
+// _project_dev, _compose_w; kernels_pca_batch.hip) reads the table on the device for every batch.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -104,6 +105,7 @@ struct oiva_batch {
     float* Spart = nullptr;        // [max stgs nsplit][F][K][3]: projection-back sums of one problem at a time
     float2* Y = nullptr;           // (sum T_b, F, K), allocated on first demix
     double2* Y128 = nullptr;
+    float2* Xr = nullptr;          // (sum T_b, F, K): X projected onto the principal subspace (oiva_batch_project_dev), allocated on first use
     // T is the largest T_b, and nsplit / pw_nsplit / tcp / rblocks the largest over the problems (the grids); every problem's own
     // geometry is in its record (host copy `probs`, device copy `probs_dev`) and stgs[p] is its projection-back statistics
     // geometry (the single-problem plan's for F bins)
@@ -293,7 +295,7 @@ int demix_on_device(oiva_batch* b, int proj_back) {
 void free_all(oiva_batch* b) {
     (void)drop_graphs(b);
     for (void* q : {(void*)b->X_owned, (void*)b->What, (void*)b->What64, (void*)b->Cx, (void*)b->Vpart, (void*)b->Ppart, (void*)b->R,
-                    (void*)b->wscale, (void*)b->Spart, (void*)b->Y, (void*)b->Y128, (void*)b->probs_dev})
+                    (void*)b->wscale, (void*)b->Spart, (void*)b->Y, (void*)b->Y128, (void*)b->Xr, (void*)b->probs_dev})
         if (q) (void)hipFree(q);
     for (void* q : b->og_bufs) (void)hipFree(q);
     for (hipEvent_t& e : b->ev)
@@ -790,6 +792,52 @@ oiva_status oiva_batch_ogive_iterate(oiva_batch* b, int first_epoch, int n, doub
         for (int p = 0; p < B; ++p) epochs_run[p] = after[p] - before[p];
     if (converged) HIP_TRY(hipMemcpy(converged, b->og.done, B * sizeof(int), hipMemcpyDeviceToHost));
     if (max_delta) HIP_TRY(hipMemcpy(max_delta, b->og.maxdelta, B * sizeof(double), hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+// ---- batched PCA front end (reference auxiva_pca.py:63-92, one problem per batch entry) -------------------------------------
+oiva_status oiva_batch_set_w_pca(oiva_batch* b, double* evals_host) {
+    NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
+    DeviceGuard guard(b->device);
+    // auxiva_pca.py:75-81 per bin, the device eigensolver on B*F bins; the eigenvalues pass through Vpart (free between the
+    // covariance and the first iteration, at least B*F*M*M doubles)
+    double* evals = evals_host ? b->Vpart : nullptr;
+    HIP_TRY(launch_pca_subspace(b->stream, b->Cx, b->What, b->What64, evals, (int)nbins(b), b->M, b->K, false));
+    b->have_w = true;
+    if (evals_host) {
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        HIP_TRY(hipMemcpy(evals_host, evals, nbins(b) * b->M * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (b->K < b->M) HIP_TRY(launch_update(b->stream, update_args(b, true)));   // J from the orthogonality constraint
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_project_dev(oiva_batch* b, void** Xr_dev) {
+    NEED(Xr_dev != nullptr, OIVA_ERR_ARG, "null argument");
+    *Xr_dev = nullptr;
+    const int rc = check_ready(b);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    if (!b->Xr) HIP_TRY(hipMalloc((void**)&b->Xr, b->frames_total * b->F * b->K * sizeof(float2)));
+    // auxiva_pca.py:79-81 for every problem in one launch, from the problem table
+    HIP_TRY(launch_pca_project(b->stream, b->X, b->What, b->Xr, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    *Xr_dev = b->Xr;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_compose_w(oiva_batch* outer, const oiva_batch* inner) {
+    NEED(outer != nullptr && inner != nullptr, OIVA_ERR_ARG, "null batch");
+    NEED(outer != inner, OIVA_ERR_ARG, "the reduced batch must be another batch");
+    NEED(inner->B == outer->B && inner->F == outer->F, OIVA_ERR_ARG, "the two batches differ in B or F");
+    NEED(inner->M == inner->K && inner->K == outer->K, OIVA_ERR_ARG,
+         "the reduced batch must be determined on the K channels of the projection");
+    NEED(inner->device == outer->device, OIVA_ERR_ARG, "the two batches live on different devices");
+    NEED(outer->have_w && inner->have_w, OIVA_ERR_STATE, "demixing matrices not set");
+    DeviceGuard guard(outer->device);
+    HIP_TRY(hipStreamSynchronize(inner->stream));
+    HIP_TRY(launch_pca_compose(outer->stream, outer->What, outer->What64, inner->What64, (long long)nbins(outer), outer->M, outer->K));
     return OIVA_OK;
 }
 

@@ -405,6 +405,14 @@ hipError_t launch_ragged_cov(hipStream_t s, const float2* X, const float* R, con
 // Cx [B*F][M*M] = (1 / T_b) * the sum of problem b's own nsplit_b unit-weight partials (as launch_sum_parts for one problem)
 hipError_t launch_ragged_sum_parts(hipStream_t s, const double* parts, const RaggedProblem* prob, double* Cx, int B, int F, int M);
 
+// The batched PCA front end (kernels_pca_batch.hip, batch.hip; auxiva_pca.py:79-81 and the composition of the filters behind it).
+//   project: Xr (sum T, F, K) packed = the K principal components of every problem's X, one launch from the problem table; What
+//   (B*F, M, M) holds P in columns 0..K-1.  The float32 chain of launch_demix_write without projection back, element by element.
+hipError_t launch_pca_project(hipStream_t s, const float2* X, const float2* What, float2* Xr, const RaggedProblem* prob, int B, int F,
+                              int M, int K, int kp, int max_pw_nsplit);
+//   compose: columns 0..K-1 of What64 (nbins, M, M) <- P[:, :K] * Wred (nbins, K, K) in float64, and rounded into What
+hipError_t launch_pca_compose(hipStream_t s, float2* What, double2* What64, const double2* Wred, long long nbins, int M, int K);
+
 // Batched OGIVE (kernels_ogive_batch.hip, batch.hip): B problems of one shape, <= 8 channels, K = 1, `precise` arithmetic.
 //   bin: OgiveState of the B*F bins (bin index = problem * F + bin; its ctrl / maxdelta are only the scratch ogive_init_kernel
 //   resets); done, epochs, maxdelta (B): the per-problem stopping rule; runmax, ticket (B): the step kernel's hand-off.

@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib, sharded
 from . import batch as _batch
 from . import ive as _ive
+from . import pca_batch as _pca_batch
 from . import stft as _stft
 from .batch import DeviceBatch
 from .overiva import get_device
@@ -184,12 +185,12 @@ def _check_separate_args(x, frame, hop, n_src, n_iter, algorithm, model, win_a, 
         dtype, M, lens = rooms.dtype, rooms.shape[2], [rooms.shape[1]] * rooms.shape[0]
     if dtype.kind not in "fiu":
         raise ValueError(f"x must be real, got dtype {dtype}")
-    if algorithm not in ("overiva", "ogive"):
-        raise ValueError(f"algorithm must be 'overiva' or 'ogive', got {algorithm!r}")
+    if algorithm not in ("overiva", "ogive", "auxiva_pca"):
+        raise ValueError(f"algorithm must be 'overiva', 'ogive' or 'auxiva_pca', got {algorithm!r}")
     if algorithm == "ogive" and ragged:
         raise ValueError("OGIVE does not run on a ragged batch: give algorithm='ogive' rooms of one length as a (B, n_samples, M) array")
-    if algorithm == "overiva" and algo_kwargs:
-        raise ValueError(f"unknown arguments for algorithm='overiva': {sorted(algo_kwargs)}")
+    if algorithm != "ogive" and algo_kwargs:
+        raise ValueError(f"unknown arguments for algorithm={algorithm!r}: {sorted(algo_kwargs)}")
     if set(algo_kwargs) - {"step_size", "tol", "update"}:
         raise ValueError(f"unknown arguments for algorithm='ogive': {sorted(set(algo_kwargs) - {'step_size', 'tol', 'update'})}")
     if algo_kwargs.get("update", "demix") not in _ive.UPDATE_IDS:
@@ -212,14 +213,7 @@ def _check_separate_args(x, frame, hop, n_src, n_iter, algorithm, model, win_a, 
         raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
     if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 0:
         raise ValueError("n_iter must be an integer >= 0")
-    if W0 is not None:
-        W0 = np.asarray(W0)
-        try:
-            shared = np.broadcast_shapes(W0.shape, (F, M, K)) == (F, M, K)
-        except ValueError:
-            shared = False
-        if not shared and W0.shape != (B, F, M, K):
-            raise ValueError(f"W0 has shape {W0.shape}: expected one broadcastable to {(F, M, K)} or {(B, F, M, K)}")
+    _batch._check_w0(W0, B, F, K if algorithm == "auxiva_pca" else M, K)      # (auxiva_pca: the start of the reduced solve)
     if sharded.active_group() is not None:
         raise ValueError("separate_batch does not run under enable_bin_sharding(): disable bin sharding for batched calls")
     return rooms, ragged, lens, int(M), int(hop), int(K), wa, ws, np.float64 if dtype == np.float64 else np.float32
@@ -228,8 +222,8 @@ def _check_separate_args(x, frame, hop, n_src, n_iter, algorithm, model, win_a, 
 def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva", model="laplace", win_a=None, win_s=None,
                    init_eig=False, W0=None, proj_back=True, return_filters=False, **algo_kwargs):
     """
-    Audio in, audio out for B rooms: STFT, ``overiva_batch`` / ``overiva_batch_ragged`` / ``ogive_batch`` and inverse STFT with
-    X and Y never leaving the device (the chain of reference overiva_sim.py:206-207, 298-315 for many rooms per call).
+    Audio in, audio out for B rooms: STFT, ``overiva_batch`` / ``overiva_batch_ragged`` / ``ogive_batch`` / ``auxiva_pca_batch``
+    and inverse STFT with X and Y never leaving the device (the chain of reference overiva_sim.py:206-207, 298-315 for many rooms per call).
 
     Parameters
     ----------
@@ -239,7 +233,9 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
         STFT frame length (even) and shift (default frame // 2); n_frames = n_samples // hop as ``stft.analysis``
     n_src, n_iter, model, init_eig, W0, proj_back, return_filters:
         as ``overiva_batch()`` (``n_src=None``: determined AuxIVA)
-    algorithm: "overiva" or "ogive" (one source, rooms of one length; ``step_size``, ``tol``, ``update`` as ``ogive_batch()``)
+    algorithm: "overiva", "ogive" (one source, rooms of one length; ``step_size``, ``tol``, ``update`` as ``ogive_batch()``) or
+        "auxiva_pca" (PCA to ``n_src`` channels, then determined AuxIVA, as ``auxiva_pca_batch()``: ``W0`` starts the reduced
+        solve, (n_freq, n_src, n_src); ``proj_back`` is ignored, the result is always projected back; W is the composed filters)
     win_a, win_s: analysis / synthesis windows; default ``stft.hann(frame)`` and its ``stft.compute_synthesis_window`` when
         hop < frame, rectangular otherwise
 
@@ -261,12 +257,17 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
             info = dict(plan.info(), audio=True)
             if algorithm == "ogive":
                 _run_ogive(plan, n_iter, W0, init_eig, model, info, **algo_kwargs)
+            elif algorithm == "auxiva_pca" and K < M:
+                _pca_batch.reduce_and_solve(plan, n_iter, W0, init_eig, model)
             else:
                 if W0 is None and init_eig:
                     plan.set_w_eig()
                 else:
                     plan.set_w(W0)
                 plan.iterate(n_iter)
+            if algorithm == "auxiva_pca":           # always projected back onto channel 0 of the input (auxiva_pca.py:89-90)
+                proj_back = True
+                info.update(algorithm="auxiva_pca", reduced=K)
             y = st.synthesis_device(plan.demix_device(proj_back))
             _batch._info = info
             if algorithm == "overiva":
