@@ -17,6 +17,7 @@
  *     everything it allocates; nothing returned by pointer outlives oiva_plan_destroy.
  *   - one plan = one device + one stream + one contiguous range of frequency bins.
  *     A plan is not thread-safe; distinct plans are independent.
+ *   - every entry point restores the calling thread's current device.
  *   - no call synchronises with the host except the ones documented to (copies to host,
  *     oiva_plan_sync, the timing helpers).
  */

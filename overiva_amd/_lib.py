@@ -238,6 +238,31 @@ def check(rc):
     raise HipError(msg)
 
 
+class Handle:
+    """Life cycle of one handle of the library: ``lib`` (set by the subclass), ``h`` (the handle once created, None when closed)
+    and ``_destroy``, the name of the function that takes it back"""
+
+    h = None
+    _destroy = None
+
+    def close(self):
+        if self.h:
+            getattr(self.lib, self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def ptr(a):
     """raw pointer of a C-contiguous numpy array"""
     assert a.flags["C_CONTIGUOUS"]

@@ -60,7 +60,7 @@ class DeviceBatch:
         return [out[off[b]:off[b + 1]] for b in range(len(self.frames))]
 
 
-class BatchPlan:
+class BatchPlan(_lib.Handle):
     """Owns the device state of B problems of shape (T, F, M) with K sources (``oiva_batch``).
 
     Stages as ``Plan``'s: ``set_x``, ``covariance``, ``set_w`` / ``set_w_eig``, ``iterate``, ``demix``, ``get_w``; ``status``
@@ -71,6 +71,7 @@ class BatchPlan:
     On the device X and Y are packed along the frames, (sum T_b, F, .): ``frames`` holds the B frame counts (here B times T)
     and ``offsets`` every problem's first frame."""
 
+    _destroy = "oiva_batch_destroy"
     dense = True          # X and Y are handed over as one (B, T, F, .) array
 
     def __init__(self, B, T, F, M, K, model="laplace", device=None, stream=None):
@@ -93,23 +94,6 @@ class BatchPlan:
     def _create(self, h, stream):
         return self.lib.oiva_batch_create(C.byref(h), self.device, self.B, self.T, self.F, self.M, self.K,
                                           _lib.MODEL_IDS[self.model], stream)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.oiva_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     @property
     def shape(self):
@@ -375,6 +359,34 @@ def overiva_batch(X, n_src=None, n_iter=20, proj_back=True, W0=None, model="lapl
         return _run_overiva(plan, X, dtype, n_iter, proj_back, W0, init_eig, return_filters, callback)
 
 
+def _run_ogive(plan, n_iter, W0, init_eig, model, step_size=0.1, tol=1e-3, update="demix", every_100=None):
+    """the epochs of OGIVE on a batch plan whose X and covariance are set: the start, ``ogive_begin`` and chunks of epochs until every
+    problem's stopping rule has fired or ``n_iter`` is reached, ``every_100()`` called at epochs 0, 100, 200, ... while any problem
+    runs; returns the (B,) arrays of epochs run and of rules met"""
+    B, F, M = plan.B, plan.F, plan.M
+    if W0 is None and init_eig:                                         # ive.py:111-126 per problem (host LAPACK; not conjugated)
+        cx = plan.get_cx(np.complex128)
+        W0 = np.empty((B, F, M, 1), np.complex128)
+        for b in range(B):
+            vals, vecs = np.linalg.eig(cx[b])
+            W0[b, :, :, 0] = np.stack([vecs[f][:, np.argmax(vals[f])] for f in range(F)])
+    plan.set_w(None if W0 is None else np.asarray(W0))
+    plan.ogive_begin(update, model)
+    epochs = np.zeros(B, dtype=int)
+    converged = np.zeros(B, dtype=bool)
+    epoch = 0
+    while epoch < n_iter and not converged.all():
+        if every_100 is not None and epoch % 100 == 0:                  # ive.py:199-205
+            every_100()
+        step = min(n_iter - epoch, _ive.CHUNK)
+        if every_100 is not None:
+            step = min(step, 100 - epoch % 100)
+        ran, converged, _ = plan.ogive_iterate(epoch, step, step_size, tol)
+        epochs += ran
+        epoch += step
+    return epochs, converged
+
+
 def ogive_batch(X, n_iter=4000, step_size=0.1, tol=1e-3, update="demix", proj_back=True, W0=None, model="laplace", init_eig=False,
                 return_filters=False, callback=None):
     """
@@ -404,26 +416,8 @@ def ogive_batch(X, n_iter=4000, step_size=0.1, tol=1e-3, update="demix", proj_ba
     with BatchPlan(B, T, F, M, 1, model) as plan:
         plan.set_x(X)
         plan.covariance()                                                   # ive.py:100
-        if W0 is None and init_eig:                                         # ive.py:111-126 per problem (host LAPACK; not conjugated)
-            cx = plan.get_cx(np.complex128)
-            W0 = np.empty((B, F, M, 1), np.complex128)
-            for b in range(B):
-                vals, vecs = np.linalg.eig(cx[b])
-                W0[b, :, :, 0] = np.stack([vecs[f][:, np.argmax(vals[f])] for f in range(F)])
-        plan.set_w(None if W0 is None else np.asarray(W0))
-        plan.ogive_begin(update, model)
-        epochs = np.zeros(B, dtype=int)
-        converged = np.zeros(B, dtype=bool)
-        epoch = 0
-        while epoch < n_iter and not converged.all():
-            if callback is not None and epoch % 100 == 0:                  # ive.py:199-205
-                callback(plan.demix(proj_back, dtype))
-            step = min(n_iter - epoch, _ive.CHUNK)
-            if callback is not None:
-                step = min(step, 100 - epoch % 100)
-            ran, converged, _ = plan.ogive_iterate(epoch, step, step_size, tol)
-            epochs += ran
-            epoch += step
+        every_100 = None if callback is None else lambda: callback(plan.demix(proj_back, dtype))
+        epochs, converged = _run_ogive(plan, n_iter, W0, init_eig, model, step_size, tol, update, every_100)
         Y = plan.demix(proj_back, dtype)                                    # ive.py:249-256
         _info = dict(plan.info(), algorithm="ogive", epochs=[int(e) for e in epochs], converged=[bool(c) for c in converged])
         w = plan.get_w(np.complex128)               # (raises LinAlgError naming the non-finite problems)

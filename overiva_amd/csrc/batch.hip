@@ -14,25 +14,12 @@
 #include <utility>
 #include <vector>
 
+#include "host_util.h"
 #include "oiva_internal.h"
 
 using namespace oiva;
 
 namespace {
-
-#define HIP_TRY(expr)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) return fail_with(OIVA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-#define NEED(cond, code, msg)                       \
-    do {                                            \
-        if (!(cond)) return fail_with(code, msg);   \
-    } while (0)
-
-int ceil_div(int a, int b) { return (a + b - 1) / b; }
-int round_up(int a, int b) { return ceil_div(a, b) * b; }
 
 constexpr int kBatchMaxChannels = 8;
 constexpr int kCovFramesPerSplit = 256;   // frame splits of the covariance pass: ceil(T / 256), a function of T alone
@@ -58,33 +45,6 @@ FrameGeom frame_geom(int T) {
     g.pw_nsplit = ceil_div(T, g.tcp);
     return g;
 }
-
-// the single-problem plan's statistics geometry (plan.hip, choose_stats_geom) for F bins: Y as overiva() writes it
-CovGeom stats_geom(int T, int F, int K, int n_cu) {
-    CovGeom g{};
-    g.nbg = ceil_div(F, kBinsPerWave);
-    g.kc = 2;
-    const int blocks = g.nbg * ceil_div(K, g.kc);
-    int ns = std::max(1, n_cu * 4 / std::max(1, blocks));
-    ns = std::min(ns, std::max(1, T / 128));
-    ns = std::min(16, ns);
-    g.tc = round_up(ceil_div(T, ns), 16);
-    g.nsplit = ceil_div(T, g.tc);
-    return g;
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
 
 }  // namespace
 
@@ -118,7 +78,7 @@ struct oiva_batch {
     RaggedProblem* probs_dev = nullptr;
     bool ragged = false;           // made by oiva_batch_create_ragged: the kernels that read the table (dense_args otherwise)
     bool have_x = false, have_cx = false, have_w = false;
-    std::vector<std::pair<int, hipGraphExec_t>> graphs;
+    GraphCache graphs{kGraphCache};    // by iterations per replay
     hipEvent_t ev[5] = {};
     // batched OGIVE (ive.py:33-256): per-bin state of B*F bins and the per-problem stopping rule, allocated by ogive_begin
     OgiveBatchState og{};
@@ -138,14 +98,12 @@ namespace {
 size_t nbins(const oiva_batch* b) { return (size_t)b->B * b->F; }
 
 int drop_graphs(oiva_batch* b) {
-    while (!b->graphs.empty()) {
-        HIP_TRY(hipGraphExecDestroy(b->graphs.back().second));
-        b->graphs.pop_back();
-    }
+    const int rc = b->graphs.clear();
+    if (rc) return rc;
     if (b->og_graph) {
         hipGraphExec_t g = b->og_graph;
         b->og_graph = nullptr;
-        HIP_TRY(hipGraphExecDestroy(g));
+        OIVA_TRY_HIP(hipGraphExecDestroy(g));
     }
     return OIVA_OK;
 }
@@ -185,24 +143,24 @@ DenseArgs dense_args(const oiva_batch* b) {
 // the four launches of one iteration (overiva.py:138-190)
 int stage(oiva_batch* b, int s) {
     if (s == 3) {
-        HIP_TRY(launch_update(b->stream, update_args(b, false)));
+        OIVA_TRY_HIP(launch_update(b->stream, update_args(b, false)));
     } else if (b->ragged) {
         if (s == 0)
-            HIP_TRY(launch_ragged_power(b->stream, b->X, b->What, b->Ppart, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit,
+            OIVA_TRY_HIP(launch_ragged_power(b->stream, b->X, b->What, b->Ppart, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit,
                                         b->tcp));
         else if (s == 1)
-            HIP_TRY(launch_ragged_activation(b->stream, b->Ppart, b->nb, b->R, b->probs_dev, b->B, b->K, b->model, b->F, b->rblocks));
+            OIVA_TRY_HIP(launch_ragged_activation(b->stream, b->Ppart, b->nb, b->R, b->probs_dev, b->B, b->K, b->model, b->F, b->rblocks));
         else
-            HIP_TRY(launch_ragged_cov(b->stream, b->X, b->R, b->probs_dev, b->wscale, b->model, b->Vpart, b->B, b->F, b->M, b->K,
+            OIVA_TRY_HIP(launch_ragged_cov(b->stream, b->X, b->R, b->probs_dev, b->wscale, b->model, b->Vpart, b->B, b->F, b->M, b->K,
                                       b->nsplit));
     } else {
         const DenseArgs d = dense_args(b);
         if (s == 0)
-            HIP_TRY(launch_batch_power(b->stream, b->X, b->What, b->Ppart, b->B, d.T, b->F, b->M, b->K, b->kp, d.pw_nsplit, d.tcp));
+            OIVA_TRY_HIP(launch_batch_power(b->stream, b->X, b->What, b->Ppart, b->B, d.T, b->F, b->M, b->K, b->kp, d.pw_nsplit, d.tcp));
         else if (s == 1)
-            HIP_TRY(launch_batch_activation(b->stream, b->Ppart, b->nb, b->R, d.r_stride, b->B, d.T, b->K, b->model, b->F));
+            OIVA_TRY_HIP(launch_batch_activation(b->stream, b->Ppart, b->nb, b->R, d.r_stride, b->B, d.T, b->K, b->model, b->F));
         else
-            HIP_TRY(launch_batch_cov(b->stream, b->X, b->R, d.r_stride, b->wscale, b->model, b->Vpart, b->B, d.T, b->F, b->M, b->K,
+            OIVA_TRY_HIP(launch_batch_cov(b->stream, b->X, b->R, d.r_stride, b->wscale, b->model, b->Vpart, b->B, d.T, b->F, b->M, b->K,
                                      d.nsplit, d.tc));
     }
     return OIVA_OK;
@@ -218,58 +176,29 @@ int one_iteration(oiva_batch* b) {
 
 // the executable graph of `iters` iterations on the batch's stream: one linear chain of 4 * iters kernel nodes
 int graph_for(oiva_batch* b, int iters, hipGraphExec_t* out) {
-    for (auto& g : b->graphs)
-        if (g.first == iters) {
-            *out = g.second;
-            return OIVA_OK;
-        }
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    HIP_TRY(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
-    int r = OIVA_OK;
-    for (int i = 0; i < iters && r == OIVA_OK; ++i) r = one_iteration(b);
-    hipError_t e = hipStreamEndCapture(b->stream, &graph);
-    if (r) {
-        if (graph) (void)hipGraphDestroy(graph);
+    return b->graphs.get(b->stream, iters, [&] {
+        int r = OIVA_OK;
+        for (int i = 0; i < iters && r == OIVA_OK; ++i) r = one_iteration(b);
         return r;
-    }
-    HIP_TRY(e);
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    HIP_TRY(e);
-    HIP_TRY(hipGraphUpload(exec, b->stream));
-    if ((int)b->graphs.size() >= kGraphCache) {
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        HIP_TRY(hipGraphExecDestroy(b->graphs.front().second));
-        b->graphs.erase(b->graphs.begin());
-    }
-    b->graphs.emplace_back(iters, exec);
-    *out = exec;
-    return OIVA_OK;
+    }, out);
 }
 
 int check_ready(oiva_batch* b) {
-    NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
-    NEED(b->have_x, OIVA_ERR_STATE, "X not set (oiva_batch_set_x_host/_dev)");
-    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
-    NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set (oiva_batch_set_w)");
+    OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(b->have_x, OIVA_ERR_STATE, "X not set (oiva_batch_set_x_host/_dev)");
+    OIVA_NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
+    OIVA_NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set (oiva_batch_set_w)");
     return OIVA_OK;
 }
 
-// W_hat of every bin in complex128, and the problems whose W (the first K columns) holds a non-finite value
-int download_w(oiva_batch* b, std::vector<double2>& wh, std::vector<int>& bad) {
-    const size_t MM = (size_t)b->M * b->M;
-    wh.resize(nbins(b) * MM);
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(wh.data(), b->What64, wh.size() * sizeof(double2), hipMemcpyDeviceToHost));
+// W_hat of every bin in complex128; W (its first K columns) into W_host (B, F, M, K) unless that is nullptr; bad (B): the problems
+// whose W holds a non-finite value
+int download_w(oiva_batch* b, void* W_host, int f64, std::vector<int>& bad) {
+    std::vector<double2> wh(nbins(b) * b->M * b->M);
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(wh.data(), b->What64, wh.size() * sizeof(double2), hipMemcpyDeviceToHost));
     bad.assign(b->B, 0);
-    for (int p = 0; p < b->B; ++p)
-        for (size_t f = 0; f < (size_t)b->F && !bad[p]; ++f)
-            for (int r = 0; r < b->M; ++r)
-                for (int k = 0; k < b->K; ++k) {
-                    const double2 v = wh[(((size_t)p * b->F + f) * b->M + r) * b->M + k];
-                    if (!std::isfinite(v.x) || !std::isfinite(v.y)) bad[p] = 1;
-                }
+    for (int p = 0; p < b->B; ++p) bad[p] = !unpack_w(wh, (size_t)p * b->F, (size_t)b->F, b->M, b->K, W_host, f64);
     return OIVA_OK;
 }
 
@@ -277,7 +206,7 @@ int download_w(oiva_batch* b, std::vector<double2>& wh, std::vector<int>& bad) {
 int demix_on_device(oiva_batch* b, int proj_back) {
     const int F = b->F, M = b->M, K = b->K;
     const size_t ny = b->frames_total * F * K;
-    if (!b->Y) HIP_TRY(hipMalloc((void**)&b->Y, ny * sizeof(float2)));
+    if (!b->Y) OIVA_TRY_HIP(dev_malloc(&b->Y, ny * sizeof(float2)));
     // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0]):
     // every problem at its packed frame offset with the statistics geometry of its own T_b
     for (int p = 0; p < b->B; ++p) {
@@ -286,8 +215,8 @@ int demix_on_device(oiva_batch* b, int proj_back) {
         const CovGeom& stg = b->stgs[p];
         const float2* Xb = b->X + t0 * F * M;
         const float2* Wb = b->What + (size_t)p * F * M * M;
-        if (proj_back) HIP_TRY(launch_demix_stats(b->stream, Xb, Wb, b->Spart, T, F, M, K, stg));
-        HIP_TRY(launch_demix_write(b->stream, Xb, Wb, proj_back ? b->Spart : nullptr, stg.nsplit, b->Y + t0 * F * K, T, F, M, K));
+        if (proj_back) OIVA_TRY_HIP(launch_demix_stats(b->stream, Xb, Wb, b->Spart, T, F, M, K, stg));
+        OIVA_TRY_HIP(launch_demix_write(b->stream, Xb, Wb, proj_back ? b->Spart : nullptr, stg.nsplit, b->Y + t0 * F * K, T, F, M, K));
     }
     return OIVA_OK;
 }
@@ -303,30 +232,17 @@ void free_all(oiva_batch* b) {
     if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
 }
 
-// the batch of frames[p] frames per problem (T = the largest); arguments checked by the callers
-int create_batch(oiva_batch** out, int device, const std::vector<int>& frames, int F, int M, int K, int model, void* stream) {
-    const int B = (int)frames.size(), T = *std::max_element(frames.begin(), frames.end());
-    DeviceGuard guard(device);
-    oiva_batch* b = new oiva_batch;
-    b->device = device;
-    b->B = B, b->T = T, b->F = F, b->M = M, b->K = K, b->model = model;
-    auto bail = [&](int rc) {
-        free_all(b);
-        delete b;
-        return rc;
-    };
-#define TRY_CREATE(expr)                                                                                          \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return bail(fail_with(OIVA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); \
-    } while (0)
+// stream, events, the problem table and the buffers of a new batch of frames[p] frames per problem; whatever it made before a
+// failure is the caller's to free
+int fill_batch(oiva_batch* b, const std::vector<int>& frames, void* stream) {
+    const int device = b->device, B = b->B, T = b->T, F = b->F, M = b->M, K = b->K;
     if (stream) {
         b->stream = static_cast<hipStream_t>(stream);
     } else {
-        TRY_CREATE(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        OIVA_TRY_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
         b->own_stream = true;
     }
-    for (hipEvent_t& e : b->ev) TRY_CREATE(hipEventCreate(&e));
+    for (hipEvent_t& e : b->ev) OIVA_TRY_HIP(hipEventCreate(&e));
     // every problem's record from its own T_b: functions of T_b, F, M, K alone (never of B); the grids (nsplit, pw_nsplit, tcp,
     // rblocks) take the largest
     b->kp = pow_sources_per_pass(M, K);
@@ -360,19 +276,33 @@ int create_batch(oiva_batch** out, int device, const std::vector<int>& frames, i
     }
     b->frames_total = x_off;
     const size_t ppart_floats = p_off, r_floats = r_off;
-    TRY_CREATE(hipMalloc((void**)&b->probs_dev, (size_t)B * sizeof(RaggedProblem)));
-    TRY_CREATE(hipMemcpy(b->probs_dev, b->probs.data(), (size_t)B * sizeof(RaggedProblem), hipMemcpyHostToDevice));
+    OIVA_TRY_HIP(dev_malloc(&b->probs_dev, (size_t)B * sizeof(RaggedProblem)));
+    OIVA_TRY_HIP(hipMemcpy(b->probs_dev, b->probs.data(), (size_t)B * sizeof(RaggedProblem), hipMemcpyHostToDevice));
     const size_t MM = (size_t)M * M;
-    TRY_CREATE(hipMalloc((void**)&b->What, nbins(b) * MM * sizeof(float2)));
-    TRY_CREATE(hipMalloc((void**)&b->What64, nbins(b) * MM * sizeof(double2)));
-    TRY_CREATE(hipMalloc((void**)&b->Cx, nbins(b) * MM * sizeof(double)));
-    TRY_CREATE(hipMalloc((void**)&b->Vpart, ((size_t)b->nsplit * nbins(b) * K * MM + 2) * sizeof(double)));   // sum_vpart reads idx + 1
-    TRY_CREATE(hipMalloc((void**)&b->Ppart, ppart_floats * sizeof(float)));
-    TRY_CREATE(hipMalloc((void**)&b->R, r_floats * sizeof(float)));
-    TRY_CREATE(hipMemset(b->R, 0, r_floats * sizeof(float)));      // (the pad rows behind every problem's r)
-    TRY_CREATE(hipMalloc((void**)&b->wscale, (size_t)B * K * sizeof(float)));
-    TRY_CREATE(hipMalloc((void**)&b->Spart, (size_t)spart_splits * F * K * 3 * sizeof(float)));
-#undef TRY_CREATE
+    OIVA_TRY_HIP(dev_malloc(&b->What, nbins(b) * MM * sizeof(float2)));
+    OIVA_TRY_HIP(dev_malloc(&b->What64, nbins(b) * MM * sizeof(double2)));
+    OIVA_TRY_HIP(dev_malloc(&b->Cx, nbins(b) * MM * sizeof(double)));
+    OIVA_TRY_HIP(dev_malloc(&b->Vpart, ((size_t)b->nsplit * nbins(b) * K * MM + 2) * sizeof(double)));   // sum_vpart reads idx + 1
+    OIVA_TRY_HIP(dev_malloc(&b->Ppart, ppart_floats * sizeof(float)));
+    OIVA_TRY_HIP(dev_malloc(&b->R, r_floats * sizeof(float)));
+    OIVA_TRY_HIP(hipMemset(b->R, 0, r_floats * sizeof(float)));      // (the pad rows behind every problem's r)
+    OIVA_TRY_HIP(dev_malloc(&b->wscale, (size_t)B * K * sizeof(float)));
+    OIVA_TRY_HIP(dev_malloc(&b->Spart, (size_t)spart_splits * F * K * 3 * sizeof(float)));
+    return OIVA_OK;
+}
+
+// the batch of frames[p] frames per problem (T = the largest); arguments checked by the callers
+int create_batch(oiva_batch** out, int device, const std::vector<int>& frames, int F, int M, int K, int model, void* stream) {
+    DeviceGuard guard(device);
+    oiva_batch* b = new oiva_batch;
+    b->device = device;
+    b->B = (int)frames.size(), b->T = *std::max_element(frames.begin(), frames.end()), b->F = F, b->M = M, b->K = K, b->model = model;
+    const int rc = fill_batch(b, frames, stream);
+    if (rc) {
+        free_all(b);
+        delete b;
+        return rc;
+    }
     *out = b;
     return OIVA_OK;
 }
@@ -382,33 +312,33 @@ int create_batch(oiva_batch** out, int device, const std::vector<int>& frames, i
 extern "C" {
 
 int oiva_batch_create(oiva_batch** out, int device, int B, int T, int F, int M, int K, int model, void* stream) {
-    NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
+    OIVA_NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
     *out = nullptr;
-    NEED(B >= 1 && T >= 1 && F >= 1, OIVA_ERR_ARG, "B, T and F must be >= 1");
-    NEED(M >= 1 && M <= kBatchMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
-    NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "number of sources must be in 1..M");
-    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
-    NEED((double)B * T * F * M < 4e9, OIVA_ERR_ARG, "batch too large");
+    OIVA_NEED(B >= 1 && T >= 1 && F >= 1, OIVA_ERR_ARG, "B, T and F must be >= 1");
+    OIVA_NEED(M >= 1 && M <= kBatchMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
+    OIVA_NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "number of sources must be in 1..M");
+    OIVA_NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
+    OIVA_NEED((double)B * T * F * M < 4e9, OIVA_ERR_ARG, "batch too large");
     return create_batch(out, device, std::vector<int>((size_t)B, T), F, M, K, model, stream);
 }
 
 oiva_status oiva_batch_create_ragged(oiva_batch** out, int device, int B, const int* frames, int F, int M, int K, int model,
                                      void* stream) {
-    NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
+    OIVA_NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
     *out = nullptr;
-    NEED(frames != nullptr, OIVA_ERR_ARG, "null frames");
-    NEED(B >= 1 && F >= 1, OIVA_ERR_ARG, "B and F must be >= 1");
-    NEED(M >= 1 && M <= kBatchMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
-    NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "number of sources must be in 1..M");
-    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
+    OIVA_NEED(frames != nullptr, OIVA_ERR_ARG, "null frames");
+    OIVA_NEED(B >= 1 && F >= 1, OIVA_ERR_ARG, "B and F must be >= 1");
+    OIVA_NEED(M >= 1 && M <= kBatchMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
+    OIVA_NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "number of sources must be in 1..M");
+    OIVA_NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
     double total = 0.;
     int tmax = 0;
     for (int p = 0; p < B; ++p) {
-        NEED(frames[p] >= 1, OIVA_ERR_ARG, "every problem needs T >= 1 frames (problem " + std::to_string(p) + ")");
+        OIVA_NEED(frames[p] >= 1, OIVA_ERR_ARG, "every problem needs T >= 1 frames (problem " + std::to_string(p) + ")");
         total += frames[p];
         tmax = std::max(tmax, frames[p]);
     }
-    NEED(total * F * M < 4e9 && (double)B * F * M * M * K * ceil_div(tmax, kCovFramesPerSplit) < 4e9, OIVA_ERR_ARG, "batch too large");
+    OIVA_NEED(total * F * M < 4e9 && (double)B * F * M * M * K * ceil_div(tmax, kCovFramesPerSplit) < 4e9, OIVA_ERR_ARG, "batch too large");
     const int rc = create_batch(out, device, std::vector<int>(frames, frames + B), F, M, K, model, stream);
     if (rc == OIVA_OK) (*out)->ragged = true;
     return rc;
@@ -424,16 +354,16 @@ int oiva_batch_destroy(oiva_batch* b) {
 }
 
 int oiva_batch_set_x_host(oiva_batch* b, const void* X, int f64) {
-    NEED(b && X, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(b && X, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(b->device);
     const size_t n = b->frames_total * b->F * b->M;
-    if (!b->X_owned) HIP_TRY(hipMalloc((void**)&b->X_owned, n * sizeof(float2)));
-    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (!b->X_owned) OIVA_TRY_HIP(dev_malloc(&b->X_owned, n * sizeof(float2)));
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
     if (f64) {
         // converted on the device, through a bounded staging buffer
         const size_t chunk = std::min(n, kStageBytes / sizeof(double2));
         double2* stage_buf = nullptr;
-        HIP_TRY(hipMalloc((void**)&stage_buf, chunk * sizeof(double2)));
+        OIVA_TRY_HIP(dev_malloc(&stage_buf, chunk * sizeof(double2)));
         hipError_t e = hipSuccess;
         for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += chunk) {
             const size_t m = std::min(chunk, n - i0);
@@ -442,9 +372,9 @@ int oiva_batch_set_x_host(oiva_batch* b, const void* X, int f64) {
             if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
         }
         (void)hipFree(stage_buf);
-        HIP_TRY(e);
+        OIVA_TRY_HIP(e);
     } else {
-        HIP_TRY(hipMemcpy(b->X_owned, X, n * sizeof(float2), hipMemcpyHostToDevice));
+        OIVA_TRY_HIP(hipMemcpy(b->X_owned, X, n * sizeof(float2), hipMemcpyHostToDevice));
     }
     if (b->X != b->X_owned) {          // captured graphs hold the pointer of X
         const int rc = drop_graphs(b);
@@ -457,10 +387,10 @@ int oiva_batch_set_x_host(oiva_batch* b, const void* X, int f64) {
 }
 
 int oiva_batch_set_x_dev(oiva_batch* b, const void* X_dev) {
-    NEED(b && X_dev, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(b && X_dev, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(b->device);
     if (b->X != X_dev) {
-        HIP_TRY(hipStreamSynchronize(b->stream));
+        OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
         const int rc = drop_graphs(b);
         if (rc) return rc;
     }
@@ -471,83 +401,68 @@ int oiva_batch_set_x_dev(oiva_batch* b, const void* X_dev) {
 }
 
 int oiva_batch_covariance(oiva_batch* b) {
-    NEED(b, OIVA_ERR_ARG, "null batch");
-    NEED(b->have_x, OIVA_ERR_STATE, "X not set");
+    OIVA_NEED(b, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(b->have_x, OIVA_ERR_STATE, "X not set");
     DeviceGuard guard(b->device);
     // unit weights, one "source": partials [nsplit][B*F][1][M*M]; problem b's own nsplit_b partials added in split order and
     // divided by T_b (overiva.py:87)
     if (b->ragged) {
-        HIP_TRY(launch_ragged_cov(b->stream, b->X, nullptr, b->probs_dev, nullptr, b->model, b->Vpart, b->B, b->F, b->M, 1, b->nsplit));
-        HIP_TRY(launch_ragged_sum_parts(b->stream, b->Vpart, b->probs_dev, b->Cx, b->B, b->F, b->M));
+        OIVA_TRY_HIP(launch_ragged_cov(b->stream, b->X, nullptr, b->probs_dev, nullptr, b->model, b->Vpart, b->B, b->F, b->M, 1, b->nsplit));
+        OIVA_TRY_HIP(launch_ragged_sum_parts(b->stream, b->Vpart, b->probs_dev, b->Cx, b->B, b->F, b->M));
     } else {
         const DenseArgs d = dense_args(b);
-        HIP_TRY(launch_batch_cov(b->stream, b->X, nullptr, 0, nullptr, b->model, b->Vpart, b->B, d.T, b->F, b->M, 1, d.nsplit, d.tc));
-        HIP_TRY(launch_sum_parts(b->stream, b->Vpart, true, d.nsplit, b->Cx, (long long)nbins(b) * b->M * b->M, 1. / (double)d.T));
+        OIVA_TRY_HIP(launch_batch_cov(b->stream, b->X, nullptr, 0, nullptr, b->model, b->Vpart, b->B, d.T, b->F, b->M, 1, d.nsplit, d.tc));
+        OIVA_TRY_HIP(launch_sum_parts(b->stream, b->Vpart, true, d.nsplit, b->Cx, (long long)nbins(b) * b->M * b->M, 1. / (double)d.T));
     }
     b->have_cx = true;
     return OIVA_OK;
 }
 
 int oiva_batch_set_w(oiva_batch* b, const void* W0, int f64) {
-    NEED(b, OIVA_ERR_ARG, "null batch");
-    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (needed for the orthogonality constraint)");
+    OIVA_NEED(b, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (needed for the orthogonality constraint)");
     DeviceGuard guard(b->device);
     const int M = b->M, K = b->K;
-    const size_t nb = nbins(b);
-    std::vector<double2> wh(nb * M * M, make_double2(0., 0.));
-    for (size_t f = 0; f < nb; ++f) {
-        double2* m = wh.data() + f * M * M;
-        for (int r = 0; r < M; ++r)
-            for (int k = 0; k < K; ++k) {
-                const size_t i = (f * M + r) * K + k;
-                if (!W0)
-                    m[r * M + k] = make_double2(r == k ? 1. : 0., 0.);               // overiva.py:113-114
-                else if (f64)
-                    m[r * M + k] = static_cast<const double2*>(W0)[i];                // overiva.py:116-117
-                else
-                    m[r * M + k] = make_double2(static_cast<const float2*>(W0)[i].x, static_cast<const float2*>(W0)[i].y);
-            }
-        for (int r = K; r < M; ++r) m[r * M + r] = make_double2(-1., 0.);           // overiva.py:122-123
-    }
+    const std::vector<double2> wh = pack_what(W0, f64, nbins(b), M, K);
     std::vector<float2> w32(wh.size());
     for (size_t i = 0; i < wh.size(); ++i) w32[i] = make_float2((float)wh[i].x, (float)wh[i].y);
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(b->What, w32.data(), w32.size() * sizeof(float2), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->What64, wh.data(), wh.size() * sizeof(double2), hipMemcpyHostToDevice));
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(b->What, w32.data(), w32.size() * sizeof(float2), hipMemcpyHostToDevice));
+    OIVA_TRY_HIP(hipMemcpy(b->What64, wh.data(), wh.size() * sizeof(double2), hipMemcpyHostToDevice));
     b->have_w = true;
-    if (K < M) HIP_TRY(launch_update(b->stream, update_args(b, true)));   // J from the orthogonality constraint, overiva.py:120-121
+    if (K < M) OIVA_TRY_HIP(launch_update(b->stream, update_args(b, true)));   // J from the orthogonality constraint, overiva.py:120-121
     return OIVA_OK;
 }
 
 int oiva_batch_set_w_eig(oiva_batch* b) {
-    NEED(b, OIVA_ERR_ARG, "null batch");
-    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
+    OIVA_NEED(b, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
     DeviceGuard guard(b->device);
     // overiva.py:106-109 per bin, the device eigensolver on B*F bins
-    HIP_TRY(launch_pca_subspace(b->stream, b->Cx, b->What, b->What64, nullptr, (int)nbins(b), b->M, b->K, true));
+    OIVA_TRY_HIP(launch_pca_subspace(b->stream, b->Cx, b->What, b->What64, nullptr, (int)nbins(b), b->M, b->K, true));
     b->have_w = true;
-    if (b->K < b->M) HIP_TRY(launch_update(b->stream, update_args(b, true)));
+    if (b->K < b->M) OIVA_TRY_HIP(launch_update(b->stream, update_args(b, true)));
     return OIVA_OK;
 }
 
 int oiva_batch_iterate(oiva_batch* b, int n) {
     int rc = check_ready(b);
     if (rc) return rc;
-    NEED(n >= 0, OIVA_ERR_ARG, "n must be >= 0");
+    OIVA_NEED(n >= 0, OIVA_ERR_ARG, "n must be >= 0");
     DeviceGuard guard(b->device);
     while (n > 0) {
         const int it = std::min(n, kGraphMaxIters);
         hipGraphExec_t g = nullptr;
         rc = graph_for(b, it, &g);
         if (rc) return rc;
-        HIP_TRY(hipGraphLaunch(g, b->stream));
+        OIVA_TRY_HIP(hipGraphLaunch(g, b->stream));
         n -= it;
     }
     return OIVA_OK;
 }
 
 int oiva_batch_demix(oiva_batch* b, void* Y_host, int f64, int proj_back) {
-    NEED(Y_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(Y_host, OIVA_ERR_ARG, "null argument");
     int rc = check_ready(b);
     if (rc) return rc;
     DeviceGuard guard(b->device);
@@ -555,48 +470,35 @@ int oiva_batch_demix(oiva_batch* b, void* Y_host, int f64, int proj_back) {
     if (rc) return rc;
     const size_t ny = b->frames_total * b->F * b->K;
     if (f64) {
-        if (!b->Y128) HIP_TRY(hipMalloc((void**)&b->Y128, ny * sizeof(double2)));
-        HIP_TRY(launch_cast_c64_to_c128(b->stream, b->Y, b->Y128, (long long)ny));
+        if (!b->Y128) OIVA_TRY_HIP(dev_malloc(&b->Y128, ny * sizeof(double2)));
+        OIVA_TRY_HIP(launch_cast_c64_to_c128(b->stream, b->Y, b->Y128, (long long)ny));
     }
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(Y_host, f64 ? (const void*)b->Y128 : (const void*)b->Y, ny * (f64 ? sizeof(double2) : sizeof(float2)),
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(Y_host, f64 ? (const void*)b->Y128 : (const void*)b->Y, ny * (f64 ? sizeof(double2) : sizeof(float2)),
                       hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 
 oiva_status oiva_batch_demix_dev(oiva_batch* b, int proj_back, void** Y_dev) {
-    NEED(Y_dev != nullptr, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(Y_dev != nullptr, OIVA_ERR_ARG, "null argument");
     *Y_dev = nullptr;
     int rc = check_ready(b);
     if (rc) return rc;
     DeviceGuard guard(b->device);
     rc = demix_on_device(b, proj_back);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
     *Y_dev = b->Y;
     return OIVA_OK;
 }
 
 int oiva_batch_get_w(oiva_batch* b, void* W_host, int f64) {
-    NEED(b && W_host, OIVA_ERR_ARG, "null argument");
-    NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set");
+    OIVA_NEED(b && W_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set");
     DeviceGuard guard(b->device);
-    std::vector<double2> wh;
     std::vector<int> bad;
-    const int rc = download_w(b, wh, bad);
+    const int rc = download_w(b, W_host, f64, bad);
     if (rc) return rc;
-    const int M = b->M, K = b->K;
-    const size_t nb = nbins(b);
-    for (size_t f = 0; f < nb; ++f)
-        for (int r = 0; r < M; ++r)
-            for (int k = 0; k < K; ++k) {
-                const double2 v = wh[(f * M + r) * M + k];
-                const size_t i = (f * M + r) * K + k;
-                if (f64)
-                    static_cast<double2*>(W_host)[i] = v;
-                else
-                    static_cast<float2*>(W_host)[i] = make_float2((float)v.x, (float)v.y);
-            }
     std::string which;
     for (int p = 0; p < b->B; ++p)
         if (bad[p]) which += (which.empty() ? "" : ", ") + std::to_string(p);
@@ -606,12 +508,11 @@ int oiva_batch_get_w(oiva_batch* b, void* W_host, int f64) {
 }
 
 int oiva_batch_status(oiva_batch* b, int* status) {
-    NEED(b && status, OIVA_ERR_ARG, "null argument");
-    NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set");
+    OIVA_NEED(b && status, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set");
     DeviceGuard guard(b->device);
-    std::vector<double2> wh;
     std::vector<int> bad;
-    const int rc = download_w(b, wh, bad);
+    const int rc = download_w(b, nullptr, 0, bad);
     if (rc) return rc;
     std::copy(bad.begin(), bad.end(), status);
     return OIVA_OK;
@@ -620,21 +521,21 @@ int oiva_batch_status(oiva_batch* b, int* status) {
 int oiva_batch_time_stages(oiva_batch* b, int n, float* total_ms, float* per_stage_ms) {
     int rc = check_ready(b);
     if (rc) return rc;
-    NEED(n >= 1 && total_ms, OIVA_ERR_ARG, "n must be >= 1");
+    OIVA_NEED(n >= 1 && total_ms, OIVA_ERR_ARG, "n must be >= 1");
     DeviceGuard guard(b->device);
     if (per_stage_ms) {
         double acc[4] = {0., 0., 0., 0.};
         for (int i = 0; i < n; ++i) {
-            HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+            OIVA_TRY_HIP(hipEventRecord(b->ev[0], b->stream));
             for (int s = 0; s < 4; ++s) {
                 rc = stage(b, s);
                 if (rc) return rc;
-                HIP_TRY(hipEventRecord(b->ev[s + 1], b->stream));
+                OIVA_TRY_HIP(hipEventRecord(b->ev[s + 1], b->stream));
             }
-            HIP_TRY(hipEventSynchronize(b->ev[4]));
+            OIVA_TRY_HIP(hipEventSynchronize(b->ev[4]));
             for (int s = 0; s < 4; ++s) {
                 float ms = 0.f;
-                HIP_TRY(hipEventElapsedTime(&ms, b->ev[s], b->ev[s + 1]));
+                OIVA_TRY_HIP(hipEventElapsedTime(&ms, b->ev[s], b->ev[s + 1]));
                 acc[s] += ms;
             }
         }
@@ -643,74 +544,59 @@ int oiva_batch_time_stages(oiva_batch* b, int n, float* total_ms, float* per_sta
     hipGraphExec_t g = nullptr;
     rc = graph_for(b, std::min(n, kGraphMaxIters), &g);
     if (rc) return rc;
-    HIP_TRY(hipGraphLaunch(g, b->stream));          // (warm)
-    HIP_TRY(hipEventRecord(b->ev[0], b->stream));
-    HIP_TRY(hipGraphLaunch(g, b->stream));
-    HIP_TRY(hipEventRecord(b->ev[1], b->stream));
-    HIP_TRY(hipEventSynchronize(b->ev[1]));
+    OIVA_TRY_HIP(hipGraphLaunch(g, b->stream));          // (warm)
+    OIVA_TRY_HIP(hipEventRecord(b->ev[0], b->stream));
+    OIVA_TRY_HIP(hipGraphLaunch(g, b->stream));
+    OIVA_TRY_HIP(hipEventRecord(b->ev[1], b->stream));
+    OIVA_TRY_HIP(hipEventSynchronize(b->ev[1]));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+    OIVA_TRY_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
     *total_ms = ms / (float)std::min(n, kGraphMaxIters);
     return OIVA_OK;
 }
 
 // ---- batched OGIVE (reference ive.py:33-256, one problem per batch entry) -------------------------------------------------
 oiva_status oiva_batch_get_cx(oiva_batch* b, void* Cx_host, int f64) {
-    NEED(b && Cx_host, OIVA_ERR_ARG, "null argument");
-    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
+    OIVA_NEED(b && Cx_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
     DeviceGuard guard(b->device);
     const size_t n = nbins(b) * b->M * b->M;
     const size_t bytes = n * (f64 ? sizeof(double2) : sizeof(float2));
     void* full = nullptr;
-    HIP_TRY(hipMalloc(&full, bytes));
+    OIVA_TRY_HIP(dev_malloc(&full, bytes));
     hipError_t e = launch_unpack_herm(b->stream, b->Cx, full, f64 != 0, (long long)nbins(b), b->M);
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e == hipSuccess) e = hipMemcpy(Cx_host, full, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(full);
-    HIP_TRY(e);
+    OIVA_TRY_HIP(e);
     return OIVA_OK;
 }
 
 oiva_status oiva_batch_ogive_begin(oiva_batch* b, int update_mode, int model) {
-    NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
-    NEED(!b->ragged, OIVA_ERR_ARG, "OGIVE is not supported on a ragged batch");
+    OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(!b->ragged, OIVA_ERR_ARG, "OGIVE is not supported on a ragged batch");
     int rc = check_ready(b);
     if (rc) return rc;
-    NEED(b->K == 1, OIVA_ERR_ARG, "OGIVE extracts one source: create the batch with K = 1");
-    NEED(update_mode >= OIVA_OGIVE_DEMIX && update_mode <= OIVA_OGIVE_SWITCHING, OIVA_ERR_ARG, "unknown update mode");
-    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
+    OIVA_NEED(b->K == 1, OIVA_ERR_ARG, "OGIVE extracts one source: create the batch with K = 1");
+    OIVA_NEED(update_mode >= OIVA_OGIVE_DEMIX && update_mode <= OIVA_OGIVE_SWITCHING, OIVA_ERR_ARG, "unknown update mode");
+    OIVA_NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
     DeviceGuard guard(b->device);
     const size_t nb = nbins(b), M = b->M, B = b->B;
     if (b->og_bufs.empty()) {
-        hipError_t e = hipSuccess;
-        auto alloc = [&](size_t bytes) -> void* {
-            void* ptr = nullptr;
-            if (e == hipSuccess) e = hipMalloc(&ptr, bytes);
-            if (ptr) b->og_bufs.push_back(ptr);
-            return ptr;
-        };
-        OgiveState& st = b->og.bin;
-        st.CxInv = (double2*)alloc(nb * M * M * sizeof(double2));
-        st.CxNorm = (double*)alloc(nb * sizeof(double));
-        st.A = (double2*)alloc(nb * M * sizeof(double2));
-        st.Delta = (double2*)alloc(nb * M * sizeof(double2));
-        st.Lambda = (double*)alloc(nb * sizeof(double));
-        st.DoA = (int*)alloc(nb * sizeof(int));
-        st.DoW = (int*)alloc(nb * sizeof(int));
-        st.Dnorm = (double*)alloc(nb * sizeof(double));
-        st.ctrl = (int*)alloc(4 * sizeof(int));                 // (reset by ogive_init_kernel; the batch keeps its own per problem)
-        st.maxdelta = (double*)alloc(2 * sizeof(double));
-        b->og.done = (int*)alloc(B * sizeof(int));
-        b->og.epochs = (int*)alloc(B * sizeof(int));
-        b->og.maxdelta = (double*)alloc(B * sizeof(double));
-        b->og.runmax = (unsigned long long*)alloc(B * sizeof(unsigned long long));
-        b->og.ticket = (unsigned*)alloc(B * sizeof(unsigned));
-        b->Opart = (double*)alloc((size_t)b->osplit * nb * (2 * M + 1) * sizeof(double));
-        if (e != hipSuccess) return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(e));
+        AllocChain alloc;
+        alloc.keep = &b->og_bufs;
+        alloc_ogive_state(b->og.bin, nb, M, alloc);      // (its ctrl / maxdelta: reset by ogive_init_kernel; the batch keeps its own per problem)
+        alloc(&b->og.done, B * sizeof(int));
+        alloc(&b->og.epochs, B * sizeof(int));
+        alloc(&b->og.maxdelta, B * sizeof(double));
+        alloc(&b->og.runmax, B * sizeof(unsigned long long));
+        alloc(&b->og.ticket, B * sizeof(unsigned));
+        alloc(&b->Opart, (size_t)b->osplit * nb * (2 * M + 1) * sizeof(double));
+        if (!alloc.ok()) return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
     }
-    HIP_TRY(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
     if (b->og_graph) {                   // captured for the previous update mode / model
-        HIP_TRY(hipGraphExecDestroy(b->og_graph));
+        OIVA_TRY_HIP(hipGraphExecDestroy(b->og_graph));
         b->og_graph = nullptr;
     }
     b->og.bin.Cx = b->Cx;
@@ -719,43 +605,43 @@ oiva_status oiva_batch_ogive_begin(oiva_batch* b, int update_mode, int model) {
     b->og_mode = update_mode;
     b->og_model = model;
     // Cx^-1, ||Cx||, a from w, the step selection (ive.py:100-102,136-139,173-180) on all B*F bins
-    HIP_TRY(launch_ogive_init(b->stream, b->og.bin, (int)nb, b->M, update_mode));
-    HIP_TRY(hipMemsetAsync(b->og.done, 0, B * sizeof(int), b->stream));
-    HIP_TRY(hipMemsetAsync(b->og.epochs, 0, B * sizeof(int), b->stream));
-    HIP_TRY(hipMemsetAsync(b->og.maxdelta, 0, B * sizeof(double), b->stream));
-    HIP_TRY(hipMemsetAsync(b->og.runmax, 0, B * sizeof(unsigned long long), b->stream));
-    HIP_TRY(hipMemsetAsync(b->og.ticket, 0, B * sizeof(unsigned), b->stream));
+    OIVA_TRY_HIP(launch_ogive_init(b->stream, b->og.bin, (int)nb, b->M, update_mode));
+    OIVA_TRY_HIP(hipMemsetAsync(b->og.done, 0, B * sizeof(int), b->stream));
+    OIVA_TRY_HIP(hipMemsetAsync(b->og.epochs, 0, B * sizeof(int), b->stream));
+    OIVA_TRY_HIP(hipMemsetAsync(b->og.maxdelta, 0, B * sizeof(double), b->stream));
+    OIVA_TRY_HIP(hipMemsetAsync(b->og.runmax, 0, B * sizeof(unsigned long long), b->stream));
+    OIVA_TRY_HIP(hipMemsetAsync(b->og.ticket, 0, B * sizeof(unsigned), b->stream));
     b->og_ready = true;
     return OIVA_OK;
 }
 
 oiva_status oiva_batch_ogive_iterate(oiva_batch* b, int first_epoch, int n, double step_size, double tol, int* epochs_run, int* converged,
                                  double* max_delta) {
-    NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
-    NEED(!b->ragged, OIVA_ERR_ARG, "OGIVE is not supported on a ragged batch");
+    OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(!b->ragged, OIVA_ERR_ARG, "OGIVE is not supported on a ragged batch");
     int rc = check_ready(b);
     if (rc) return rc;
-    NEED(b->og_ready, OIVA_ERR_STATE, "call oiva_batch_ogive_begin first");
-    NEED(n >= 0 && first_epoch >= 0, OIVA_ERR_ARG, "negative epoch count");
+    OIVA_NEED(b->og_ready, OIVA_ERR_STATE, "call oiva_batch_ogive_begin first");
+    OIVA_NEED(n >= 0 && first_epoch >= 0, OIVA_ERR_ARG, "negative epoch count");
     DeviceGuard guard(b->device);
     const int B = b->B;
     std::vector<int> before(B), after(B);
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(before.data(), b->og.epochs, B * sizeof(int), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(before.data(), b->og.epochs, B * sizeof(int), hipMemcpyDeviceToHost));
     const int amodel = b->og_model == OIVA_MODEL_LAPLACE ? kModelOgiveLaplace : OIVA_MODEL_GAUSS;
     const DenseArgs d = dense_args(b);
     // one epoch is five launches on the batch's stream (four when the switching criterion does not run)
     auto epochs = [&](int e0, int count) -> int {
         for (int e = e0; e < e0 + count; ++e) {
             if (b->og_mode == OIVA_OGIVE_SWITCHING && e % 10 == 0)
-                HIP_TRY(launch_batch_ogive_switch(b->stream, b->og, B, b->F, b->M));                     // ive.py:192-193
-            HIP_TRY(launch_batch_ogive_power(b->stream, b->X, b->What, b->Ppart, b->og.done, B, d.T, b->F, b->M, d.pw_nsplit,
+                OIVA_TRY_HIP(launch_batch_ogive_switch(b->stream, b->og, B, b->F, b->M));                     // ive.py:192-193
+            OIVA_TRY_HIP(launch_batch_ogive_power(b->stream, b->X, b->What, b->Ppart, b->og.done, B, d.T, b->F, b->M, d.pw_nsplit,
                                              d.tcp));                                                     // ive.py:196, :210/:213
-            HIP_TRY(launch_batch_ogive_activation(b->stream, b->Ppart, b->nb, b->R, d.r_stride, b->og.done, B, d.T, amodel,
+            OIVA_TRY_HIP(launch_batch_ogive_activation(b->stream, b->Ppart, b->nb, b->R, d.r_stride, b->og.done, B, d.T, amodel,
                                                   b->F));                                                 // ive.py:209-217
-            HIP_TRY(launch_batch_ogive_framesum(b->stream, b->X, b->What64, b->R, d.r_stride, b->og.done, b->Opart, B, d.T, b->F,
+            OIVA_TRY_HIP(launch_batch_ogive_framesum(b->stream, b->X, b->What64, b->R, d.r_stride, b->og.done, b->Opart, B, d.T, b->F,
                                                 b->M, b->osplit, b->otc));                                // ive.py:218-227
-            HIP_TRY(launch_batch_ogive_step(b->stream, b->og, b->Opart, b->osplit, B, b->F, b->M, step_size, tol));   // ive.py:228-246
+            OIVA_TRY_HIP(launch_batch_ogive_step(b->stream, b->og, b->Opart, b->osplit, B, b->F, b->M, step_size, tol));   // ive.py:228-246
         }
         return OIVA_OK;
     };
@@ -763,81 +649,71 @@ oiva_status oiva_batch_ogive_iterate(oiva_batch* b, int first_epoch, int n, doub
         // n epochs as one linear graph on the batch's stream, cached while (n, phase, step size, tol) stay the same
         const int phase = first_epoch % 10;
         if (!b->og_graph || b->og_graph_n != n || b->og_graph_phase != phase || b->og_graph_mu != step_size || b->og_graph_tol != tol) {
-            if (b->og_graph) HIP_TRY(hipGraphExecDestroy(b->og_graph));
+            if (b->og_graph) OIVA_TRY_HIP(hipGraphExecDestroy(b->og_graph));
             b->og_graph = nullptr;
-            hipGraph_t graph = nullptr;
-            HIP_TRY(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
-            rc = epochs(phase, n);
-            hipError_t e = hipStreamEndCapture(b->stream, &graph);
-            if (rc) {
-                if (graph) (void)hipGraphDestroy(graph);
-                return rc;
-            }
-            HIP_TRY(e);
-            e = hipGraphInstantiate(&b->og_graph, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            HIP_TRY(e);
+            rc = capture_graph(b->stream, [&] { return epochs(phase, n); }, &b->og_graph, false);
+            if (rc) return rc;
             b->og_graph_n = n;
             b->og_graph_phase = phase;
             b->og_graph_mu = step_size;
             b->og_graph_tol = tol;
         }
-        HIP_TRY(hipGraphLaunch(b->og_graph, b->stream));
+        OIVA_TRY_HIP(hipGraphLaunch(b->og_graph, b->stream));
     } else if ((rc = epochs(first_epoch, n))) {
         return rc;
     }
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(after.data(), b->og.epochs, B * sizeof(int), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(after.data(), b->og.epochs, B * sizeof(int), hipMemcpyDeviceToHost));
     if (epochs_run)
         for (int p = 0; p < B; ++p) epochs_run[p] = after[p] - before[p];
-    if (converged) HIP_TRY(hipMemcpy(converged, b->og.done, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (max_delta) HIP_TRY(hipMemcpy(max_delta, b->og.maxdelta, B * sizeof(double), hipMemcpyDeviceToHost));
+    if (converged) OIVA_TRY_HIP(hipMemcpy(converged, b->og.done, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (max_delta) OIVA_TRY_HIP(hipMemcpy(max_delta, b->og.maxdelta, B * sizeof(double), hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 
 // ---- batched PCA front end (reference auxiva_pca.py:63-92, one problem per batch entry) -------------------------------------
 oiva_status oiva_batch_set_w_pca(oiva_batch* b, double* evals_host) {
-    NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
-    NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
+    OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
     DeviceGuard guard(b->device);
     // auxiva_pca.py:75-81 per bin, the device eigensolver on B*F bins; the eigenvalues pass through Vpart (free between the
     // covariance and the first iteration, at least B*F*M*M doubles)
     double* evals = evals_host ? b->Vpart : nullptr;
-    HIP_TRY(launch_pca_subspace(b->stream, b->Cx, b->What, b->What64, evals, (int)nbins(b), b->M, b->K, false));
+    OIVA_TRY_HIP(launch_pca_subspace(b->stream, b->Cx, b->What, b->What64, evals, (int)nbins(b), b->M, b->K, false));
     b->have_w = true;
     if (evals_host) {
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        HIP_TRY(hipMemcpy(evals_host, evals, nbins(b) * b->M * sizeof(double), hipMemcpyDeviceToHost));
+        OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+        OIVA_TRY_HIP(hipMemcpy(evals_host, evals, nbins(b) * b->M * sizeof(double), hipMemcpyDeviceToHost));
     }
-    if (b->K < b->M) HIP_TRY(launch_update(b->stream, update_args(b, true)));   // J from the orthogonality constraint
+    if (b->K < b->M) OIVA_TRY_HIP(launch_update(b->stream, update_args(b, true)));   // J from the orthogonality constraint
     return OIVA_OK;
 }
 
 oiva_status oiva_batch_project_dev(oiva_batch* b, void** Xr_dev) {
-    NEED(Xr_dev != nullptr, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(Xr_dev != nullptr, OIVA_ERR_ARG, "null argument");
     *Xr_dev = nullptr;
     const int rc = check_ready(b);
     if (rc) return rc;
     DeviceGuard guard(b->device);
-    if (!b->Xr) HIP_TRY(hipMalloc((void**)&b->Xr, b->frames_total * b->F * b->K * sizeof(float2)));
+    if (!b->Xr) OIVA_TRY_HIP(dev_malloc(&b->Xr, b->frames_total * b->F * b->K * sizeof(float2)));
     // auxiva_pca.py:79-81 for every problem in one launch, from the problem table
-    HIP_TRY(launch_pca_project(b->stream, b->X, b->What, b->Xr, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit));
-    HIP_TRY(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(launch_pca_project(b->stream, b->X, b->What, b->Xr, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit));
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
     *Xr_dev = b->Xr;
     return OIVA_OK;
 }
 
 oiva_status oiva_batch_compose_w(oiva_batch* outer, const oiva_batch* inner) {
-    NEED(outer != nullptr && inner != nullptr, OIVA_ERR_ARG, "null batch");
-    NEED(outer != inner, OIVA_ERR_ARG, "the reduced batch must be another batch");
-    NEED(inner->B == outer->B && inner->F == outer->F, OIVA_ERR_ARG, "the two batches differ in B or F");
-    NEED(inner->M == inner->K && inner->K == outer->K, OIVA_ERR_ARG,
-         "the reduced batch must be determined on the K channels of the projection");
-    NEED(inner->device == outer->device, OIVA_ERR_ARG, "the two batches live on different devices");
-    NEED(outer->have_w && inner->have_w, OIVA_ERR_STATE, "demixing matrices not set");
+    OIVA_NEED(outer != nullptr && inner != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(outer != inner, OIVA_ERR_ARG, "the reduced batch must be another batch");
+    OIVA_NEED(inner->B == outer->B && inner->F == outer->F, OIVA_ERR_ARG, "the two batches differ in B or F");
+    OIVA_NEED(inner->M == inner->K && inner->K == outer->K, OIVA_ERR_ARG,
+              "the reduced batch must be determined on the K channels of the projection");
+    OIVA_NEED(inner->device == outer->device, OIVA_ERR_ARG, "the two batches live on different devices");
+    OIVA_NEED(outer->have_w && inner->have_w, OIVA_ERR_STATE, "demixing matrices not set");
     DeviceGuard guard(outer->device);
-    HIP_TRY(hipStreamSynchronize(inner->stream));
-    HIP_TRY(launch_pca_compose(outer->stream, outer->What, outer->What64, inner->What64, (long long)nbins(outer), outer->M, outer->K));
+    OIVA_TRY_HIP(hipStreamSynchronize(inner->stream));
+    OIVA_TRY_HIP(launch_pca_compose(outer->stream, outer->What, outer->What64, inner->What64, (long long)nbins(outer), outer->M, outer->K));
     return OIVA_OK;
 }
 

@@ -14,27 +14,12 @@
 #include <string>
 #include <vector>
 
+#include "host_util.h"
 #include "oiva_internal.h"
 
 using namespace oiva;
 
 namespace {
-
-int bfail(int code, const std::string& msg) { return oiva::fail_with(code, msg); }
-#define B_HIP(expr)                                                                                       \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return bfail(OIVA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define B_FFT(expr)                                                                                  \
-    do {                                                                                             \
-        hipfftResult r_ = (expr);                                                                    \
-        if (r_ != HIPFFT_SUCCESS) return bfail(OIVA_ERR_HIP, std::string(#expr) + ": hipfft error " + std::to_string((int)r_)); \
-    } while (0)
-#define B_NEED(cond, code, msg)               \
-    do {                                      \
-        if (!(cond)) return bfail(code, msg); \
-    } while (0)
 
 constexpr int kMaxChannels = 8;        // as the batched solvers
 constexpr int kPhases = 8;             // upload, framing, R2C, to (t, F, M) | from (t, F, K), C2R, overlap-add, download
@@ -66,31 +51,31 @@ extern "C" {
 
 oiva_status oiva_bstft_create(oiva_bstft** out, int device, int B, const int* n_samples, int M, int frame, int hop, const float* win_a,
                               const float* win_s, void* stream) {
-    B_NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
+    OIVA_NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
     *out = nullptr;
-    B_NEED(n_samples != nullptr, OIVA_ERR_ARG, "null n_samples");
-    B_NEED(B >= 1, OIVA_ERR_ARG, "B must be >= 1");
-    B_NEED(M >= 1 && M <= kMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
-    B_NEED(frame >= 2 && frame % 2 == 0, OIVA_ERR_ARG, "frame must be even and >= 2");
-    B_NEED(hop >= 1 && hop <= frame, OIVA_ERR_ARG, "hop must be in 1..frame");
+    OIVA_NEED(n_samples != nullptr, OIVA_ERR_ARG, "null n_samples");
+    OIVA_NEED(B >= 1, OIVA_ERR_ARG, "B must be >= 1");
+    OIVA_NEED(M >= 1 && M <= kMaxChannels, OIVA_ERR_ARG, "the batched path runs on 1..8 channels");
+    OIVA_NEED(frame >= 2 && frame % 2 == 0, OIVA_ERR_ARG, "frame must be even and >= 2");
+    OIVA_NEED(hop >= 1 && hop <= frame, OIVA_ERR_ARG, "hop must be in 1..frame");
     const int F = frame / 2 + 1;
     const double lim31 = 2147483648., lim63 = 9223372036854775808.;
     double samples = 0., frames = 0.;
     for (int b = 0; b < B; ++b) {
-        B_NEED(n_samples[b] >= hop, OIVA_ERR_ARG, "room " + std::to_string(b) + " is shorter than one hop");
+        OIVA_NEED(n_samples[b] >= hop, OIVA_ERR_ARG, "room " + std::to_string(b) + " is shorter than one hop");
         const double Tb = n_samples[b] / hop;
-        B_NEED((double)n_samples[b] * M < lim31 && Tb * M * (frame + 2) < lim31, OIVA_ERR_ARG,
-               "room " + std::to_string(b) + " is too large (2^31 elements per room)");
+        OIVA_NEED((double)n_samples[b] * M < lim31 && Tb * M * (frame + 2) < lim31, OIVA_ERR_ARG,
+                  "room " + std::to_string(b) + " is too large (2^31 elements per room)");
         samples += n_samples[b];
         frames += Tb;
     }
     // the largest buffer is X / spec: frames * M * F complex64; hipFFT counts its transforms in an int
-    B_NEED(frames * M * F * 8. < lim63 && samples * M * 4. < lim63 && frames * M < lim31 && frames < lim31, OIVA_ERR_ARG,
-           "batch too large");
+    OIVA_NEED(frames * M * F * 8. < lim63 && samples * M * 4. < lim63 && frames * M < lim31 && frames < lim31, OIVA_ERR_ARG,
+              "batch too large");
     int ndev = 0;
-    B_HIP(hipGetDeviceCount(&ndev));
-    B_NEED(device >= 0 && device < ndev, OIVA_ERR_ARG, "no such device");
-    B_HIP(hipSetDevice(device));
+    OIVA_TRY_HIP(hipGetDeviceCount(&ndev));
+    OIVA_NEED(device >= 0 && device < ndev, OIVA_ERR_ARG, "no such device");
+    DeviceGuard guard(device);
     oiva_bstft* p = new oiva_bstft();
     p->device = device;
     p->B = B, p->M = M, p->L = frame, p->hop = hop, p->F = F;
@@ -104,36 +89,33 @@ oiva_status oiva_bstft_create(oiva_bstft** out, int device, int B, const int* n_
         p->samples_total += r.n;
         p->frames_total += r.T;
     }
-    hipError_t e = hipSuccess;
+    AllocChain alloc;
     if (stream) {
         p->stream = static_cast<hipStream_t>(stream);
     } else {
-        e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-        p->own_stream = e == hipSuccess;
+        alloc.err = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+        p->own_stream = alloc.ok();
     }
     for (hipEvent_t& ev : p->ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    auto alloc = [&](void** ptr, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(ptr, bytes);
-    };
+        if (alloc.ok()) alloc.err = hipEventCreate(&ev);
     const size_t rows = (size_t)p->frames_total * M;
-    alloc((void**)&p->x, (size_t)std::max(p->samples_total, p->frames_total * hop) * M * sizeof(float));
-    alloc((void**)&p->frames, rows * frame * sizeof(float));
-    alloc((void**)&p->spec, rows * F * sizeof(float2));
-    alloc((void**)&p->X, rows * F * sizeof(float2));
-    alloc((void**)&p->rooms_dev, (size_t)B * sizeof(BstftRoom));
-    if (e == hipSuccess) e = hipMemcpy(p->rooms_dev, p->rooms.data(), (size_t)B * sizeof(BstftRoom), hipMemcpyHostToDevice);
+    alloc(&p->x, (size_t)std::max(p->samples_total, p->frames_total * hop) * M * sizeof(float));
+    alloc(&p->frames, rows * frame * sizeof(float));
+    alloc(&p->spec, rows * F * sizeof(float2));
+    alloc(&p->X, rows * F * sizeof(float2));
+    alloc(&p->rooms_dev, (size_t)B * sizeof(BstftRoom));
+    if (alloc.ok()) alloc.err = hipMemcpy(p->rooms_dev, p->rooms.data(), (size_t)B * sizeof(BstftRoom), hipMemcpyHostToDevice);
     if (win_a) {
-        alloc((void**)&p->win_a, frame * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(p->win_a, win_a, frame * sizeof(float), hipMemcpyHostToDevice);
+        alloc(&p->win_a, frame * sizeof(float));
+        if (alloc.ok()) alloc.err = hipMemcpy(p->win_a, win_a, frame * sizeof(float), hipMemcpyHostToDevice);
     }
     if (win_s) {
-        alloc((void**)&p->win_s, frame * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(p->win_s, win_s, frame * sizeof(float), hipMemcpyHostToDevice);
+        alloc(&p->win_s, frame * sizeof(float));
+        if (alloc.ok()) alloc.err = hipMemcpy(p->win_s, win_s, frame * sizeof(float), hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) {
+    if (!alloc.ok()) {
         oiva_bstft_destroy(p);
-        return bfail(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(e));
+        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
     }
     *out = p;
     return OIVA_OK;
@@ -141,7 +123,7 @@ oiva_status oiva_bstft_create(oiva_bstft** out, int device, int B, const int* n_
 
 oiva_status oiva_bstft_destroy(oiva_bstft* p) {
     if (!p) return OIVA_OK;
-    (void)hipSetDevice(p->device);
+    DeviceGuard guard(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     if (p->have_fwd) (void)hipfftDestroy(p->fwd);
     if (p->have_inv) (void)hipfftDestroy(p->inv);
@@ -156,7 +138,7 @@ oiva_status oiva_bstft_destroy(oiva_bstft* p) {
 }
 
 oiva_status oiva_bstft_shape(oiva_bstft* p, int* frames, int* n_freq) {
-    B_NEED(p, OIVA_ERR_ARG, "null handle");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null handle");
     if (frames)
         for (int b = 0; b < p->B; ++b) frames[b] = p->rooms[b].T;
     if (n_freq) *n_freq = p->F;
@@ -164,75 +146,75 @@ oiva_status oiva_bstft_shape(oiva_bstft* p, int* frames, int* n_freq) {
 }
 
 oiva_status oiva_bstft_analysis(oiva_bstft* p, const float* x_host, void** X_dev) {
-    B_NEED(p && x_host && X_dev, OIVA_ERR_ARG, "null argument");
-    B_HIP(hipSetDevice(p->device));
+    OIVA_NEED(p && x_host && X_dev, OIVA_ERR_ARG, "null argument");
+    DeviceGuard guard(p->device);
     const int M = p->M, L = p->L, F = p->F;
     if (!p->have_fwd) {
         int n[1] = {L};
-        B_FFT(hipfftPlanMany(&p->fwd, 1, n, nullptr, 1, L, nullptr, 1, F, HIPFFT_R2C, (int)(p->frames_total * M)));
-        B_FFT(hipfftSetStream(p->fwd, p->stream));
+        OIVA_TRY_FFT(hipfftPlanMany(&p->fwd, 1, n, nullptr, 1, L, nullptr, 1, F, HIPFFT_R2C, (int)(p->frames_total * M)));
+        OIVA_TRY_FFT(hipfftSetStream(p->fwd, p->stream));
         p->have_fwd = true;
     }
-    B_HIP(hipEventRecord(p->ev[0], p->stream));
-    B_HIP(hipMemcpyAsync(p->x, x_host, (size_t)p->samples_total * M * sizeof(float), hipMemcpyHostToDevice, p->stream));
-    B_HIP(hipEventRecord(p->ev[1], p->stream));
-    B_HIP(launch_bstft_frame(p->stream, p->x, p->win_a, p->frames, p->rooms_dev, p->B, p->frames_total, M, L, p->hop));
-    B_HIP(hipEventRecord(p->ev[2], p->stream));
-    B_FFT(hipfftExecR2C(p->fwd, p->frames, reinterpret_cast<hipfftComplex*>(p->spec)));
-    B_HIP(hipEventRecord(p->ev[3], p->stream));
-    B_HIP(launch_bstft_to_tfc(p->stream, p->spec, p->X, p->frames_total, F, M));
-    B_HIP(hipEventRecord(p->ev[4], p->stream));
-    B_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[0], p->stream));
+    OIVA_TRY_HIP(hipMemcpyAsync(p->x, x_host, (size_t)p->samples_total * M * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[1], p->stream));
+    OIVA_TRY_HIP(launch_bstft_frame(p->stream, p->x, p->win_a, p->frames, p->rooms_dev, p->B, p->frames_total, M, L, p->hop));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[2], p->stream));
+    OIVA_TRY_FFT(hipfftExecR2C(p->fwd, p->frames, reinterpret_cast<hipfftComplex*>(p->spec)));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[3], p->stream));
+    OIVA_TRY_HIP(launch_bstft_to_tfc(p->stream, p->spec, p->X, p->frames_total, F, M));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[4], p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     p->timed_a = true;
     *X_dev = p->X;
     return OIVA_OK;
 }
 
 oiva_status oiva_bstft_synthesis_dev(oiva_bstft* p, const void* Y_dev, int K, float* y_host) {
-    B_NEED(p && Y_dev && y_host, OIVA_ERR_ARG, "null argument");
-    B_NEED(K >= 1 && K <= p->M, OIVA_ERR_ARG, "synthesis takes 1..M channels");
-    B_HIP(hipSetDevice(p->device));
+    OIVA_NEED(p && Y_dev && y_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(K >= 1 && K <= p->M, OIVA_ERR_ARG, "synthesis takes 1..M channels");
+    DeviceGuard guard(p->device);
     const int L = p->L, F = p->F;
     // one inverse plan per channel count (the solver returns fewer channels than the analysis had)
     if (!p->have_inv || p->inv_chan != K) {
-        if (p->have_inv) B_FFT(hipfftDestroy(p->inv));
+        if (p->have_inv) OIVA_TRY_FFT(hipfftDestroy(p->inv));
         p->have_inv = false;
         int n[1] = {L};
-        B_FFT(hipfftPlanMany(&p->inv, 1, n, nullptr, 1, F, nullptr, 1, L, HIPFFT_C2R, (int)(p->frames_total * K)));
-        B_FFT(hipfftSetStream(p->inv, p->stream));
+        OIVA_TRY_FFT(hipfftPlanMany(&p->inv, 1, n, nullptr, 1, F, nullptr, 1, L, HIPFFT_C2R, (int)(p->frames_total * K)));
+        OIVA_TRY_FFT(hipfftSetStream(p->inv, p->stream));
         p->have_inv = true;
         p->inv_chan = K;
     }
     const long long n_out = p->frames_total * p->hop;
-    B_HIP(hipEventRecord(p->ev[5], p->stream));
-    B_HIP(launch_bstft_from_tfc(p->stream, static_cast<const float2*>(Y_dev), p->spec, p->frames_total, F, K));
-    B_HIP(hipEventRecord(p->ev[6], p->stream));
-    B_FFT(hipfftExecC2R(p->inv, reinterpret_cast<hipfftComplex*>(p->spec), p->frames));
-    B_HIP(hipEventRecord(p->ev[7], p->stream));
-    B_HIP(launch_bstft_overlap_add(p->stream, p->frames, p->win_s, p->x, p->rooms_dev, p->B, n_out, K, L, p->hop));
-    B_HIP(hipEventRecord(p->ev[8], p->stream));
-    B_HIP(hipMemcpyAsync(y_host, p->x, (size_t)n_out * K * sizeof(float), hipMemcpyDeviceToHost, p->stream));
-    B_HIP(hipEventRecord(p->ev[9], p->stream));
-    B_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[5], p->stream));
+    OIVA_TRY_HIP(launch_bstft_from_tfc(p->stream, static_cast<const float2*>(Y_dev), p->spec, p->frames_total, F, K));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[6], p->stream));
+    OIVA_TRY_FFT(hipfftExecC2R(p->inv, reinterpret_cast<hipfftComplex*>(p->spec), p->frames));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[7], p->stream));
+    OIVA_TRY_HIP(launch_bstft_overlap_add(p->stream, p->frames, p->win_s, p->x, p->rooms_dev, p->B, n_out, K, L, p->hop));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[8], p->stream));
+    OIVA_TRY_HIP(hipMemcpyAsync(y_host, p->x, (size_t)n_out * K * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[9], p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     p->timed_s = true;
     return OIVA_OK;
 }
 
 oiva_status oiva_bstft_phase_ms(oiva_bstft* p, float* ms) {
-    B_NEED(p && ms, OIVA_ERR_ARG, "null argument");
-    B_HIP(hipSetDevice(p->device));
+    OIVA_NEED(p && ms, OIVA_ERR_ARG, "null argument");
+    DeviceGuard guard(p->device);
     for (int i = 0; i < kPhases; ++i) ms[i] = 0.f;
     if (p->timed_a)
-        for (int i = 0; i < 4; ++i) B_HIP(hipEventElapsedTime(&ms[i], p->ev[i], p->ev[i + 1]));
+        for (int i = 0; i < 4; ++i) OIVA_TRY_HIP(hipEventElapsedTime(&ms[i], p->ev[i], p->ev[i + 1]));
     if (p->timed_s)
-        for (int i = 0; i < 4; ++i) B_HIP(hipEventElapsedTime(&ms[4 + i], p->ev[5 + i], p->ev[6 + i]));
+        for (int i = 0; i < 4; ++i) OIVA_TRY_HIP(hipEventElapsedTime(&ms[4 + i], p->ev[5 + i], p->ev[6 + i]));
     return OIVA_OK;
 }
 
 oiva_status oiva_device_to_host(void* host, const void* dev, long long bytes) {
-    B_NEED(host && dev, OIVA_ERR_ARG, "null argument");
-    B_NEED(bytes >= 0, OIVA_ERR_ARG, "negative size");
-    B_HIP(hipMemcpy(host, dev, (size_t)bytes, hipMemcpyDeviceToHost));
+    OIVA_NEED(host && dev, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(bytes >= 0, OIVA_ERR_ARG, "negative size");
+    OIVA_TRY_HIP(hipMemcpy(host, dev, (size_t)bytes, hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 

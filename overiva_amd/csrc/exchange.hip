@@ -15,6 +15,7 @@
 // Result layout = rank-major concatenation of the parts = what all_gather_into_tensor produces, so the consumers do
 // not know which transport ran.  The host side (overiva_amd/exchange.py) checks the transport against
 // torch.distributed's all-gather with host-side time-outs before it is used, and falls back to the collective.
+#include "host_util.h"
 #include "oiva_internal.h"
 
 #include <algorithm>
@@ -80,24 +81,15 @@ int oiva::xchg_peers(oiva_xchg* x, char** peers, int* rank, int* world, size_t* 
     return 0;
 }
 
-#define XNEED(cond, code, msg) \
-    do {                       \
-        if (!(cond)) return fail_with(code, msg); \
-    } while (0)
-#define XHIP(expr)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return fail_with(OIVA_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
 extern "C" {
 
 int oiva_xchg_create(oiva_xchg** out, int device, int rank, int world, long long part_bytes) {
-    XNEED(out, OIVA_ERR_ARG, "null output");
-    XNEED(world >= 1 && world <= OIVA_XCHG_MAX_RANKS && rank >= 0 && rank < world && part_bytes > 0 && part_bytes % 4 == 0,
-          OIVA_ERR_ARG, "bad rank / world / part size (a whole number of floats)");
+    OIVA_NEED(out, OIVA_ERR_ARG, "null output");
+    OIVA_NEED(world >= 1 && world <= OIVA_XCHG_MAX_RANKS && rank >= 0 && rank < world && part_bytes > 0 && part_bytes % 4 == 0,
+              OIVA_ERR_ARG, "bad rank / world / part size (a whole number of floats)");
     static_assert(sizeof(hipIpcMemHandle_t) == OIVA_XCHG_HANDLE_BYTES, "handle size");
-    XHIP(hipSetDevice(device));
+    DeviceGuard guard(device);
+    OIVA_TRY_HIP(hipSetDevice(device));      // (the validation of `device`; the guard puts the caller's back)
     auto* x = new oiva_xchg;
     x->device = device;
     x->rank = rank;
@@ -106,7 +98,7 @@ int oiva_xchg_create(oiva_xchg** out, int device, int rank, int world, long long
     const size_t total = buffers_bytes(world, x->slot_bytes) + 2 * kCounterStride;
     hipError_t e = hipExtMallocWithFlags((void**)&x->block, total, hipDeviceMallocFinegrained);
     if (e == hipSuccess) e = hipMemset(x->block, 0, total);
-    if (e == hipSuccess) e = hipMalloc((void**)&x->ticket, sizeof(unsigned));
+    if (e == hipSuccess) e = dev_malloc(&x->ticket, sizeof(unsigned));
     if (e == hipSuccess) e = hipMemset(x->ticket, 0, sizeof(unsigned));
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
@@ -121,24 +113,24 @@ int oiva_xchg_create(oiva_xchg** out, int device, int rank, int world, long long
 }
 
 int oiva_xchg_export(oiva_xchg* x, void* handle) {
-    XNEED(x && handle, OIVA_ERR_ARG, "null argument");
-    XHIP(hipSetDevice(x->device));
+    OIVA_NEED(x && handle, OIVA_ERR_ARG, "null argument");
+    DeviceGuard guard(x->device);
     hipIpcMemHandle_t h;
-    XHIP(hipIpcGetMemHandle(&h, x->block));
+    OIVA_TRY_HIP(hipIpcGetMemHandle(&h, x->block));
     std::memcpy(handle, &h, sizeof(h));
     return OIVA_OK;
 }
 
 int oiva_xchg_connect(oiva_xchg* x, const void* handles) {
-    XNEED(x && handles, OIVA_ERR_ARG, "null argument");
-    XNEED(!x->connected, OIVA_ERR_STATE, "already connected");
-    XHIP(hipSetDevice(x->device));
+    OIVA_NEED(x && handles, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(!x->connected, OIVA_ERR_STATE, "already connected");
+    DeviceGuard guard(x->device);
     for (int r = 0; r < x->world; ++r) {
         if (r == x->rank) continue;
         hipIpcMemHandle_t h;
         std::memcpy(&h, static_cast<const char*>(handles) + (size_t)r * sizeof(h), sizeof(h));
         void* p = nullptr;
-        XHIP(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
+        OIVA_TRY_HIP(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
         x->peer[r] = static_cast<char*>(p);
         x->opened[r] = true;
     }
@@ -147,17 +139,17 @@ int oiva_xchg_connect(oiva_xchg* x, const void* handles) {
 }
 
 int oiva_xchg_gathered(oiva_xchg* x, int epoch, void** gathered) {
-    XNEED(x && gathered && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(x && gathered && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
     *gathered = x->block + (size_t)(epoch & 1) * x->world * x->slot_bytes;
     return OIVA_OK;
 }
 
 int oiva_xchg_push(oiva_xchg* x, void* stream, const void* part_dev, long long part_bytes, int epoch) {
-    XNEED(x && part_dev && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
-    XNEED(x->connected || x->world == 1, OIVA_ERR_STATE, "exchange not connected");
-    XNEED((size_t)part_bytes == x->slot_bytes && ((uintptr_t)part_dev & 15) == 0, OIVA_ERR_ARG,
-          "part must be 16-byte aligned and of the size given at creation");
-    XHIP(hipSetDevice(x->device));
+    OIVA_NEED(x && part_dev && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(x->connected || x->world == 1, OIVA_ERR_STATE, "exchange not connected");
+    OIVA_NEED((size_t)part_bytes == x->slot_bytes && ((uintptr_t)part_dev & 15) == 0, OIVA_ERR_ARG,
+              "part must be 16-byte aligned and of the size given at creation");
+    DeviceGuard guard(x->device);
     PushArgs a;
     for (int r = 0; r < OIVA_XCHG_MAX_RANKS; ++r) a.peer[r] = r < x->world ? x->peer[r] : nullptr;
     const bool vec = part_bytes % 16 == 0;
@@ -172,29 +164,29 @@ int oiva_xchg_push(oiva_xchg* x, void* stream, const void* part_dev, long long p
     else
         hipLaunchKernelGGL(push_kernel<float>, grid, dim3(kBlock), 0, st, a, static_cast<const float*>(part_dev), x->ticket, x->rank,
                            x->world, slot4, n, epoch & 1);
-    XHIP(hipGetLastError());
+    OIVA_TRY_HIP(hipGetLastError());
     return OIVA_OK;
 }
 
 static unsigned expected_count(const oiva_xchg* x, int epoch) { return (unsigned)((epoch + 1) >> 1) * (unsigned)x->world; }
 
 int oiva_xchg_wait(oiva_xchg* x, void* stream, int epoch) {
-    XNEED(x && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
-    XHIP(hipSetDevice(x->device));
+    OIVA_NEED(x && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
+    DeviceGuard guard(x->device);
     unsigned* counter = reinterpret_cast<unsigned*>(x->block + buffers_bytes(x->world, x->slot_bytes) + (epoch & 1) * kCounterStride);
-    XHIP(hipStreamWaitValue32(static_cast<hipStream_t>(stream), counter, expected_count(x, epoch), hipStreamWaitValueGte, 0xffffffffu));
+    OIVA_TRY_HIP(hipStreamWaitValue32(static_cast<hipStream_t>(stream), counter, expected_count(x, epoch), hipStreamWaitValueGte, 0xffffffffu));
     return OIVA_OK;
 }
 
 int oiva_xchg_poll(oiva_xchg* x, int epoch, int timeout_ms, int* arrived) {
-    XNEED(x && arrived && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
-    XHIP(hipSetDevice(x->device));
+    OIVA_NEED(x && arrived && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
+    DeviceGuard guard(x->device);
     const unsigned* counter =
         reinterpret_cast<const unsigned*>(x->block + buffers_bytes(x->world, x->slot_bytes) + (epoch & 1) * kCounterStride);
     *arrived = 0;
     for (int waited = 0;; ++waited) {
         unsigned v = 0;
-        XHIP(hipMemcpy(&v, counter, sizeof(v), hipMemcpyDeviceToHost));
+        OIVA_TRY_HIP(hipMemcpy(&v, counter, sizeof(v), hipMemcpyDeviceToHost));
         if (v >= expected_count(x, epoch)) {
             *arrived = 1;
             return OIVA_OK;
@@ -206,24 +198,24 @@ int oiva_xchg_poll(oiva_xchg* x, int epoch, int timeout_ms, int* arrived) {
 }
 
 int oiva_xchg_force(oiva_xchg* x, int epoch) {
-    XNEED(x && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
-    XHIP(hipSetDevice(x->device));
+    OIVA_NEED(x && epoch >= 1, OIVA_ERR_ARG, "bad arguments");
+    DeviceGuard guard(x->device);
     // a host store of the value the stream waits for, through a stream of its own (the waiting stream is blocked, and
     // nothing here may synchronise with it)
     unsigned* counter = reinterpret_cast<unsigned*>(x->block + buffers_bytes(x->world, x->slot_bytes) + (epoch & 1) * kCounterStride);
     const unsigned v = expected_count(x, epoch);
     hipStream_t s = nullptr;
-    XHIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    OIVA_TRY_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     hipError_t e = hipMemcpyAsync(counter, &v, sizeof(v), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipStreamDestroy(s);
-    XHIP(e);
+    OIVA_TRY_HIP(e);
     return OIVA_OK;
 }
 
 int oiva_xchg_destroy(oiva_xchg* x) {
     if (!x) return OIVA_OK;
-    (void)hipSetDevice(x->device);
+    DeviceGuard guard(x->device);
     (void)hipDeviceSynchronize();
     for (int r = 0; r < x->world; ++r)
         if (x->opened[r]) (void)hipIpcCloseMemHandle(x->peer[r]);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "host_io.h"
+#include "host_util.h"
 #include "oiva_internal.h"
 #include "resident.h"
 
@@ -19,40 +20,20 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-}  // namespace
-
-int oiva::fail_with(int code, const std::string& msg) { return fail(code, msg); }
-oiva::KernelTimer& oiva::kernel_timer() {
-    static thread_local KernelTimer t;
-    return t;
-}
-
-namespace {
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(OIVA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-#define NEED(cond, code, msg) \
-    do {                      \
-        if (!(cond)) return fail(code, msg); \
-    } while (0)
-
-int round_up(int a, int b) { return (a + b - 1) / b * b; }
-int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
 constexpr int kGraphBatch = 8;       // iterations of the graph captured ahead of time (oiva_plan_use_graph)
 constexpr int kGraphMaxIters = 32;   // longest graph captured on demand: an iterate(n) call is ceil(n / 32) replays
 constexpr int kGraphCache = 6;       // captured lengths kept per plan
 
 }  // namespace
+
+int oiva::fail_with(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
+oiva::KernelTimer& oiva::kernel_timer() {
+    static thread_local KernelTimer t;
+    return t;
+}
 
 // ---- large device buffers (X, Y, staging) come from a process-wide pool -------------------------------------------
 // The drop-in call creates and destroys a plan per call; hipMalloc + hipFree of the 524 MB of X and the 131 MB of Y at the
@@ -95,20 +76,17 @@ void pool_release_all() {
     bp.held.clear();
     bp.total = 0;
 }
+}  // namespace
 // hipMalloc of the library: the pool's idle buffers are memory the caller thinks is free, so before an allocation fails for
 // want of memory they are handed back and the allocation is tried once more
-hipError_t dev_malloc(void** out, size_t bytes) {
+hipError_t oiva::dev_malloc(void** out, size_t bytes) {
     hipError_t e = hipMalloc(out, bytes);
     if (e != hipErrorOutOfMemory) return e;
     (void)hipGetLastError();
     pool_release_all();
     return hipMalloc(out, bytes);
 }
-template <class P>
-hipError_t dev_malloc(P** out, size_t bytes) {
-    return dev_malloc(reinterpret_cast<void**>(out), bytes);
-}
-hipError_t big_alloc(int dev, void** out, size_t bytes) {
+hipError_t oiva::big_alloc(int dev, void** out, size_t bytes) {
     if (bytes >= kPoolMinBytes) {
         BigPool& bp = big_pool();
         std::lock_guard<std::mutex> g(bp.m);
@@ -122,7 +100,7 @@ hipError_t big_alloc(int dev, void** out, size_t bytes) {
     }
     return dev_malloc(out, bytes);
 }
-void big_free(int dev, void* ptr, size_t bytes) {
+void oiva::big_free(int dev, void* ptr, size_t bytes) {
     if (!ptr) return;
     if (bytes >= kPoolMinBytes && bytes <= pool_cap_bytes()) {
         BigPool& bp = big_pool();
@@ -138,7 +116,6 @@ void big_free(int dev, void* ptr, size_t bytes) {
     }
     (void)hipFree(ptr);
 }
-}  // namespace
 
 struct oiva_plan {
     int device = 0;
@@ -243,7 +220,7 @@ struct oiva_plan {
     float2* ck_what = nullptr;                  // oiva_plan_save_w: a copy of W_hat (and of its complex128 form) on the device
     double2* ck_what64 = nullptr;
     bool ck_valid = false, ck_what64_valid = false;
-    std::vector<std::pair<int, hipGraphExec_t>> graphs;   // (iterations, executable graph), most recently used last
+    GraphCache graphs{kGraphCache};             // by iterations per replay
     hipEvent_t ev[2] = {};
 };
 
@@ -419,13 +396,7 @@ void choose_stats_geom(oiva_plan* p) {
         p->stg = g;
         return;
     }
-    g.nbg = ceil_div(p->F, kBinsPerWave);
-    g.kc = 2;
-    const int nz = ceil_div(p->K, g.kc);
-    const int nsplit = std::min(16, pick_splits(p->n_cu * 4, g.nbg * nz, p->T, 128));
-    g.tc = round_up(ceil_div(p->T, nsplit), 16);
-    g.nsplit = ceil_div(p->T, g.tc);
-    p->stg = g;
+    p->stg = stats_geom(p->T, p->F, p->K, p->n_cu);
 }
 
 void choose_pow_geom(oiva_plan* p, int nsplit_req) {
@@ -474,13 +445,10 @@ void choose_pow_geom(oiva_plan* p, int nsplit_req) {
 }
 
 int drop_graph(oiva_plan* p) {
-    while (!p->graphs.empty()) {
-        hipGraphExec_t g = p->graphs.back().second;
-        p->graphs.pop_back();
-        HIP_TRY(hipGraphExecDestroy(g));
-    }
+    const int rc = p->graphs.clear();
+    if (rc) return rc;
     if (p->og_graph) {
-        HIP_TRY(hipGraphExecDestroy(p->og_graph));
+        OIVA_TRY_HIP(hipGraphExecDestroy(p->og_graph));
         p->og_graph = nullptr;
     }
     return OIVA_OK;
@@ -490,9 +458,9 @@ size_t vpart_floats(const oiva_plan* p, int nsplit) { return (size_t)nsplit * p-
 
 int ensure_vpart(oiva_plan* p) {
     if (p->cov.nsplit > p->vpart_splits_alloc) {
-        if (p->Vpart) HIP_TRY(hipFree(p->Vpart));
+        if (p->Vpart) OIVA_TRY_HIP(hipFree(p->Vpart));
         p->Vpart = nullptr;
-        HIP_TRY(dev_malloc(&p->Vpart, (vpart_floats(p, p->cov.nsplit) + 2) * sizeof(double)));   // either element type; sum_vpart reads idx + 1
+        OIVA_TRY_HIP(dev_malloc(&p->Vpart, (vpart_floats(p, p->cov.nsplit) + 2) * sizeof(double)));   // either element type; sum_vpart reads idx + 1
         p->vpart_splits_alloc = p->cov.nsplit;
     }
     return OIVA_OK;
@@ -509,24 +477,24 @@ int stage_power(oiva_plan* p) {
         // as a loss on the 1024-bin shard
         if (g.rounds > 1 || p->power_reverse > 1) g.ord = make_pow_order(g.nsplit, g.tcp, p->cov.nsplit, p->cov.tc);
     }
-    HIP_TRY(launch_power(p->stream, p->X, p->X_pad && p->pad_valid ? p->X_pad : nullptr, p->What, p->Ppart, p->T, p->F, p->M, p->K, g));
+    OIVA_TRY_HIP(launch_power(p->stream, p->X, p->X_pad && p->pad_valid ? p->X_pad : nullptr, p->What, p->Ppart, p->T, p->F, p->M, p->K, g));
     return OIVA_OK;
 }
 int stage_activation(oiva_plan* p, const float* parts, int nparts) {
     if (p->fx_on && parts == p->Ppart) {
         // bins sharded over GPUs, the ranks' sums exchanged by the activation kernel itself (no collective, no host in the loop)
-        HIP_TRY(launch_activation_xchg(p->stream, parts, nparts, p->fx_gath, p->fx_rank, p->fx_world, p->fx_loopback ? (p->fx_stall ? 2 : 1) : 0, p->fx_nblk_own, p->fx_nblk_peer, p->fx_state + 16,
+        OIVA_TRY_HIP(launch_activation_xchg(p->stream, parts, nparts, p->fx_gath, p->fx_rank, p->fx_world, p->fx_loopback ? (p->fx_stall ? 2 : 1) : 0, p->fx_nblk_own, p->fx_nblk_peer, p->fx_state + 16,
                                        p->fx_state, (long long)(p->fx_timeout_ms > 0 ? p->fx_timeout_ms : 2000) * 100000, p->R, p->T, p->K,
                                        p->model, p->F_total));
         p->raw_weights = 0;
         return OIVA_OK;
     }
-    HIP_TRY(launch_activation(p->stream, parts, nparts, p->R, p->T, p->K, p->model, p->F_total));
+    OIVA_TRY_HIP(launch_activation(p->stream, parts, nparts, p->R, p->T, p->K, p->model, p->F_total));
     p->raw_weights = 0;
     return OIVA_OK;
 }
 int stage_cov(oiva_plan* p) {
-    HIP_TRY(launch_cov(p->stream, p->X, p->X_pad, p->R, p->Wwide ? static_cast<float*>(p->Wwide) : p->Plocal /* weights scratch, (T,16) */, p->wscale, p->model,
+    OIVA_TRY_HIP(launch_cov(p->stream, p->X, p->X_pad, p->R, p->Wwide ? static_cast<float*>(p->Wwide) : p->Plocal /* weights scratch, (T,16) */, p->wscale, p->model,
                        p->raw_weights, p->Vpart, p->cov_f64(), p->T, p->F, p->M, p->K, p->cov));
     p->wscale_pending = !p->raw_weights;
     return OIVA_OK;
@@ -547,7 +515,7 @@ int stage_update(oiva_plan* p, bool init_only) {
     a.init_only = init_only ? 1 : 0;
     a.use_double = p->upd_f64() ? 1 : 0;
     a.layout = (p->prec & OIVA_PREC_UPDATE_ROWS) ? 1 : 0;
-    HIP_TRY(launch_update(p->stream, a));
+    OIVA_TRY_HIP(launch_update(p->stream, a));
     p->what64_valid = a.What64 != nullptr;      // the float32 variants leave the complex128 copy behind
     if (!init_only) p->wscale_pending = false;
     return OIVA_OK;
@@ -572,7 +540,7 @@ int stage_cov_update(oiva_plan* p) {
     a.init_only = 0;
     a.use_double = p->upd_f64() ? 1 : 0;
     a.layout = 0;
-    HIP_TRY(launch_cov_update(p->stream, p->X, p->R, p->wscale, p->model, a, p->cov.tc));
+    OIVA_TRY_HIP(launch_cov_update(p->stream, p->X, p->R, p->wscale, p->model, a, p->cov.tc));
     p->what64_valid = a.What64 != nullptr;
     p->wscale_pending = false;
     return OIVA_OK;
@@ -609,11 +577,11 @@ int resident_alloc(oiva_plan* p) {
     const size_t b_flags = up((16 + (size_t)g.NB * g.NS) * sizeof(unsigned));      // ctrl words, then the XCD table
     const size_t b_stamps = up((size_t)kResidentStampIters * kResidentStamps * sizeof(unsigned long long));
     const size_t total = b_parts + b_psum + b_vpart + b_rsum + b_wpub + b_flags + b_stamps;
-    if (!p->res_what) HIP_TRY(dev_malloc(&p->res_what, (size_t)p->F * NA * sizeof(float2)));
-    if (!p->res_what64) HIP_TRY(dev_malloc(&p->res_what64, (size_t)p->F * NA * sizeof(double2)));
-    if (!p->res_code_host) HIP_TRY(hipHostMalloc((void**)&p->res_code_host, sizeof(unsigned), hipHostMallocDefault));
-    HIP_TRY(dev_malloc(&p->res_block, total));
-    HIP_TRY(hipMemsetAsync(p->res_block, 0, total, p->stream));
+    if (!p->res_what) OIVA_TRY_HIP(dev_malloc(&p->res_what, (size_t)p->F * NA * sizeof(float2)));
+    if (!p->res_what64) OIVA_TRY_HIP(dev_malloc(&p->res_what64, (size_t)p->F * NA * sizeof(double2)));
+    if (!p->res_code_host) OIVA_TRY_HIP(hipHostMalloc((void**)&p->res_code_host, sizeof(unsigned), hipHostMallocDefault));
+    OIVA_TRY_HIP(dev_malloc(&p->res_block, total));
+    OIVA_TRY_HIP(hipMemsetAsync(p->res_block, 0, total, p->stream));
     char* c = static_cast<char*>(p->res_block);
     p->res_parts = reinterpret_cast<float*>(c);
     c += b_parts;
@@ -659,10 +627,10 @@ int run_resident(oiva_plan* p, int n, bool* ran) {
     a.stamp_all = 0;
     if (p->res_trace && n <= 64) {
         const size_t bytes = (size_t)g.NB * g.NS * n * kResidentStamps * sizeof(unsigned long long);
-        if (p->res_trace_buf) HIP_TRY(hipFree(p->res_trace_buf));
+        if (p->res_trace_buf) OIVA_TRY_HIP(hipFree(p->res_trace_buf));
         p->res_trace_buf = nullptr;
-        HIP_TRY(dev_malloc(&p->res_trace_buf, bytes));
-        HIP_TRY(hipMemsetAsync(p->res_trace_buf, 0, bytes, p->stream));
+        OIVA_TRY_HIP(dev_malloc(&p->res_trace_buf, bytes));
+        OIVA_TRY_HIP(hipMemsetAsync(p->res_trace_buf, 0, bytes, p->stream));
         a.stamps = p->res_trace_buf;
         a.stamp_all = 1;
         p->res_trace_iters = n;
@@ -681,23 +649,23 @@ int run_resident(oiva_plan* p, int n, bool* ran) {
     a.world = p->res_world;
     a.loopback = p->res_loopback ? 1 : 0;
     for (int r = 0; r < OIVA_XCHG_MAX_RANKS; ++r) a.gath[r] = reinterpret_cast<float*>(p->res_gath[r]);
-    HIP_TRY(launch_resident(p->stream, a, p->M, p->K, p->upd_f64(), p->cov_f64()));
+    OIVA_TRY_HIP(launch_resident(p->stream, a, p->M, p->K, p->upd_f64(), p->cov_f64()));
     p->res_launches++;
-    HIP_TRY(hipMemcpyAsync(p->res_code_host, a.ctrl, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));   // (pinned: one wait for both)
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemcpyAsync(p->res_code_host, a.ctrl, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));   // (pinned: one wait for both)
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     const unsigned code = *p->res_code_host;
     if (code != 0) {
         // some wait ran into its time-out (workgroups not co-resident, or the test hook): whatever the workgroups that did
         // finish wrote went to the staging copy, W_hat itself is untouched.
         // Clear the flags, start the epochs over and stay on the four-launch path from here on.
-        HIP_TRY(hipMemset(p->res_block, 0, p->res_block_bytes));
+        OIVA_TRY_HIP(hipMemset(p->res_block, 0, p->res_block_bytes));
         p->res_epoch = 0;
         p->res_last_code = (int)code;
         p->res_fallbacks++;
         p->res_on = false;
         p->res_stamped = 0;
         if (p->res_world > 1)      // the other ranks' state is unknown: no silent fall-back, the caller has to decide for all of them
-            return fail(OIVA_ERR_STATE, "the X-resident launch gave up waiting (code " + std::to_string(code) +
+            return fail_with(OIVA_ERR_STATE, "the X-resident launch gave up waiting (code " + std::to_string(code) +
                                         "): a rank did not deliver its parts in time; W_hat of this rank is unchanged");
         return OIVA_OK;
     }
@@ -726,43 +694,15 @@ int run_resident(oiva_plan* p, int n, bool* ran) {
 // us).  oiva_plan_use_graph captures the 8-iteration graph ahead of time, so that short calls never capture inside a
 // caller's timed region; other lengths are captured by the first call that asks for them (0.1-0.4 ms) and kept.
 int graph_for(oiva_plan* p, int iters, hipGraphExec_t* out) {
-    for (size_t i = 0; i < p->graphs.size(); ++i)
-        if (p->graphs[i].first == iters) {
-            auto hit = p->graphs[i];
-            p->graphs.erase(p->graphs.begin() + (long)i);
-            p->graphs.push_back(hit);
-            *out = hit.second;
-            return OIVA_OK;
-        }
-    const bool pending = p->wscale_pending;
-    const int raw = p->raw_weights;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    HIP_TRY(hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal));
-    int r = OIVA_OK;
-    for (int i = 0; i < iters && r == OIVA_OK; ++i) r = one_iteration(p);
-    hipError_t e = hipStreamEndCapture(p->stream, &graph);
-    p->wscale_pending = pending;   // capturing toggled the host-side flags without running anything
-    p->raw_weights = raw;
-    if (r) {
-        if (graph) (void)hipGraphDestroy(graph);
+    return p->graphs.get(p->stream, iters, [&] {
+        const bool pending = p->wscale_pending;
+        const int raw = p->raw_weights;
+        int r = OIVA_OK;
+        for (int i = 0; i < iters && r == OIVA_OK; ++i) r = one_iteration(p);
+        p->wscale_pending = pending;   // capturing toggled the host-side flags without running anything
+        p->raw_weights = raw;
         return r;
-    }
-    HIP_TRY(e);
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    HIP_TRY(e);
-    // move the executable graph to the device now: otherwise its FIRST launch pays for that, inside whatever the
-    // caller is timing (a few percent of a 20-iteration run)
-    HIP_TRY(hipGraphUpload(exec, p->stream));
-    if ((int)p->graphs.size() >= kGraphCache) {
-        HIP_TRY(hipStreamSynchronize(p->stream));          // (the evicted graph may still be replaying)
-        HIP_TRY(hipGraphExecDestroy(p->graphs.front().second));
-        p->graphs.erase(p->graphs.begin());
-    }
-    p->graphs.emplace_back(iters, exec);
-    *out = exec;
-    return OIVA_OK;
+    }, out);
 }
 
 int build_graphs(oiva_plan* p) {
@@ -774,9 +714,9 @@ int build_graphs(oiva_plan* p) {
 int upload_what(oiva_plan* p, const std::vector<double2>& wh) {
     std::vector<float2> w32(wh.size());
     for (size_t i = 0; i < wh.size(); ++i) w32[i] = make_float2((float)wh[i].x, (float)wh[i].y);
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemcpy(p->What, w32.data(), w32.size() * sizeof(float2), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->What64, wh.data(), wh.size() * sizeof(double2), hipMemcpyHostToDevice));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemcpy(p->What, w32.data(), w32.size() * sizeof(float2), hipMemcpyHostToDevice));
+    OIVA_TRY_HIP(hipMemcpy(p->What64, wh.data(), wh.size() * sizeof(double2), hipMemcpyHostToDevice));
     p->what64_valid = true;
     return OIVA_OK;
 }
@@ -784,13 +724,13 @@ int upload_what(oiva_plan* p, const std::vector<double2>& wh) {
 // the current W_hat in float64: the complex128 copy when the float64 update maintains it, else the complex64 one
 int download_what(oiva_plan* p, std::vector<double2>& wh) {
     wh.resize((size_t)p->F * p->M * p->M);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     if (p->what64_valid) {
-        HIP_TRY(hipMemcpy(wh.data(), p->What64, wh.size() * sizeof(double2), hipMemcpyDeviceToHost));
+        OIVA_TRY_HIP(hipMemcpy(wh.data(), p->What64, wh.size() * sizeof(double2), hipMemcpyDeviceToHost));
         return OIVA_OK;
     }
     std::vector<float2> w32(wh.size());
-    HIP_TRY(hipMemcpy(w32.data(), p->What, w32.size() * sizeof(float2), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(hipMemcpy(w32.data(), p->What, w32.size() * sizeof(float2), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < wh.size(); ++i) wh[i] = make_double2(w32[i].x, w32[i].y);
     return OIVA_OK;
 }
@@ -798,31 +738,18 @@ int download_what(oiva_plan* p, std::vector<double2>& wh) {
 // the padded copy of X the vector-ALU covariance kernels read at 9 / 11 / 13 / 15 channels
 int ensure_pad(oiva_plan* p) {
     if (p->X_pad == nullptr || p->pad_valid) return OIVA_OK;
-    HIP_TRY(launch_pad_channels(p->stream, p->X, p->X_pad, (long long)p->T * p->F, p->M));
+    OIVA_TRY_HIP(launch_pad_channels(p->stream, p->X, p->X_pad, (long long)p->T * p->F, p->M));
     p->pad_valid = true;
     return OIVA_OK;
 }
 
 int check_ready(oiva_plan* p) {
-    NEED(p != nullptr, OIVA_ERR_ARG, "null plan");
-    NEED(p->have_x, OIVA_ERR_STATE, "X not set (oiva_plan_set_x_host/_dev)");
-    NEED(p->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_plan_covariance)");
-    NEED(p->have_w, OIVA_ERR_STATE, "demixing matrix not set (oiva_plan_set_w)");
+    OIVA_NEED(p != nullptr, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p->have_x, OIVA_ERR_STATE, "X not set (oiva_plan_set_x_host/_dev)");
+    OIVA_NEED(p->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_plan_covariance)");
+    OIVA_NEED(p->have_w, OIVA_ERR_STATE, "demixing matrix not set (oiva_plan_set_w)");
     return OIVA_OK;
 }
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
 
 }  // namespace
 
@@ -833,23 +760,23 @@ int oiva_version(void) { return 100; }
 const char* oiva_last_error(void) { return g_err.c_str(); }
 
 int oiva_device_count(int* n) {
-    NEED(n != nullptr, OIVA_ERR_ARG, "null pointer");
-    HIP_TRY(hipGetDeviceCount(n));
+    OIVA_NEED(n != nullptr, OIVA_ERR_ARG, "null pointer");
+    OIVA_TRY_HIP(hipGetDeviceCount(n));
     return OIVA_OK;
 }
 
 int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, int model, int F_total, void* stream) {
-    NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
+    OIVA_NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
     *out = nullptr;
-    NEED(T >= 1 && F >= 1, OIVA_ERR_ARG, "T and F must be >= 1");
-    NEED(M >= 1 && M <= OIVA_MAX_CHANNELS, OIVA_ERR_ARG, "number of channels must be in 1..32");
-    NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "n_src must be in 1..n_chan");
-    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
-    NEED(F_total >= F, OIVA_ERR_ARG, "F_total must be >= F");
-    NEED(cov_supported(M), OIVA_ERR_ARG, "unsupported number of channels");
+    OIVA_NEED(T >= 1 && F >= 1, OIVA_ERR_ARG, "T and F must be >= 1");
+    OIVA_NEED(M >= 1 && M <= OIVA_MAX_CHANNELS, OIVA_ERR_ARG, "number of channels must be in 1..32");
+    OIVA_NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "n_src must be in 1..n_chan");
+    OIVA_NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
+    OIVA_NEED(F_total >= F, OIVA_ERR_ARG, "F_total must be >= F");
+    OIVA_NEED(cov_supported(M), OIVA_ERR_ARG, "unsupported number of channels");
     int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    NEED(device >= 0 && device < ndev, OIVA_ERR_ARG, "no such device");
+    OIVA_TRY_HIP(hipGetDeviceCount(&ndev));
+    OIVA_NEED(device >= 0 && device < ndev, OIVA_ERR_ARG, "no such device");
     DeviceGuard guard(device);
 
     oiva_plan* p = new oiva_plan();
@@ -866,7 +793,7 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
         hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
             delete p;
-            return fail(OIVA_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+            return fail_with(OIVA_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
         }
         p->own_stream = true;
     }
@@ -881,7 +808,7 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
         hipError_t ep = dev_malloc((void**)&p->X_pad, (size_t)T * F * (M + 1) * sizeof(float2));
         if (ep != hipSuccess) {
             oiva_plan_destroy(p);
-            return fail(OIVA_ERR_HIP, std::string("allocation of the padded copy of X failed: ") + hipGetErrorString(ep));
+            return fail_with(OIVA_ERR_HIP, std::string("allocation of the padded copy of X failed: ") + hipGetErrorString(ep));
         }
     }
     {
@@ -898,29 +825,26 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
     p->res_ok = resident_geometry(T, F, M, K, p->n_cu, 0, &p->rg);
     const size_t nTK = (size_t)T * K;
     const size_t nFMM = (size_t)F * M * M;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** ptr, size_t bytes) {
-        if (e == hipSuccess) e = dev_malloc(ptr, bytes);
-    };
-    alloc((void**)&p->What, nFMM * sizeof(float2));
-    alloc((void**)&p->What64, nFMM * sizeof(double2));
-    alloc((void**)&p->Cx, nFMM * sizeof(double));
-    alloc((void**)&p->Ppart, (size_t)p->pw.nb * nTK * sizeof(float));
+    AllocChain alloc;
+    alloc(&p->What, nFMM * sizeof(float2));
+    alloc(&p->What64, nFMM * sizeof(double2));
+    alloc(&p->Cx, nFMM * sizeof(double));
+    alloc(&p->Ppart, (size_t)p->pw.nb * nTK * sizeof(float));
     p->ppart_alloc = p->pw.nb;
-    alloc((void**)&p->Plocal, std::max(nTK, ((size_t)T + 1) * 32) * sizeof(float));   // also the (T + 1, 16) weights scratch (floats or doubles)
-    if (M > kNarrowMax) alloc((void**)&p->Wwide, nTK * sizeof(double));                // the wide path's (T, K) float64 weights
-    alloc((void**)&p->R, r_buffer_bytes(T, K));   // activations, zeroed pad rows, per-block sums (rsum_offset_floats)
-    if (e == hipSuccess) e = hipMemset(p->R, 0, r_buffer_bytes(T, K));
-    alloc((void**)&p->wscale, (size_t)K * sizeof(float));
-    alloc((void**)&p->Spart, (size_t)p->stg.nsplit * F * K * 3 * sizeof(float));
-    alloc((void**)&p->scratch_c, (size_t)K * nFMM * sizeof(double2));
-    alloc((void**)&p->scratch_p, std::max((size_t)K * nFMM, nTK) * sizeof(double));
+    alloc(&p->Plocal, std::max(nTK, ((size_t)T + 1) * 32) * sizeof(float));   // also the (T + 1, 16) weights scratch (floats or doubles)
+    if (M > kNarrowMax) alloc(&p->Wwide, nTK * sizeof(double));                // the wide path's (T, K) float64 weights
+    alloc(&p->R, r_buffer_bytes(T, K));   // activations, zeroed pad rows, per-block sums (rsum_offset_floats)
+    if (alloc.ok()) alloc.err = hipMemset(p->R, 0, r_buffer_bytes(T, K));
+    alloc(&p->wscale, (size_t)K * sizeof(float));
+    alloc(&p->Spart, (size_t)p->stg.nsplit * F * K * 3 * sizeof(float));
+    alloc(&p->scratch_c, (size_t)K * nFMM * sizeof(double2));
+    alloc(&p->scratch_p, std::max((size_t)K * nFMM, nTK) * sizeof(double));
     for (auto& ev : p->ev) {
-        if (e == hipSuccess) e = hipEventCreate(&ev);
+        if (alloc.ok()) alloc.err = hipEventCreate(&ev);
     }
-    if (e != hipSuccess) {
+    if (!alloc.ok()) {
         oiva_plan_destroy(p);
-        return fail(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(e));
+        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
     }
     int rc = ensure_vpart(p);
     if (rc) {
@@ -935,7 +859,7 @@ int oiva_plan_destroy(oiva_plan* p) {
     if (!p) return OIVA_OK;
     DeviceGuard guard(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    for (auto& g : p->graphs) (void)hipGraphExecDestroy(g.second);
+    (void)p->graphs.clear();
     if (p->og_graph) (void)hipGraphExecDestroy(p->og_graph);
     if (p->res_code_host) (void)hipHostFree(p->res_code_host);
     if (p->io_stream) (void)hipStreamSynchronize(p->io_stream);
@@ -970,17 +894,17 @@ int oiva_plan_destroy(oiva_plan* p) {
 }
 
 int oiva_plan_set_x_host(oiva_plan* p, const void* X, long long row_pitch_bytes) {
-    NEED(p && X, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && X, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(p->device);
     const size_t row = (size_t)p->F * p->M * sizeof(float2);
     const size_t pitch = row_pitch_bytes > 0 ? (size_t)row_pitch_bytes : row;
-    NEED(pitch >= row, OIVA_ERR_ARG, "row pitch smaller than one frame of this plan's bins");
+    OIVA_NEED(pitch >= row, OIVA_ERR_ARG, "row pitch smaller than one frame of this plan's bins");
     if (!p->X_owned) {
-        HIP_TRY(big_alloc(p->device, (void**)&p->X_owned, row * p->T));
+        OIVA_TRY_HIP(big_alloc(p->device, (void**)&p->X_owned, row * p->T));
         p->x_owned_bytes = row * p->T;
     }
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemcpy2D(p->X_owned, row, X, pitch, row, p->T, hipMemcpyHostToDevice));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemcpy2D(p->X_owned, row, X, pitch, row, p->T, hipMemcpyHostToDevice));
     if (p->X != p->X_owned) {             // switching from a borrowed array: captured graphs hold its pointer
         int rc = drop_graph(p);
         if (rc) return rc;
@@ -993,22 +917,22 @@ int oiva_plan_set_x_host(oiva_plan* p, const void* X, long long row_pitch_bytes)
 }
 
 int oiva_plan_set_x_host_c128(oiva_plan* p, const void* X, long long row_pitch_bytes) {
-    NEED(p && X, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && X, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(p->device);
     const size_t n_row = (size_t)p->F * p->M;
     const size_t row = n_row * sizeof(double2);
     const size_t pitch = row_pitch_bytes > 0 ? (size_t)row_pitch_bytes : row;
-    NEED(pitch >= row, OIVA_ERR_ARG, "row pitch smaller than one frame of this plan's bins");
+    OIVA_NEED(pitch >= row, OIVA_ERR_ARG, "row pitch smaller than one frame of this plan's bins");
     if (!p->X_owned) {
-        HIP_TRY(big_alloc(p->device, (void**)&p->X_owned, n_row * sizeof(float2) * p->T));
+        OIVA_TRY_HIP(big_alloc(p->device, (void**)&p->X_owned, n_row * sizeof(float2) * p->T));
         p->x_owned_bytes = n_row * sizeof(float2) * p->T;
     }
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     // in slabs of frames through a staging buffer (<= 256 MB): the conversion of one slab overlaps nothing, but the
     // footprint stays bounded and the host never touches the data (a NumPy astype of 1 GB costs 60 ms)
     const int slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)p->T, ((size_t)256 << 20) / row));
     double2* stage = nullptr;
-    HIP_TRY(big_alloc(p->device, (void**)&stage, row * slab));
+    OIVA_TRY_HIP(big_alloc(p->device, (void**)&stage, row * slab));
     hipError_t e = hipSuccess;
     for (int t0 = 0; t0 < p->T && e == hipSuccess; t0 += slab) {
         const int nt = std::min(slab, p->T - t0);
@@ -1017,7 +941,7 @@ int oiva_plan_set_x_host_c128(oiva_plan* p, const void* X, long long row_pitch_b
         if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     }
     if (e == hipSuccess) big_free(p->device, stage, row * slab); else (void)hipFree(stage);
-    HIP_TRY(e);
+    OIVA_TRY_HIP(e);
     if (p->X != p->X_owned) {             // switching from a borrowed array: captured graphs hold its pointer
         int rc = drop_graph(p);
         if (rc) return rc;
@@ -1030,11 +954,11 @@ int oiva_plan_set_x_host_c128(oiva_plan* p, const void* X, long long row_pitch_b
 }
 
 int oiva_plan_set_x_dev(oiva_plan* p, const void* X_dev) {
-    NEED(p && X_dev, OIVA_ERR_ARG, "null argument");
-    NEED(((uintptr_t)X_dev & 15) == 0, OIVA_ERR_ARG, "device X must be 16-byte aligned");
+    OIVA_NEED(p && X_dev, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(((uintptr_t)X_dev & 15) == 0, OIVA_ERR_ARG, "device X must be 16-byte aligned");
     if (p->X != (const float2*)X_dev) {   // captured graphs hold the old pointer
         DeviceGuard guard(p->device);
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
         int rc = drop_graph(p);
         if (rc) return rc;
     }
@@ -1046,8 +970,8 @@ int oiva_plan_set_x_dev(oiva_plan* p, const void* X_dev) {
 }
 
 int oiva_plan_covariance(oiva_plan* p) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(p->have_x, OIVA_ERR_STATE, "X not set");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p->have_x, OIVA_ERR_STATE, "X not set");
     DeviceGuard guard(p->device);
     // (the padded copy follows X here: every path that changes X clears have_cx, and the iteration needs Cx; a borrowed X
     //  rewritten in place needs a new Cx too)
@@ -1058,45 +982,29 @@ int oiva_plan_covariance(oiva_plan* p) {
     g.kc = 1;
     g.part32 = 0;          // (one "source": never the matrix-core kernel)
     // unit weights, one "source": partials land in Vpart laid out as [nsplit][F][1][M*M]
-    HIP_TRY(launch_cov(p->stream, p->X, p->X_pad, nullptr, nullptr, nullptr, p->model, 0, p->Vpart, p->cov_f64(), p->T, p->F, p->M, 1, g));
-    HIP_TRY(launch_sum_parts(p->stream, p->Vpart, p->vpart_f64_of(g), g.nsplit, p->Cx, (long long)p->F * p->M * p->M, 1. / (double)p->T));
+    OIVA_TRY_HIP(launch_cov(p->stream, p->X, p->X_pad, nullptr, nullptr, nullptr, p->model, 0, p->Vpart, p->cov_f64(), p->T, p->F, p->M, 1, g));
+    OIVA_TRY_HIP(launch_sum_parts(p->stream, p->Vpart, p->vpart_f64_of(g), g.nsplit, p->Cx, (long long)p->F * p->M * p->M, 1. / (double)p->T));
     p->have_cx = true;
     return OIVA_OK;
 }
 
 int oiva_plan_get_cx(oiva_plan* p, void* Cx_host, int f64) {
-    NEED(p && Cx_host, OIVA_ERR_ARG, "null argument");
-    NEED(p->have_cx, OIVA_ERR_STATE, "input covariance not computed");
+    OIVA_NEED(p && Cx_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p->have_cx, OIVA_ERR_STATE, "input covariance not computed");
     DeviceGuard guard(p->device);
     const size_t n = (size_t)p->F * p->M * p->M;
-    HIP_TRY(launch_unpack_herm(p->stream, p->Cx, p->scratch_c, f64 != 0, p->F, p->M));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemcpy(Cx_host, p->scratch_c, n * (f64 ? sizeof(double2) : sizeof(float2)), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(launch_unpack_herm(p->stream, p->Cx, p->scratch_c, f64 != 0, p->F, p->M));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemcpy(Cx_host, p->scratch_c, n * (f64 ? sizeof(double2) : sizeof(float2)), hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 
 int oiva_plan_set_w(oiva_plan* p, const void* W0_host, int f64) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(p->have_cx, OIVA_ERR_STATE, "input covariance not computed (needed for the orthogonality constraint)");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p->have_cx, OIVA_ERR_STATE, "input covariance not computed (needed for the orthogonality constraint)");
     DeviceGuard guard(p->device);
-    const int F = p->F, M = p->M, K = p->K;
-    std::vector<double2> wh((size_t)F * M * M, make_double2(0., 0.));
-    for (int f = 0; f < F; ++f) {
-        double2* m = wh.data() + (size_t)f * M * M;
-        for (int r = 0; r < M; ++r)
-            for (int k = 0; k < K; ++k) {
-                const size_t i = ((size_t)f * M + r) * K + k;
-                if (!W0_host) {
-                    m[r * M + k] = make_double2(r == k ? 1. : 0., 0.);           // overiva.py:113-114
-                } else if (f64) {
-                    m[r * M + k] = static_cast<const double2*>(W0_host)[i];       // overiva.py:116-117
-                } else {
-                    const float2 v = static_cast<const float2*>(W0_host)[i];
-                    m[r * M + k] = make_double2(v.x, v.y);
-                }
-            }
-        for (int r = K; r < M; ++r) m[r * M + r] = make_double2(-1., 0.);  // overiva.py:122-123
-    }
+    const int M = p->M, K = p->K;
+    const std::vector<double2> wh = pack_what(W0_host, f64, (size_t)p->F, M, K);
     int rc = upload_what(p, wh);
     if (rc) return rc;
     p->wscale_pending = false;
@@ -1111,17 +1019,17 @@ int oiva_plan_set_w_pca(oiva_plan* p, double* evals_host) { return set_w_from_ei
 int oiva_plan_set_w_eig(oiva_plan* p) { return set_w_from_eigenvectors(p, nullptr, true); }
 
 static int set_w_from_eigenvectors(oiva_plan* p, double* evals_host, bool lapack_phase) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(p->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_plan_covariance)");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_plan_covariance)");
     DeviceGuard guard(p->device);
     double* evals = evals_host ? p->scratch_p : nullptr;       // scratch_p holds at least K * F * M * M doubles
-    HIP_TRY(launch_pca_subspace(p->stream, p->Cx, p->What, p->What64, evals, p->F, p->M, p->K, lapack_phase));
+    OIVA_TRY_HIP(launch_pca_subspace(p->stream, p->Cx, p->What, p->What64, evals, p->F, p->M, p->K, lapack_phase));
     p->what64_valid = true;
     p->wscale_pending = false;
     p->have_w = true;
     if (evals_host) {
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        HIP_TRY(hipMemcpy(evals_host, evals, (size_t)p->F * p->M * sizeof(double), hipMemcpyDeviceToHost));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipMemcpy(evals_host, evals, (size_t)p->F * p->M * sizeof(double), hipMemcpyDeviceToHost));
     }
     if (p->K < p->M) return stage_update(p, true);             // J from the orthogonality constraint
     return OIVA_OK;
@@ -1132,21 +1040,21 @@ static int check_fused(oiva_plan* p);
 int oiva_plan_demix_dev(oiva_plan* p, int proj_back, void** Y_dev) {
     int rc = check_ready(p);
     if (rc) return rc;
-    NEED(Y_dev, OIVA_ERR_ARG, "null output");
+    OIVA_NEED(Y_dev, OIVA_ERR_ARG, "null output");
     DeviceGuard guard(p->device);
     if ((rc = check_fused(p))) return rc;
     const size_t row = (size_t)p->F * p->K * sizeof(float2);
     if (!p->Y) {
-        HIP_TRY(big_alloc(p->device, (void**)&p->Y, row * p->T));
+        OIVA_TRY_HIP(big_alloc(p->device, (void**)&p->Y, row * p->T));
         p->y_bytes = row * p->T;
     }
     const float* sp = nullptr;
     if (proj_back) {
-        HIP_TRY(launch_demix_stats(p->stream, p->X, p->What, p->Spart, p->T, p->F, p->M, p->K, p->stg));
+        OIVA_TRY_HIP(launch_demix_stats(p->stream, p->X, p->What, p->Spart, p->T, p->F, p->M, p->K, p->stg));
         sp = p->Spart;
     }
-    HIP_TRY(launch_demix_write(p->stream, p->X, p->What, sp, p->stg.nsplit, p->Y, p->T, p->F, p->M, p->K));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(launch_demix_write(p->stream, p->X, p->What, sp, p->stg.nsplit, p->Y, p->T, p->F, p->M, p->K));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     *Y_dev = p->Y;
     return OIVA_OK;
 }
@@ -1154,10 +1062,10 @@ int oiva_plan_demix_dev(oiva_plan* p, int proj_back, void** Y_dev) {
 int oiva_plan_iterate(oiva_plan* p, int n) {
     int rc = check_ready(p);
     if (rc) return rc;
-    NEED(n >= 0, OIVA_ERR_ARG, "negative iteration count");
-    NEED(p->F == p->F_total || resident_applies(p) || p->fx_on, OIVA_ERR_STATE,
-         "plan owns a bin shard: drive it with oiva_plan_power / all-gather / oiva_plan_update (or connect an in-kernel exchange: "
-         "oiva_plan_fused_connect, oiva_plan_resident_connect)");
+    OIVA_NEED(n >= 0, OIVA_ERR_ARG, "negative iteration count");
+    OIVA_NEED(p->F == p->F_total || resident_applies(p) || p->fx_on, OIVA_ERR_STATE,
+              "plan owns a bin shard: drive it with oiva_plan_power / all-gather / oiva_plan_update (or connect an in-kernel exchange: "
+              "oiva_plan_fused_connect, oiva_plan_resident_connect)");
     DeviceGuard guard(p->device);
     if (n == 0) return OIVA_OK;
     if (resident_applies(p)) {
@@ -1170,7 +1078,7 @@ int oiva_plan_iterate(oiva_plan* p, int n) {
             const int m = std::min(left, kGraphMaxIters);
             hipGraphExec_t g = nullptr;
             if ((rc = graph_for(p, m, &g))) return rc;
-            HIP_TRY(hipGraphLaunch(g, p->stream));
+            OIVA_TRY_HIP(hipGraphLaunch(g, p->stream));
             left -= m;
         }
         // the host-side flags after n iterations, whether the graph was captured now (capturing runs stage_update, which sets
@@ -1193,19 +1101,19 @@ int oiva_plan_power(oiva_plan* p) {
 }
 
 int oiva_plan_power_buffer(oiva_plan* p, int parts_per_rank, void** parts_dev, long long* bytes) {
-    NEED(p && parts_dev, OIVA_ERR_ARG, "null argument");
-    NEED(parts_per_rank >= p->pw.nb, OIVA_ERR_ARG, "parts_per_rank smaller than this plan's own bin batches");
+    OIVA_NEED(p && parts_dev, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(parts_per_rank >= p->pw.nb, OIVA_ERR_ARG, "parts_per_rank smaller than this plan's own bin batches");
     DeviceGuard guard(p->device);
     const size_t part = (size_t)p->T * p->K * sizeof(float);
     if (parts_per_rank > p->ppart_alloc) {
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
         int rc = drop_graph(p);
         if (rc) return rc;
-        if (p->Ppart) HIP_TRY(hipFree(p->Ppart));
+        if (p->Ppart) OIVA_TRY_HIP(hipFree(p->Ppart));
         p->Ppart = nullptr;
-        HIP_TRY(dev_malloc(&p->Ppart, part * parts_per_rank));
+        OIVA_TRY_HIP(dev_malloc(&p->Ppart, part * parts_per_rank));
         // parts beyond nb stay zero; on the plan's own stream, so that it is ordered before the next power pass
-        HIP_TRY(hipMemsetAsync(p->Ppart, 0, part * parts_per_rank, p->stream));
+        OIVA_TRY_HIP(hipMemsetAsync(p->Ppart, 0, part * parts_per_rank, p->stream));
         p->ppart_alloc = parts_per_rank;
     }
     *parts_dev = p->Ppart;
@@ -1216,7 +1124,7 @@ int oiva_plan_power_buffer(oiva_plan* p, int parts_per_rank, void** parts_dev, l
 int oiva_plan_update(oiva_plan* p, const void* parts_dev, int nparts) {
     int rc = check_ready(p);
     if (rc) return rc;
-    NEED(parts_dev && nparts >= 1, OIVA_ERR_ARG, "need at least one part");
+    OIVA_NEED(parts_dev && nparts >= 1, OIVA_ERR_ARG, "need at least one part");
     DeviceGuard guard(p->device);
     if ((rc = stage_activation(p, (const float*)parts_dev, nparts))) return rc;
     if (cov_update_applies(p)) return stage_cov_update(p);
@@ -1234,21 +1142,21 @@ int oiva_plan_update(oiva_plan* p, const void* parts_dev, int nparts) {
 static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, int proj_back, bool c128) {
     int rc = check_ready(p);
     if (rc) return rc;
-    NEED(Y_host, OIVA_ERR_ARG, "null output");
+    OIVA_NEED(Y_host, OIVA_ERR_ARG, "null output");
     DeviceGuard guard(p->device);
     const size_t n_row = (size_t)p->F * p->K;
     const size_t row_dev = n_row * sizeof(float2);
     const size_t row = c128 ? n_row * sizeof(double2) : row_dev;
     const size_t pitch = row_pitch_bytes > 0 ? (size_t)row_pitch_bytes : row;
-    NEED(pitch >= row, OIVA_ERR_ARG, "row pitch smaller than one frame of this plan's bins");
+    OIVA_NEED(pitch >= row, OIVA_ERR_ARG, "row pitch smaller than one frame of this plan's bins");
     if ((rc = check_fused(p))) return rc;
     if (!p->Y) {
-        HIP_TRY(big_alloc(p->device, (void**)&p->Y, row_dev * p->T));
+        OIVA_TRY_HIP(big_alloc(p->device, (void**)&p->Y, row_dev * p->T));
         p->y_bytes = row_dev * p->T;
     }
     const float* sp = nullptr;
     if (proj_back) {
-        HIP_TRY(launch_demix_stats(p->stream, p->X, p->What, p->Spart, p->T, p->F, p->M, p->K, p->stg));
+        OIVA_TRY_HIP(launch_demix_stats(p->stream, p->X, p->What, p->Spart, p->T, p->F, p->M, p->K, p->stg));
         sp = p->Spart;
     }
     static const int mode = [] {
@@ -1260,15 +1168,15 @@ static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
     const size_t slab_target = p->io_slab_bytes ? p->io_slab_bytes : ((size_t)8 << 20);
     if (mode == 0 || (size_t)p->T * row < slab_target / 2) {
         // small outputs (and the legacy form): one kernel, one copy
-        HIP_TRY(launch_demix_write(p->stream, p->X, p->What, sp, p->stg.nsplit, p->Y, p->T, p->F, p->M, p->K));
+        OIVA_TRY_HIP(launch_demix_write(p->stream, p->X, p->What, sp, p->stg.nsplit, p->Y, p->T, p->F, p->M, p->K));
         if (!c128) {
-            HIP_TRY(hipStreamSynchronize(p->stream));
-            HIP_TRY(hipMemcpy2D(Y_host, pitch, p->Y, row, row, p->T, hipMemcpyDeviceToHost));
+            OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+            OIVA_TRY_HIP(hipMemcpy2D(Y_host, pitch, p->Y, row, row, p->T, hipMemcpyDeviceToHost));
             return OIVA_OK;
         }
         const int slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)p->T, ((size_t)256 << 20) / row));
         double2* stage = nullptr;
-        HIP_TRY(dev_malloc(&stage, row * slab));
+        OIVA_TRY_HIP(dev_malloc(&stage, row * slab));
         hipError_t e = hipSuccess;
         for (int t0 = 0; t0 < p->T && e == hipSuccess; t0 += slab) {
             const int nt = std::min(slab, p->T - t0);
@@ -1278,20 +1186,20 @@ static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
                 e = hipMemcpy2D(static_cast<char*>(Y_host) + (size_t)t0 * pitch, pitch, stage, row, row, nt, hipMemcpyDeviceToHost);
         }
         (void)hipFree(stage);
-        HIP_TRY(e);
+        OIVA_TRY_HIP(e);
         return OIVA_OK;
     }
     // ---- slabs of about 8 MB of output
     const int slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)p->T, slab_target / row));
     const int nslab = ceil_div(p->T, slab);
     const size_t slab_bytes = (size_t)slab * row;
-    if (!p->io_stream) HIP_TRY(hipStreamCreateWithFlags(&p->io_stream, hipStreamNonBlocking));
+    if (!p->io_stream) OIVA_TRY_HIP(hipStreamCreateWithFlags(&p->io_stream, hipStreamNonBlocking));
     for (int i = 0; i < kHostRingSlots; ++i) {
-        if (!p->io_written[i]) HIP_TRY(hipEventCreateWithFlags(&p->io_written[i], hipEventDisableTiming));
-        if (!p->io_copied[i]) HIP_TRY(hipEventCreateWithFlags(&p->io_copied[i], hipEventDisableTiming));
+        if (!p->io_written[i]) OIVA_TRY_HIP(hipEventCreateWithFlags(&p->io_written[i], hipEventDisableTiming));
+        if (!p->io_copied[i]) OIVA_TRY_HIP(hipEventCreateWithFlags(&p->io_copied[i], hipEventDisableTiming));
     }
     if (c128 && p->io_c128_bytes < slab_bytes) {
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
         // all three or none: the recorded size is that of every non-null slot, also after a failed allocation
         for (auto& b : p->io_c128) {
             big_free(p->device, b, p->io_c128_bytes);
@@ -1305,7 +1213,7 @@ static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
                     if (c) (void)hipFree(c);
                     c = nullptr;
                 }
-                HIP_TRY(e);
+                OIVA_TRY_HIP(e);
             }
         }
         p->io_c128_bytes = slab_bytes;
@@ -1321,13 +1229,13 @@ static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
     std::unique_lock<std::mutex> io_lock(io_mutex, std::defer_lock);
     if (!registered) {
         io_lock.lock();
-        HIP_TRY(host_ring_slots(slab_bytes, pinned));
+        OIVA_TRY_HIP(host_ring_slots(slab_bytes, pinned));
     }
     auto finish = [&](hipError_t e) -> int {
         // nothing of this call is in flight when the ring (io_mutex) passes to the next caller, also after an error
         (void)hipStreamSynchronize(p->io_stream);
         if (registered) (void)hipHostUnregister(Y_host);
-        if (e != hipSuccess) return fail(OIVA_ERR_HIP, std::string("final demix: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail_with(OIVA_ERR_HIP, std::string("final demix: ") + hipGetErrorString(e));
         return OIVA_OK;
     };
     auto issue = [&](int k) -> hipError_t {
@@ -1380,7 +1288,7 @@ int oiva_pool_trim(void) {
 }
 
 int oiva_plan_set_io_slab(oiva_plan* p, long long bytes) {
-    NEED(p && bytes >= 0, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(p && bytes >= 0, OIVA_ERR_ARG, "bad arguments");
     p->io_slab_bytes = (size_t)bytes;
     return OIVA_OK;
 }
@@ -1394,28 +1302,16 @@ int oiva_plan_demix_c128(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
 }
 
 int oiva_plan_get_w(oiva_plan* p, void* W_host, int f64) {
-    NEED(p && W_host, OIVA_ERR_ARG, "null argument");
-    NEED(p->have_w, OIVA_ERR_STATE, "demixing matrix not set");
+    OIVA_NEED(p && W_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p->have_w, OIVA_ERR_STATE, "demixing matrix not set");
     DeviceGuard guard(p->device);
-    const int F = p->F, M = p->M, K = p->K;
     int rc = check_fused(p);
     if (rc) return rc;
     std::vector<double2> wh;
     rc = download_what(p, wh);
     if (rc) return rc;
-    bool finite = true;
-    for (int f = 0; f < F; ++f)
-        for (int r = 0; r < M; ++r)
-            for (int k = 0; k < K; ++k) {
-                const double2 v = wh[((size_t)f * M + r) * M + k];
-                finite = finite && std::isfinite(v.x) && std::isfinite(v.y);
-                const size_t i = ((size_t)f * M + r) * K + k;
-                if (f64)
-                    static_cast<double2*>(W_host)[i] = v;
-                else
-                    static_cast<float2*>(W_host)[i] = make_float2((float)v.x, (float)v.y);
-            }
-    if (!finite) return fail(OIVA_ERR_NUMERIC, "demixing matrix holds non-finite values (singular W_hat^H V)");
+    const bool finite = unpack_w(wh, 0, (size_t)p->F, p->M, p->K, W_host, f64);
+    if (!finite) return fail_with(OIVA_ERR_NUMERIC, "demixing matrix holds non-finite values (singular W_hat^H V)");
     return OIVA_OK;
 }
 
@@ -1424,46 +1320,46 @@ int oiva_plan_get_w(oiva_plan* p, void* W_host, int f64) {
 // work already queued on the plan's stream and read after ONE wait for that stream.
 static int check_fused(oiva_plan* p) {
     if (!p->fx_state || !p->fx_on) return OIVA_OK;
-    if (!p->fx_flag_host) HIP_TRY(hipHostMalloc((void**)&p->fx_flag_host, sizeof(unsigned), hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(p->fx_flag_host, p->fx_state, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (!p->fx_flag_host) OIVA_TRY_HIP(hipHostMalloc((void**)&p->fx_flag_host, sizeof(unsigned), hipHostMallocDefault));
+    OIVA_TRY_HIP(hipMemcpyAsync(p->fx_flag_host, p->fx_state, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     const unsigned code = *p->fx_flag_host;
     if (code != 0)
-        return fail(OIVA_ERR_STATE, "the exchange inside the activation kernel gave up waiting for a rank's partial powers (workgroup " +
+        return fail_with(OIVA_ERR_STATE, "the exchange inside the activation kernel gave up waiting for a rank's partial powers (workgroup " +
                                         std::to_string(code - 1) + "): the state of this plan is undefined (oiva_plan_restore_w brings back the "
                                         "demixing matrices saved by oiva_plan_save_w; oiva_plan_fused_connect(p, NULL) clears the condition)");
     return OIVA_OK;
 }
 
 int oiva_plan_sync(oiva_plan* p) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     return check_fused(p);
 }
 
 int oiva_plan_save_w(oiva_plan* p) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(p->have_w, OIVA_ERR_STATE, "demixing matrix not set");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p->have_w, OIVA_ERR_STATE, "demixing matrix not set");
     DeviceGuard guard(p->device);
     const size_t n = (size_t)p->F * p->M * p->M;
-    if (!p->ck_what) HIP_TRY(dev_malloc((void**)&p->ck_what, n * sizeof(float2)));
-    if (!p->ck_what64) HIP_TRY(dev_malloc((void**)&p->ck_what64, n * sizeof(double2)));
+    if (!p->ck_what) OIVA_TRY_HIP(dev_malloc((void**)&p->ck_what, n * sizeof(float2)));
+    if (!p->ck_what64) OIVA_TRY_HIP(dev_malloc((void**)&p->ck_what64, n * sizeof(double2)));
     // on the plan's stream: ordered behind the iterations already queued, in front of the ones that follow
-    HIP_TRY(hipMemcpyAsync(p->ck_what, p->What, n * sizeof(float2), hipMemcpyDeviceToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->ck_what64, p->What64, n * sizeof(double2), hipMemcpyDeviceToDevice, p->stream));
+    OIVA_TRY_HIP(hipMemcpyAsync(p->ck_what, p->What, n * sizeof(float2), hipMemcpyDeviceToDevice, p->stream));
+    OIVA_TRY_HIP(hipMemcpyAsync(p->ck_what64, p->What64, n * sizeof(double2), hipMemcpyDeviceToDevice, p->stream));
     p->ck_what64_valid = p->what64_valid;
     p->ck_valid = true;
     return OIVA_OK;
 }
 
 int oiva_plan_restore_w(oiva_plan* p) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(p->ck_valid, OIVA_ERR_STATE, "nothing saved (oiva_plan_save_w)");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p->ck_valid, OIVA_ERR_STATE, "nothing saved (oiva_plan_save_w)");
     DeviceGuard guard(p->device);
     const size_t n = (size_t)p->F * p->M * p->M;
-    HIP_TRY(hipMemcpyAsync(p->What, p->ck_what, n * sizeof(float2), hipMemcpyDeviceToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->What64, p->ck_what64, n * sizeof(double2), hipMemcpyDeviceToDevice, p->stream));
+    OIVA_TRY_HIP(hipMemcpyAsync(p->What, p->ck_what, n * sizeof(float2), hipMemcpyDeviceToDevice, p->stream));
+    OIVA_TRY_HIP(hipMemcpyAsync(p->What64, p->ck_what64, n * sizeof(double2), hipMemcpyDeviceToDevice, p->stream));
     p->what64_valid = p->ck_what64_valid;
     p->wscale_pending = false;
     p->have_w = true;
@@ -1472,43 +1368,43 @@ int oiva_plan_restore_w(oiva_plan* p) {
 
 static int fused_setup(oiva_plan* p) {
     const size_t words = 16 + (size_t)rsum_blocks(p->T) * p->K;
-    if (!p->fx_state) HIP_TRY(dev_malloc((void**)&p->fx_state, words * sizeof(unsigned)));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemset(p->fx_state, 0, words * sizeof(unsigned)));
+    if (!p->fx_state) OIVA_TRY_HIP(dev_malloc((void**)&p->fx_state, words * sizeof(unsigned)));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemset(p->fx_state, 0, words * sizeof(unsigned)));
     return drop_graph(p);                       // captured graphs hold the other activation kernel
 }
 
 int oiva_plan_fused_connect(oiva_plan* p, oiva_xchg* x) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(!p->fx_loopback, OIVA_ERR_STATE, "the plan runs the loop-back exchange (oiva_plan_fused_loopback(p, 0) switches it off)");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(!p->fx_loopback, OIVA_ERR_STATE, "the plan runs the loop-back exchange (oiva_plan_fused_loopback(p, 0) switches it off)");
     DeviceGuard guard(p->device);
     if (!x) {
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
         p->fx_on = false;
         p->fx_world = 1;
         p->fx_rank = 0;
         for (auto& g : p->fx_gath) g = nullptr;
-        if (p->fx_state) HIP_TRY(hipMemset(p->fx_state, 0, sizeof(unsigned)));     // a wait that gave up is history now
+        if (p->fx_state) OIVA_TRY_HIP(hipMemset(p->fx_state, 0, sizeof(unsigned)));     // a wait that gave up is history now
         return drop_graph(p);
     }
     char* peers[OIVA_XCHG_MAX_RANKS];
     int rank = 0, world = 1;
     size_t slot = 0;
-    NEED(xchg_peers(x, peers, &rank, &world, &slot) == 0, OIVA_ERR_STATE, "exchange not connected");
+    OIVA_NEED(xchg_peers(x, peers, &rank, &world, &slot) == 0, OIVA_ERR_STATE, "exchange not connected");
     // slot = nblk * T * K * 8 bytes: nblk block sums per rank (every rank the same; 1 = the rank's sum)
     const size_t word_bytes = (size_t)p->T * p->K * 8;
-    NEED(slot % word_bytes == 0 && slot / word_bytes >= 1 && slot / word_bytes <= (size_t)kCanonBlocks, OIVA_ERR_ARG,
-         "exchange slot size must be nblk * T * K * 8 bytes, nblk = 1 ... 8 block sums per rank");
+    OIVA_NEED(slot % word_bytes == 0 && slot / word_bytes >= 1 && slot / word_bytes <= (size_t)kCanonBlocks, OIVA_ERR_ARG,
+              "exchange slot size must be nblk * T * K * 8 bytes, nblk = 1 ... 8 block sums per rank");
     const int nblk = (int)(slot / word_bytes);
-    NEED(p->pw.nb % nblk == 0, OIVA_ERR_ARG, "the plan's 64-bin parts do not divide into that many blocks");
-    NEED((world - 1) * nblk <= kCanonBlocks, OIVA_ERR_ARG, "the activation kernel polls at most 8 words of the other ranks per frame and source (9 ranks of one sum each)");
+    OIVA_NEED(p->pw.nb % nblk == 0, OIVA_ERR_ARG, "the plan's 64-bin parts do not divide into that many blocks");
+    OIVA_NEED((world - 1) * nblk <= kCanonBlocks, OIVA_ERR_ARG, "the activation kernel polls at most 8 words of the other ranks per frame and source (9 ranks of one sum each)");
     int rc = fused_setup(p);
     if (rc) return rc;
     // the epochs of this connection start at 1 again: words left in the own gather buffer by an earlier connection (tagged
     // 1 ... n) must not pass for current ones.  The other ranks store into this buffer from their first iteration on, so
     // the callers rendezvous between connecting and iterating (include/overiva_hip.h; sharded.py does).
-    HIP_TRY(hipMemset(peers[rank], 0, (size_t)2 * world * slot));
-    HIP_TRY(hipDeviceSynchronize());
+    OIVA_TRY_HIP(hipMemset(peers[rank], 0, (size_t)2 * world * slot));
+    OIVA_TRY_HIP(hipDeviceSynchronize());
     p->fx_nblk_own = p->fx_nblk_peer = nblk;
     for (int r = 0; r < OIVA_XCHG_MAX_RANKS; ++r) p->fx_gath[r] = peers[r];
     p->fx_rank = rank;
@@ -1518,12 +1414,12 @@ int oiva_plan_fused_connect(oiva_plan* p, oiva_xchg* x) {
 }
 
 int oiva_plan_fused_loopback(oiva_plan* p, int world) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(world >= 0 && world <= OIVA_XCHG_MAX_RANKS, OIVA_ERR_ARG, "bad number of ranks");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(world >= 0 && world <= OIVA_XCHG_MAX_RANKS, OIVA_ERR_ARG, "bad number of ranks");
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     if (p->fx_loop_buf) {
-        HIP_TRY(hipFree(p->fx_loop_buf));
+        OIVA_TRY_HIP(hipFree(p->fx_loop_buf));
         p->fx_loop_buf = nullptr;
     }
     if (p->fx_loopback) {
@@ -1534,17 +1430,17 @@ int oiva_plan_fused_loopback(oiva_plan* p, int world) {
         if (rc) return rc;
     }
     if (world <= 1) return OIVA_OK;
-    NEED(!p->fx_on, OIVA_ERR_STATE, "the plan is connected to other ranks (oiva_plan_fused_connect(p, NULL) disconnects)");
-    NEED(p->F == p->F_total, OIVA_ERR_STATE, "loop-back plays the other ranks with zeros: the plan must own all bins");
+    OIVA_NEED(!p->fx_on, OIVA_ERR_STATE, "the plan is connected to other ranks (oiva_plan_fused_connect(p, NULL) disconnects)");
+    OIVA_NEED(p->F == p->F_total, OIVA_ERR_STATE, "loop-back plays the other ranks with zeros: the plan must own all bins");
     // own blocks: those of the single-GPU sum (the result keeps its bits); per phantom rank the words a real rank of that
     // world would send: 8 / world blocks
     const int bsz = (p->pw.nb + kCanonBlocks - 1) / kCanonBlocks;
     p->fx_nblk_own = (p->pw.nb + bsz - 1) / bsz;
     p->fx_nblk_peer = std::max(1, kCanonBlocks / world);
-    NEED((world - 1) * p->fx_nblk_peer <= kCanonBlocks, OIVA_ERR_ARG, "at most 9 ranks");
+    OIVA_NEED((world - 1) * p->fx_nblk_peer <= kCanonBlocks, OIVA_ERR_ARG, "at most 9 ranks");
     const size_t bytes = (size_t)2 * world * p->fx_nblk_peer * p->T * p->K * 8;
-    HIP_TRY(hipExtMallocWithFlags((void**)&p->fx_loop_buf, bytes, hipDeviceMallocFinegrained));
-    HIP_TRY(hipMemset(p->fx_loop_buf, 0, bytes));
+    OIVA_TRY_HIP(hipExtMallocWithFlags((void**)&p->fx_loop_buf, bytes, hipDeviceMallocFinegrained));
+    OIVA_TRY_HIP(hipMemset(p->fx_loop_buf, 0, bytes));
     int rc = fused_setup(p);
     if (rc) return rc;
     for (int r = 0; r < world; ++r) p->fx_gath[r] = p->fx_loop_buf;
@@ -1556,27 +1452,27 @@ int oiva_plan_fused_loopback(oiva_plan* p, int world) {
 }
 
 int oiva_plan_fused_debug(oiva_plan* p, int timeout_ms, int stall) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
     p->fx_timeout_ms = timeout_ms;
     p->fx_stall = stall;
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     return drop_graph(p);                       // (both are kernel arguments of captured launches)
 }
 
 int oiva_plan_iterate_timed(oiva_plan* p, int n, float* total_ms, float* per_kernel_ms) {
     int rc = check_ready(p);
     if (rc) return rc;
-    NEED(n >= 1 && total_ms, OIVA_ERR_ARG, "bad arguments");
-    NEED(p->F == p->F_total, OIVA_ERR_STATE, "timed iterate needs a plan that owns all bins");
+    OIVA_NEED(n >= 1 && total_ms, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(p->F == p->F_total, OIVA_ERR_STATE, "timed iterate needs a plan that owns all bins");
     DeviceGuard guard(p->device);
     hipEvent_t e_begin = p->ev[0], e_end = p->ev[1];
     if (!per_kernel_ms) {
-        HIP_TRY(hipEventRecord(e_begin, p->stream));
+        OIVA_TRY_HIP(hipEventRecord(e_begin, p->stream));
         if ((rc = oiva_plan_iterate(p, n))) return rc;
-        HIP_TRY(hipEventRecord(e_end, p->stream));
-        HIP_TRY(hipEventSynchronize(e_end));
-        HIP_TRY(hipEventElapsedTime(total_ms, e_begin, e_end));
+        OIVA_TRY_HIP(hipEventRecord(e_end, p->stream));
+        OIVA_TRY_HIP(hipEventSynchronize(e_end));
+        OIVA_TRY_HIP(hipEventElapsedTime(total_ms, e_begin, e_end));
         return OIVA_OK;
     }
     // per-kernel: an event before every launch and one after the last launch of each iteration, all
@@ -1593,7 +1489,7 @@ int oiva_plan_iterate_timed(oiva_plan* p, int n, float* total_ms, float* per_ker
         hipError_t err = hipEventCreate(&e);
         if (err != hipSuccess) {
             destroy();
-            return fail(OIVA_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(err));
+            return fail_with(OIVA_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(err));
         }
     }
     std::vector<hipEvent_t> kev((size_t)2 * n, nullptr);
@@ -1640,21 +1536,21 @@ int oiva_plan_iterate_timed(oiva_plan* p, int n, float* total_ms, float* per_ker
     for (hipEvent_t e : kev)
         if (e) (void)hipEventDestroy(e);
     if (rc) return rc;
-    HIP_TRY(err);
+    OIVA_TRY_HIP(err);
     return OIVA_OK;
 }
 
 int oiva_plan_get_cov_splits(oiva_plan* p, int* nsplit) {
-    NEED(p && nsplit, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && nsplit, OIVA_ERR_ARG, "null argument");
     *nsplit = p->cov.nsplit;
     return OIVA_OK;
 }
 
 int oiva_plan_set_cov_splits(oiva_plan* p, int nsplit) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(nsplit >= 0 && nsplit <= p->T, OIVA_ERR_ARG, "bad split count");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(nsplit >= 0 && nsplit <= p->T, OIVA_ERR_ARG, "bad split count");
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     int rc = drop_graph(p);
     if (rc) return rc;
     choose_cov_geom(p, nsplit);
@@ -1662,9 +1558,9 @@ int oiva_plan_set_cov_splits(oiva_plan* p, int nsplit) {
 }
 
 int oiva_plan_set_cov_quad(oiva_plan* p, int enable, int* active) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     int rc = drop_graph(p);
     if (rc) return rc;
     p->cov_quad_on = enable != 0;
@@ -1674,10 +1570,10 @@ int oiva_plan_set_cov_quad(oiva_plan* p, int enable, int* active) {
 }
 
 int oiva_plan_set_fuse_cov_update(oiva_plan* p, int enable, int* active) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
     if (enable >= 0) {
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
         int rc = drop_graph(p);
         if (rc) return rc;
         p->fuse_cov_update = enable != 0;
@@ -1687,9 +1583,9 @@ int oiva_plan_set_fuse_cov_update(oiva_plan* p, int enable, int* active) {
 }
 
 int oiva_plan_set_cov_hmfma(oiva_plan* p, int enable) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     int rc = drop_graph(p);
     if (rc) return rc;
     p->cov_hmfma_on = enable != 0;
@@ -1698,10 +1594,10 @@ int oiva_plan_set_cov_hmfma(oiva_plan* p, int enable) {
 }
 
 int oiva_plan_set_pow_splits(oiva_plan* p, int nsplit) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(nsplit >= 0 && nsplit <= p->T, OIVA_ERR_ARG, "bad split count");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(nsplit >= 0 && nsplit <= p->T, OIVA_ERR_ARG, "bad split count");
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     int rc = drop_graph(p);
     if (rc) return rc;
     choose_pow_geom(p, nsplit);
@@ -1709,9 +1605,9 @@ int oiva_plan_set_pow_splits(oiva_plan* p, int nsplit) {
 }
 
 int oiva_plan_set_power_reverse(oiva_plan* p, int enable) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     int rc = drop_graph(p);
     if (rc) return rc;
     p->power_reverse = enable < 0 ? 0 : enable > 2 ? 2 : enable;
@@ -1719,7 +1615,7 @@ int oiva_plan_set_power_reverse(oiva_plan* p, int enable) {
 }
 
 int oiva_plan_use_graph(oiva_plan* p, int enable) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
     p->use_graph = enable ? 1 : 0;
     if (!enable) return drop_graph(p);
@@ -1728,10 +1624,10 @@ int oiva_plan_use_graph(oiva_plan* p, int enable) {
 }
 
 int oiva_plan_set_precision(oiva_plan* p, int flags) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED((flags & ~(OIVA_PREC_UPDATE_F64 | OIVA_PREC_UPDATE_ROWS | OIVA_PREC_COV_F64)) == 0, OIVA_ERR_ARG, "unknown precision flag");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED((flags & ~(OIVA_PREC_UPDATE_F64 | OIVA_PREC_UPDATE_ROWS | OIVA_PREC_COV_F64)) == 0, OIVA_ERR_ARG, "unknown precision flag");
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     int rc = drop_graph(p);
     if (rc) return rc;
     if ((flags & OIVA_PREC_UPDATE_F64) && p->have_w && !p->what64_valid) {
@@ -1752,14 +1648,14 @@ int oiva_plan_set_precision(oiva_plan* p, int flags) {
 
 // ---- X-resident iteration ------------------------------------------------------------------------------
 int oiva_plan_set_resident(oiva_plan* p, int enable) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     if (!enable) {
         p->res_on = false;
         return OIVA_OK;
     }
-    NEED(p->res_ok, OIVA_ERR_ARG,
-         "shape does not qualify for the X-resident iteration (4 or 8 channels, 1 or 2 sources with background channels, "
-         "16 bins x <= 256 frames per compute unit)");
+    OIVA_NEED(p->res_ok, OIVA_ERR_ARG,
+              "shape does not qualify for the X-resident iteration (4 or 8 channels, 1 or 2 sources with background channels, "
+              "16 bins x <= 256 frames per compute unit)");
     DeviceGuard guard(p->device);
     int rc = resident_alloc(p);
     if (rc) return rc;
@@ -1768,15 +1664,15 @@ int oiva_plan_set_resident(oiva_plan* p, int enable) {
 }
 
 int oiva_plan_set_resident_splits(oiva_plan* p, int nsplit) {
-    NEED(p && nsplit >= 0, OIVA_ERR_ARG, "bad arguments");
-    NEED(!p->res_on, OIVA_ERR_STATE, "switch the resident iteration off before changing its geometry");
+    OIVA_NEED(p && nsplit >= 0, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(!p->res_on, OIVA_ERR_STATE, "switch the resident iteration off before changing its geometry");
     DeviceGuard guard(p->device);
     ResidentGeom g;
     const bool ok = resident_geometry(p->T, p->F, p->M, p->K, p->n_cu, nsplit, &g);
-    NEED(ok || nsplit == 0, OIVA_ERR_ARG, "the shape does not fit on chip with that many frame splits");
+    OIVA_NEED(ok || nsplit == 0, OIVA_ERR_ARG, "the shape does not fit on chip with that many frame splits");
     if (p->res_block) {                        // buffers were sized for the old geometry
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        HIP_TRY(hipFree(p->res_block));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipFree(p->res_block));
         p->res_block = nullptr;
     }
     p->res_ok = ok;
@@ -1785,13 +1681,13 @@ int oiva_plan_set_resident_splits(oiva_plan* p, int nsplit) {
 }
 
 int oiva_plan_resident_loopback(oiva_plan* p, int world) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(world >= 0 && world <= OIVA_XCHG_MAX_RANKS, OIVA_ERR_ARG, "bad number of ranks");
-    NEED(!p->res_on, OIVA_ERR_STATE, "switch the resident iteration off before changing its exchange");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(world >= 0 && world <= OIVA_XCHG_MAX_RANKS, OIVA_ERR_ARG, "bad number of ranks");
+    OIVA_NEED(!p->res_on, OIVA_ERR_STATE, "switch the resident iteration off before changing its exchange");
     DeviceGuard guard(p->device);
     if (p->res_loop_buf) {
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        HIP_TRY(hipFree(p->res_loop_buf));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipFree(p->res_loop_buf));
         p->res_loop_buf = nullptr;
     }
     p->res_loopback = false;
@@ -1799,40 +1695,40 @@ int oiva_plan_resident_loopback(oiva_plan* p, int world) {
     p->res_rank = 0;
     for (auto& g : p->res_gath) g = nullptr;
     if (world <= 1) return OIVA_OK;
-    NEED(p->res_ok, OIVA_ERR_ARG, "shape does not qualify for the X-resident iteration");
-    NEED(p->F == p->F_total, OIVA_ERR_STATE, "loop-back plays the other ranks with zeros: the plan must own all bins");
+    OIVA_NEED(p->res_ok, OIVA_ERR_ARG, "shape does not qualify for the X-resident iteration");
+    OIVA_NEED(p->F == p->F_total, OIVA_ERR_STATE, "loop-back plays the other ranks with zeros: the plan must own all bins");
     // the gather buffer of the multi-GPU exchange, same kind of memory (fine-grained, system-scope atomics), but nobody else
     // maps it: [2 (epoch parity)][world][NS * TW][K] floats
     const size_t bytes = (size_t)2 * world * p->rg.NS * p->rg.TW * p->K * sizeof(float);
-    HIP_TRY(hipExtMallocWithFlags((void**)&p->res_loop_buf, bytes, hipDeviceMallocFinegrained));
-    HIP_TRY(hipMemset(p->res_loop_buf, 0, bytes));
+    OIVA_TRY_HIP(hipExtMallocWithFlags((void**)&p->res_loop_buf, bytes, hipDeviceMallocFinegrained));
+    OIVA_TRY_HIP(hipMemset(p->res_loop_buf, 0, bytes));
     for (int r = 0; r < world; ++r) p->res_gath[r] = p->res_loop_buf;
     p->res_world = world;
     p->res_loopback = true;
     if (p->res_block) {                        // epochs restart with the fresh buffer
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        HIP_TRY(hipMemset(p->res_block, 0, p->res_block_bytes));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipMemset(p->res_block, 0, p->res_block_bytes));
         p->res_epoch = 0;
     }
     return OIVA_OK;
 }
 
 int oiva_plan_resident_connect(oiva_plan* p, oiva_xchg* x) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(!p->res_loopback, OIVA_ERR_STATE, "the plan runs the loop-back exchange (oiva_plan_resident_loopback(p, 0) switches it off)");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(!p->res_loopback, OIVA_ERR_STATE, "the plan runs the loop-back exchange (oiva_plan_resident_loopback(p, 0) switches it off)");
     if (!x) {                                  // back to a single rank
         p->res_world = 1;
         p->res_rank = 0;
         for (auto& g : p->res_gath) g = nullptr;
         return OIVA_OK;
     }
-    NEED(p->res_ok, OIVA_ERR_ARG, "shape does not qualify for the X-resident iteration");
+    OIVA_NEED(p->res_ok, OIVA_ERR_ARG, "shape does not qualify for the X-resident iteration");
     char* peers[OIVA_XCHG_MAX_RANKS];
     int rank = 0, world = 1;
     size_t slot = 0;
-    NEED(xchg_peers(x, peers, &rank, &world, &slot) == 0, OIVA_ERR_STATE, "exchange not connected");
+    OIVA_NEED(xchg_peers(x, peers, &rank, &world, &slot) == 0, OIVA_ERR_STATE, "exchange not connected");
     const size_t want = (size_t)p->rg.NS * p->rg.TW * p->K * sizeof(float);
-    NEED(slot == want, OIVA_ERR_ARG, "exchange slot size must be frame_splits * frames_per_split * K * 4 bytes of THIS plan "
+    OIVA_NEED(slot == want, OIVA_ERR_ARG, "exchange slot size must be frame_splits * frames_per_split * K * 4 bytes of THIS plan "
                                      "(every rank must run the same split geometry)");
     for (int r = 0; r < OIVA_XCHG_MAX_RANKS; ++r) p->res_gath[r] = peers[r];
     p->res_rank = rank;
@@ -1841,7 +1737,7 @@ int oiva_plan_resident_connect(oiva_plan* p, oiva_xchg* x) {
 }
 
 int oiva_plan_resident_info(oiva_plan* p, int* info) {
-    NEED(p && info, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && info, OIVA_ERR_ARG, "null argument");
     const ResidentGeom& g = p->rg;
     const int v[OIVA_RESIDENT_INFO] = {p->res_ok ? 1 : 0, p->res_on ? 1 : 0, g.NB, g.NS, g.TW, g.J, g.JR, g.lds_bytes,
                                        p->res_last_code, p->res_launches, p->res_fallbacks, g.J * kBlock * p->M * 8};
@@ -1850,15 +1746,15 @@ int oiva_plan_resident_info(oiva_plan* p, int* info) {
 }
 
 int oiva_plan_resident_phases(oiva_plan* p, double* phase_us, int* n_iter) {
-    NEED(p && phase_us && n_iter, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && phase_us && n_iter, OIVA_ERR_ARG, "null argument");
     for (int i = 0; i < OIVA_RESIDENT_PHASES; ++i) phase_us[i] = 0.;
     *n_iter = 0;
     if (!p->res_stamps || p->res_stamped <= 0) return OIVA_OK;
     DeviceGuard guard(p->device);
     const int n = p->res_stamped;
     std::vector<unsigned long long> st((size_t)n * kResidentStamps);
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemcpy(st.data(), p->res_stamps, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemcpy(st.data(), p->res_stamps, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     static_assert(OIVA_RESIDENT_PHASES <= kResidentStamps - 1, "one phase between consecutive stamps");
     for (int it = 0; it < n; ++it)
         for (int i = 0; i < OIVA_RESIDENT_PHASES; ++i)
@@ -1868,21 +1764,21 @@ int oiva_plan_resident_phases(oiva_plan* p, double* phase_us, int* n_iter) {
 }
 
 int oiva_plan_resident_trace(oiva_plan* p, int enable, unsigned long long* stamps_host, int* n_wg, int* n_iter) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
     p->res_trace = enable != 0;
     if (n_wg) *n_wg = p->rg.NB * p->rg.NS;
     if (n_iter) *n_iter = p->res_trace_buf ? p->res_trace_iters : 0;
     if (stamps_host && p->res_trace_buf) {
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        HIP_TRY(hipMemcpy(stamps_host, p->res_trace_buf,
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipMemcpy(stamps_host, p->res_trace_buf,
                           (size_t)p->rg.NB * p->rg.NS * p->res_trace_iters * kResidentStamps * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     }
     return OIVA_OK;
 }
 
 int oiva_plan_resident_debug(oiva_plan* p, int timeout_ms, int stall_block) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     p->res_timeout_ms = timeout_ms;
     p->res_stall = stall_block;
     p->res_stall_iter = 0;
@@ -1890,7 +1786,7 @@ int oiva_plan_resident_debug(oiva_plan* p, int timeout_ms, int stall_block) {
 }
 
 int oiva_plan_resident_debug_from(oiva_plan* p, int timeout_ms, int stall_block, int first_stalled_iteration) {
-    NEED(p && first_stalled_iteration >= 0, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(p && first_stalled_iteration >= 0, OIVA_ERR_ARG, "bad arguments");
     p->res_timeout_ms = timeout_ms;
     p->res_stall = stall_block;
     p->res_stall_iter = first_stalled_iteration;
@@ -1899,43 +1795,29 @@ int oiva_plan_resident_debug_from(oiva_plan* p, int timeout_ms, int stall_block,
 
 // ---- OGIVE (reference ive.py:33-256) ----------------------------------------------------------------
 int oiva_plan_ogive_begin(oiva_plan* p, int update_mode, int model) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(p->M <= kNarrowMax, OIVA_ERR_ARG, "OGIVE runs on 1..16 channels (its per-bin state is sized for them)");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p->M <= kNarrowMax, OIVA_ERR_ARG, "OGIVE runs on 1..16 channels (its per-bin state is sized for them)");
     int rc = check_ready(p);
     if (rc) return rc;
-    NEED(p->K == 1, OIVA_ERR_ARG, "OGIVE extracts one source: create the plan with K = 1");
-    NEED(p->F == p->F_total, OIVA_ERR_STATE, "OGIVE is not bin-sharded");
-    NEED(update_mode >= OIVA_OGIVE_DEMIX && update_mode <= OIVA_OGIVE_SWITCHING, OIVA_ERR_ARG, "unknown update mode");
-    NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
+    OIVA_NEED(p->K == 1, OIVA_ERR_ARG, "OGIVE extracts one source: create the plan with K = 1");
+    OIVA_NEED(p->F == p->F_total, OIVA_ERR_STATE, "OGIVE is not bin-sharded");
+    OIVA_NEED(update_mode >= OIVA_OGIVE_DEMIX && update_mode <= OIVA_OGIVE_SWITCHING, OIVA_ERR_ARG, "unknown update mode");
+    OIVA_NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
     DeviceGuard guard(p->device);
     const size_t F = p->F, M = p->M;
     if (p->og_bufs.empty()) {
-        hipError_t e = hipSuccess;
-        auto alloc = [&](size_t bytes) -> void* {
-            void* ptr = nullptr;
-            if (e == hipSuccess) e = dev_malloc(&ptr, bytes);
-            if (ptr) p->og_bufs.push_back(ptr);
-            return ptr;
-        };
-        p->og.CxInv = (double2*)alloc(F * M * M * sizeof(double2));
-        p->og.CxNorm = (double*)alloc(F * sizeof(double));
-        p->og.A = (double2*)alloc(F * M * sizeof(double2));
-        p->og.Delta = (double2*)alloc(F * M * sizeof(double2));
-        p->og.Lambda = (double*)alloc(F * sizeof(double));
-        p->og.DoA = (int*)alloc(F * sizeof(int));
-        p->og.DoW = (int*)alloc(F * sizeof(int));
-        p->og.Dnorm = (double*)alloc(F * sizeof(double));
-        p->og.ctrl = (int*)alloc(4 * sizeof(int));
-        p->og.maxdelta = (double*)alloc(2 * sizeof(double));
-        if (e != hipSuccess) return fail(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(e));
+        AllocChain alloc;
+        alloc.keep = &p->og_bufs;
+        alloc_ogive_state(p->og, F, M, alloc);
+        if (!alloc.ok()) return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
     }
     if (!p->what64_valid) {              // the step kernel reads and writes the complex128 copy of w
         std::vector<double2> wh;
         if ((rc = download_what(p, wh)) || (rc = upload_what(p, wh))) return rc;
     }
     if (p->og_graph) {                   // a cached chunk of epochs was captured for the previous update mode / model
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        HIP_TRY(hipGraphExecDestroy(p->og_graph));
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+        OIVA_TRY_HIP(hipGraphExecDestroy(p->og_graph));
         p->og_graph = nullptr;
     }
     p->og.Cx = p->Cx;
@@ -1943,7 +1825,7 @@ int oiva_plan_ogive_begin(oiva_plan* p, int update_mode, int model) {
     p->og.What64 = p->What64;
     p->og_mode = update_mode;
     p->og_model = model;
-    HIP_TRY(launch_ogive_init(p->stream, p->og, p->F, p->M, update_mode));
+    OIVA_TRY_HIP(launch_ogive_init(p->stream, p->og, p->F, p->M, update_mode));
     p->og_ready = true;
     return OIVA_OK;
 }
@@ -1952,22 +1834,22 @@ int oiva_plan_ogive_iterate(oiva_plan* p, int first_epoch, int n, double step_si
                             int* converged, double* max_delta) {
     int rc = check_ready(p);
     if (rc) return rc;
-    NEED(p->og_ready, OIVA_ERR_STATE, "call oiva_plan_ogive_begin first");
-    NEED(n >= 0 && first_epoch >= 0, OIVA_ERR_ARG, "negative epoch count");
+    OIVA_NEED(p->og_ready, OIVA_ERR_STATE, "call oiva_plan_ogive_begin first");
+    OIVA_NEED(n >= 0 && first_epoch >= 0, OIVA_ERR_ARG, "negative epoch count");
     DeviceGuard guard(p->device);
     int before[2] = {0, 0};
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemcpy(before, p->og.ctrl, sizeof(before), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemcpy(before, p->og.ctrl, sizeof(before), hipMemcpyDeviceToHost));
     const int amodel = p->og_model == OIVA_MODEL_LAPLACE ? kModelOgiveLaplace : OIVA_MODEL_GAUSS;
     auto epochs = [&](int e0, int count) -> int {
         for (int e = e0; e < e0 + count; ++e) {
-            if (p->og_mode == OIVA_OGIVE_SWITCHING && e % 10 == 0) HIP_TRY(launch_ogive_switch(p->stream, p->og, p->F, p->M));   // ive.py:192-193
+            if (p->og_mode == OIVA_OGIVE_SWITCHING && e % 10 == 0) OIVA_TRY_HIP(launch_ogive_switch(p->stream, p->og, p->F, p->M));   // ive.py:192-193
             int r = stage_power(p);                                                             // ive.py:196 + the norm of :210/:213
             if (r) return r;
-            HIP_TRY(launch_activation(p->stream, p->Ppart, p->pw.nb, p->R, p->T, 1, amodel, p->F));   // ive.py:209-217 (floor + 1/r in the consumer)
-            HIP_TRY(launch_cov(p->stream, p->X, p->X_pad, p->R, p->Plocal, p->wscale, p->model, /*raw: weights 1 / max(r, eps)*/ 1, p->Vpart,
+            OIVA_TRY_HIP(launch_activation(p->stream, p->Ppart, p->pw.nb, p->R, p->T, 1, amodel, p->F));   // ive.py:209-217 (floor + 1/r in the consumer)
+            OIVA_TRY_HIP(launch_cov(p->stream, p->X, p->X_pad, p->R, p->Plocal, p->wscale, p->model, /*raw: weights 1 / max(r, eps)*/ 1, p->Vpart,
                                p->cov_f64(), p->T, p->F, p->M, 1, p->cov));                    // ive.py:221-227
-            HIP_TRY(launch_ogive_step(p->stream, p->og, p->Vpart, p->vpart_f64(), p->cov.nsplit, p->T, p->F, p->M, step_size,
+            OIVA_TRY_HIP(launch_ogive_step(p->stream, p->og, p->Vpart, p->vpart_f64(), p->cov.nsplit, p->T, p->F, p->M, step_size,
                                       tol));                                                     // ive.py:228-246
         }
         return OIVA_OK;
@@ -1979,61 +1861,51 @@ int oiva_plan_ogive_iterate(oiva_plan* p, int first_epoch, int n, double step_si
         const int phase = first_epoch % 10;
         if (!p->og_graph || p->og_graph_n != n || p->og_graph_phase != phase || p->og_graph_mu != step_size ||
             p->og_graph_tol != tol) {
-            if (p->og_graph) HIP_TRY(hipGraphExecDestroy(p->og_graph));
+            if (p->og_graph) OIVA_TRY_HIP(hipGraphExecDestroy(p->og_graph));
             p->og_graph = nullptr;
-            hipGraph_t graph = nullptr;
-            HIP_TRY(hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal));
-            rc = epochs(phase, n);
-            hipError_t e = hipStreamEndCapture(p->stream, &graph);
-            if (rc) {
-                if (graph) (void)hipGraphDestroy(graph);
-                return rc;
-            }
-            HIP_TRY(e);
-            e = hipGraphInstantiate(&p->og_graph, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            HIP_TRY(e);
+            rc = capture_graph(p->stream, [&] { return epochs(phase, n); }, &p->og_graph, false);
+            if (rc) return rc;
             p->og_graph_n = n;
             p->og_graph_phase = phase;
             p->og_graph_mu = step_size;
             p->og_graph_tol = tol;
         }
-        HIP_TRY(hipGraphLaunch(p->og_graph, p->stream));
+        OIVA_TRY_HIP(hipGraphLaunch(p->og_graph, p->stream));
     } else if ((rc = epochs(first_epoch, n))) {
         return rc;
     }
     p->wscale_pending = false;
     int after[2] = {0, 0};
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemcpy(after, p->og.ctrl, sizeof(after), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemcpy(after, p->og.ctrl, sizeof(after), hipMemcpyDeviceToHost));
     if (epochs_run) *epochs_run = after[1] - before[1];
     if (converged) *converged = after[0];
-    if (max_delta) HIP_TRY(hipMemcpy(max_delta, p->og.maxdelta, sizeof(double), hipMemcpyDeviceToHost));
+    if (max_delta) OIVA_TRY_HIP(hipMemcpy(max_delta, p->og.maxdelta, sizeof(double), hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 
 // ---- test-only stage access -----------------------------------------------------------------------
 int oiva_test_set_rinv(oiva_plan* p, const float* rinv_host) {
-    NEED(p && rinv_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && rinv_host, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(p->device);
     // the device keeps r, not 1/r: store the reciprocal and tell the covariance pass to skip gamma
     std::vector<float> r((size_t)p->T * p->K);
     for (size_t i = 0; i < r.size(); ++i) r[i] = 1.f / rinv_host[i];
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemcpy(p->R, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemcpy(p->R, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
     p->raw_weights = 1;
     return OIVA_OK;
 }
 
 int oiva_test_get_rinv(oiva_plan* p, float* rinv_host, float* wscale_host) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     if (rinv_host) {
         // same formula as oiva::activation_weight on the r the device holds
         const int T = p->T, K = p->K;
         std::vector<float> r((size_t)T * K);
-        HIP_TRY(hipMemcpy(r.data(), p->R, r.size() * sizeof(float), hipMemcpyDeviceToHost));
+        OIVA_TRY_HIP(hipMemcpy(r.data(), p->R, r.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (int k = 0; k < K; ++k) {
             double s = 0.;
             for (int t = 0; t < T; ++t) s += (double)r[(size_t)t * K + k];
@@ -2045,13 +1917,13 @@ int oiva_test_get_rinv(oiva_plan* p, float* rinv_host, float* wscale_host) {
             }
         }
     }
-    if (wscale_host) HIP_TRY(hipMemcpy(wscale_host, p->wscale, (size_t)p->K * sizeof(float), hipMemcpyDeviceToHost));
+    if (wscale_host) OIVA_TRY_HIP(hipMemcpy(wscale_host, p->wscale, (size_t)p->K * sizeof(float), hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 
 int oiva_test_run_weighted_cov(oiva_plan* p) {
-    NEED(p, OIVA_ERR_ARG, "null plan");
-    NEED(p->have_x, OIVA_ERR_STATE, "X not set");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(p->have_x, OIVA_ERR_STATE, "X not set");
     DeviceGuard guard(p->device);
     int rc = ensure_pad(p);
     if (rc) return rc;
@@ -2059,16 +1931,16 @@ int oiva_test_run_weighted_cov(oiva_plan* p) {
 }
 
 int oiva_test_get_v(oiva_plan* p, void* V_host, int f64) {
-    NEED(p && V_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && V_host, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(p->device);
     const int F = p->F, M = p->M, K = p->K;
     const long long nfk = (long long)F * K * M * M;
-    HIP_TRY(launch_sum_parts(p->stream, p->Vpart, p->vpart_f64(), p->cov.nsplit, p->scratch_p, nfk, 1. / (double)p->T));
-    HIP_TRY(launch_unpack_herm(p->stream, p->scratch_p, p->scratch_c, f64 != 0, (long long)F * K, M));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(launch_sum_parts(p->stream, p->Vpart, p->vpart_f64(), p->cov.nsplit, p->scratch_p, nfk, 1. / (double)p->T));
+    OIVA_TRY_HIP(launch_unpack_herm(p->stream, p->scratch_p, p->scratch_c, f64 != 0, (long long)F * K, M));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     const size_t esz = f64 ? sizeof(double2) : sizeof(float2);
     std::vector<char> fk((size_t)nfk * esz);
-    HIP_TRY(hipMemcpy(fk.data(), p->scratch_c, fk.size(), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(hipMemcpy(fk.data(), p->scratch_c, fk.size(), hipMemcpyDeviceToHost));
     // device order is [F][K][M][M]; the oracle's is (K, F, M, M)
     char* out = (char*)V_host;
     const size_t mm = (size_t)M * M * esz;
@@ -2086,7 +1958,7 @@ int oiva_test_run_update(oiva_plan* p) {
 }
 
 int oiva_test_get_what(oiva_plan* p, void* What_host, int f64) {
-    NEED(p && What_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && What_host, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(p->device);
     std::vector<double2> wh;
     int rc = download_what(p, wh);
@@ -2101,7 +1973,7 @@ int oiva_test_get_what(oiva_plan* p, void* What_host, int f64) {
 }
 
 int oiva_test_set_what(oiva_plan* p, const void* What_host, int f64) {
-    NEED(p && What_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && What_host, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(p->device);
     std::vector<double2> wh((size_t)p->F * p->M * p->M);
     if (f64) {
@@ -2120,7 +1992,7 @@ int oiva_test_set_what(oiva_plan* p, const void* What_host, int f64) {
 int oiva_test_time_stage(oiva_plan* p, int stage, int reps, float* avg_ms) {
     int rc = check_ready(p);
     if (rc) return rc;
-    NEED(reps >= 1 && avg_ms && stage >= 0 && stage < OIVA_N_STAGES, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(reps >= 1 && avg_ms && stage >= 0 && stage < OIVA_N_STAGES, OIVA_ERR_ARG, "bad arguments");
     DeviceGuard guard(p->device);
     auto run = [&]() -> int {
         switch (stage) {
@@ -2131,45 +2003,45 @@ int oiva_test_time_stage(oiva_plan* p, int stage, int reps, float* avg_ms) {
         }
     };
     if ((rc = run())) return rc;  // warm
-    HIP_TRY(hipEventRecord(p->ev[0], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[0], p->stream));
     for (int i = 0; i < reps; ++i)
         if ((rc = run())) return rc;
-    HIP_TRY(hipEventRecord(p->ev[1], p->stream));
-    HIP_TRY(hipEventSynchronize(p->ev[1]));
+    OIVA_TRY_HIP(hipEventRecord(p->ev[1], p->stream));
+    OIVA_TRY_HIP(hipEventSynchronize(p->ev[1]));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
+    OIVA_TRY_HIP(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
     *avg_ms = ms / reps;
     return OIVA_OK;
 }
 
 int oiva_test_run_power(oiva_plan* p, float* p_host) {
-    NEED(p && p_host, OIVA_ERR_ARG, "null argument");
-    NEED(p->have_x && p->have_w, OIVA_ERR_STATE, "X / W not set");
+    OIVA_NEED(p && p_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p->have_x && p->have_w, OIVA_ERR_STATE, "X / W not set");
     DeviceGuard guard(p->device);
     int rc = stage_power(p);
     if (rc) return rc;
     const size_t n = (size_t)p->T * p->K;
-    HIP_TRY(launch_sum_parts(p->stream, p->Ppart, false, p->pw.nb, p->scratch_p, (long long)n, 1.));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(launch_sum_parts(p->stream, p->Ppart, false, p->pw.nb, p->scratch_p, (long long)n, 1.));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     std::vector<double> sum(n);
-    HIP_TRY(hipMemcpy(sum.data(), p->scratch_p, n * sizeof(double), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(hipMemcpy(sum.data(), p->scratch_p, n * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) p_host[i] = (float)sum[i];
     return OIVA_OK;
 }
 
 int oiva_test_get_ppart(oiva_plan* p, float* parts_host, int* nparts) {
-    NEED(p && nparts, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(p && nparts, OIVA_ERR_ARG, "null argument");
     *nparts = p->pw.nb;
     if (!parts_host) return OIVA_OK;
     DeviceGuard guard(p->device);
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemcpy(parts_host, p->Ppart, (size_t)p->pw.nb * p->T * p->K * sizeof(float), hipMemcpyDeviceToHost));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipMemcpy(parts_host, p->Ppart, (size_t)p->pw.nb * p->T * p->K * sizeof(float), hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 
 int oiva_test_power_order(int nsplit, int tcp, int cov_splits, int cov_tc, int* order) {
-    NEED(order && nsplit >= 1 && tcp >= 1 && cov_splits >= 1 && cov_tc >= 1, OIVA_ERR_ARG, "bad arguments");
-    NEED(cov_splits <= kPowOrderMaxSplits, OIVA_ERR_ARG, "more covariance splits than the order table holds");
+    OIVA_NEED(order && nsplit >= 1 && tcp >= 1 && cov_splits >= 1 && cov_tc >= 1, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(cov_splits <= kPowOrderMaxSplits, OIVA_ERR_ARG, "more covariance splits than the order table holds");
     const PowOrder o = make_pow_order(nsplit, tcp, cov_splits, cov_tc);
     for (int y = 0; y < nsplit; ++y) order[y] = power_chunk_tail_first(y, nsplit, o);
     return OIVA_OK;

@@ -20,27 +20,12 @@
 #include <algorithm>
 #include <string>
 
+#include "host_util.h"
 #include "oiva_internal.h"
 
 using namespace oiva;
 
 namespace {
-
-int sfail(int code, const std::string& msg) { return oiva::fail_with(code, msg); }   // oiva_last_error() reports it
-#define S_HIP(expr)                                                                                       \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return sfail(OIVA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define S_FFT(expr)                                                                                  \
-    do {                                                                                             \
-        hipfftResult r_ = (expr);                                                                    \
-        if (r_ != HIPFFT_SUCCESS) return sfail(OIVA_ERR_HIP, std::string(#expr) + ": hipfft error " + std::to_string((int)r_)); \
-    } while (0)
-#define S_NEED(cond, code, msg)               \
-    do {                                      \
-        if (!(cond)) return sfail(code, msg); \
-    } while (0)
 
 // frames[(t*C + c)*L + n] = win[n] * x[(t*hop - (L-hop) + n), c]   (zero before the first sample)
 __global__ __launch_bounds__(kBlock) void frame_kernel(const float* __restrict__ x, const float* __restrict__ win,
@@ -119,15 +104,15 @@ extern "C" {
 
 int oiva_stft_create(oiva_stft** out, int device, int n_samples, int n_chan, int frame, int hop, const float* win_a,
                      const float* win_s) {
-    S_NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
+    OIVA_NEED(out != nullptr, OIVA_ERR_ARG, "null out pointer");
     *out = nullptr;
-    S_NEED(n_chan >= 1 && frame >= 2 && frame % 2 == 0, OIVA_ERR_ARG, "frame must be even, n_chan >= 1");
-    S_NEED(hop >= 1 && hop <= frame, OIVA_ERR_ARG, "hop must be in 1..frame");
-    S_NEED(n_samples >= hop, OIVA_ERR_ARG, "fewer samples than one hop");
+    OIVA_NEED(n_chan >= 1 && frame >= 2 && frame % 2 == 0, OIVA_ERR_ARG, "frame must be even, n_chan >= 1");
+    OIVA_NEED(hop >= 1 && hop <= frame, OIVA_ERR_ARG, "hop must be in 1..frame");
+    OIVA_NEED(n_samples >= hop, OIVA_ERR_ARG, "fewer samples than one hop");
     int ndev = 0;
-    S_HIP(hipGetDeviceCount(&ndev));
-    S_NEED(device >= 0 && device < ndev, OIVA_ERR_ARG, "no such device");
-    S_HIP(hipSetDevice(device));
+    OIVA_TRY_HIP(hipGetDeviceCount(&ndev));
+    OIVA_NEED(device >= 0 && device < ndev, OIVA_ERR_ARG, "no such device");
+    DeviceGuard guard(device);
     oiva_stft* p = new oiva_stft();
     p->device = device;
     p->n_samples = n_samples;
@@ -136,26 +121,24 @@ int oiva_stft_create(oiva_stft** out, int device, int n_samples, int n_chan, int
     p->hop = hop;
     p->T = n_samples / hop;
     p->F = frame / 2 + 1;
-    hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+    AllocChain alloc;
+    alloc.err = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
     const size_t nx = (size_t)std::max(n_samples, p->T * hop) * n_chan;
-    auto alloc = [&](void** ptr, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(ptr, bytes);
-    };
-    alloc((void**)&p->x, nx * sizeof(float));
-    alloc((void**)&p->frames, (size_t)p->T * n_chan * frame * sizeof(float));
-    alloc((void**)&p->spec, (size_t)p->T * n_chan * p->F * sizeof(float2));
-    alloc((void**)&p->X, (size_t)p->T * n_chan * p->F * sizeof(float2));
+    alloc(&p->x, nx * sizeof(float));
+    alloc(&p->frames, (size_t)p->T * n_chan * frame * sizeof(float));
+    alloc(&p->spec, (size_t)p->T * n_chan * p->F * sizeof(float2));
+    alloc(&p->X, (size_t)p->T * n_chan * p->F * sizeof(float2));
     if (win_a) {
-        alloc((void**)&p->win_a, frame * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(p->win_a, win_a, frame * sizeof(float), hipMemcpyHostToDevice);
+        alloc(&p->win_a, frame * sizeof(float));
+        if (alloc.ok()) alloc.err = hipMemcpy(p->win_a, win_a, frame * sizeof(float), hipMemcpyHostToDevice);
     }
     if (win_s) {
-        alloc((void**)&p->win_s, frame * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(p->win_s, win_s, frame * sizeof(float), hipMemcpyHostToDevice);
+        alloc(&p->win_s, frame * sizeof(float));
+        if (alloc.ok()) alloc.err = hipMemcpy(p->win_s, win_s, frame * sizeof(float), hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) {
+    if (!alloc.ok()) {
         oiva_stft_destroy(p);
-        return sfail(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(e));
+        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
     }
     *out = p;
     return OIVA_OK;
@@ -163,7 +146,7 @@ int oiva_stft_create(oiva_stft** out, int device, int n_samples, int n_chan, int
 
 int oiva_stft_destroy(oiva_stft* p) {
     if (!p) return OIVA_OK;
-    (void)hipSetDevice(p->device);
+    DeviceGuard guard(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     if (p->have_fwd) (void)hipfftDestroy(p->fwd);
     if (p->have_inv) (void)hipfftDestroy(p->inv);
@@ -176,62 +159,62 @@ int oiva_stft_destroy(oiva_stft* p) {
 }
 
 int oiva_stft_shape(oiva_stft* p, int* n_frames, int* n_freq) {
-    S_NEED(p, OIVA_ERR_ARG, "null handle");
+    OIVA_NEED(p, OIVA_ERR_ARG, "null handle");
     if (n_frames) *n_frames = p->T;
     if (n_freq) *n_freq = p->F;
     return OIVA_OK;
 }
 
 int oiva_stft_analysis(oiva_stft* p, const float* x_host, void* X_host, void** X_dev) {
-    S_NEED(p && x_host, OIVA_ERR_ARG, "null argument");
-    S_HIP(hipSetDevice(p->device));
+    OIVA_NEED(p && x_host, OIVA_ERR_ARG, "null argument");
+    DeviceGuard guard(p->device);
     const int T = p->T, C = p->C, L = p->L, F = p->F;
     if (!p->have_fwd) {
         int n[1] = {L};
-        S_FFT(hipfftPlanMany(&p->fwd, 1, n, nullptr, 1, L, nullptr, 1, F, HIPFFT_R2C, T * C));
-        S_FFT(hipfftSetStream(p->fwd, p->stream));
+        OIVA_TRY_FFT(hipfftPlanMany(&p->fwd, 1, n, nullptr, 1, L, nullptr, 1, F, HIPFFT_R2C, T * C));
+        OIVA_TRY_FFT(hipfftSetStream(p->fwd, p->stream));
         p->have_fwd = true;
     }
-    S_HIP(hipMemcpyAsync(p->x, x_host, (size_t)p->n_samples * C * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    OIVA_TRY_HIP(hipMemcpyAsync(p->x, x_host, (size_t)p->n_samples * C * sizeof(float), hipMemcpyHostToDevice, p->stream));
     const long long ne = (long long)T * C * L;
     hipLaunchKernelGGL(frame_kernel, dim3((unsigned)((ne + kBlock - 1) / kBlock)), dim3(kBlock), 0, p->stream, p->x, p->win_a,
                        p->frames, p->n_samples, C, L, p->hop, T);
-    S_HIP(hipGetLastError());
-    S_FFT(hipfftExecR2C(p->fwd, p->frames, reinterpret_cast<hipfftComplex*>(p->spec)));
+    OIVA_TRY_HIP(hipGetLastError());
+    OIVA_TRY_FFT(hipfftExecR2C(p->fwd, p->frames, reinterpret_cast<hipfftComplex*>(p->spec)));
     const long long nx = (long long)T * F * C;
     hipLaunchKernelGGL(to_tfc_kernel, dim3((unsigned)((nx + kBlock - 1) / kBlock)), dim3(kBlock), 0, p->stream, p->spec, p->X, T, F, C);
-    S_HIP(hipGetLastError());
-    if (X_host) S_HIP(hipMemcpyAsync(X_host, p->X, (size_t)nx * sizeof(float2), hipMemcpyDeviceToHost, p->stream));
-    S_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipGetLastError());
+    if (X_host) OIVA_TRY_HIP(hipMemcpyAsync(X_host, p->X, (size_t)nx * sizeof(float2), hipMemcpyDeviceToHost, p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     if (X_dev) *X_dev = p->X;
     return OIVA_OK;
 }
 
 int oiva_stft_synthesis(oiva_stft* p, const void* Y_host, int n_chan, float* y_host) {
-    S_NEED(p && Y_host && y_host, OIVA_ERR_ARG, "null argument");
-    S_NEED(n_chan >= 1 && n_chan <= p->C, OIVA_ERR_ARG, "synthesis takes at most the channel count of the plan");
-    S_HIP(hipSetDevice(p->device));
+    OIVA_NEED(p && Y_host && y_host, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(n_chan >= 1 && n_chan <= p->C, OIVA_ERR_ARG, "synthesis takes at most the channel count of the plan");
+    DeviceGuard guard(p->device);
     const int T = p->T, C = n_chan, L = p->L, F = p->F;
     // one inverse plan per channel count (the solver returns fewer channels than the analysis had)
     if (!p->have_inv || p->inv_chan != C) {
-        if (p->have_inv) S_FFT(hipfftDestroy(p->inv));
+        if (p->have_inv) OIVA_TRY_FFT(hipfftDestroy(p->inv));
         int n[1] = {L};
-        S_FFT(hipfftPlanMany(&p->inv, 1, n, nullptr, 1, F, nullptr, 1, L, HIPFFT_C2R, T * C));
-        S_FFT(hipfftSetStream(p->inv, p->stream));
+        OIVA_TRY_FFT(hipfftPlanMany(&p->inv, 1, n, nullptr, 1, F, nullptr, 1, L, HIPFFT_C2R, T * C));
+        OIVA_TRY_FFT(hipfftSetStream(p->inv, p->stream));
         p->have_inv = true;
         p->inv_chan = C;
     }
     const long long nx = (long long)T * F * C;
-    S_HIP(hipMemcpyAsync(p->X, Y_host, (size_t)nx * sizeof(float2), hipMemcpyHostToDevice, p->stream));
+    OIVA_TRY_HIP(hipMemcpyAsync(p->X, Y_host, (size_t)nx * sizeof(float2), hipMemcpyHostToDevice, p->stream));
     hipLaunchKernelGGL(from_tfc_kernel, dim3((unsigned)((nx + kBlock - 1) / kBlock)), dim3(kBlock), 0, p->stream, p->X, p->spec, T, F, C);
-    S_HIP(hipGetLastError());
-    S_FFT(hipfftExecC2R(p->inv, reinterpret_cast<hipfftComplex*>(p->spec), p->frames));
+    OIVA_TRY_HIP(hipGetLastError());
+    OIVA_TRY_FFT(hipfftExecC2R(p->inv, reinterpret_cast<hipfftComplex*>(p->spec), p->frames));
     const long long ny = (long long)T * p->hop * C;
     hipLaunchKernelGGL(overlap_add_kernel, dim3((unsigned)((ny + kBlock - 1) / kBlock)), dim3(kBlock), 0, p->stream, p->frames,
                        p->win_s, p->x, C, L, p->hop, T);
-    S_HIP(hipGetLastError());
-    S_HIP(hipMemcpyAsync(y_host, p->x, (size_t)ny * sizeof(float), hipMemcpyDeviceToHost, p->stream));
-    S_HIP(hipStreamSynchronize(p->stream));
+    OIVA_TRY_HIP(hipGetLastError());
+    OIVA_TRY_HIP(hipMemcpyAsync(y_host, p->x, (size_t)ny * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     return OIVA_OK;
 }
 

@@ -44,8 +44,9 @@ class CollectiveExchange:
         pass
 
 
-class PushExchange:
+class PushExchange(_lib.Handle):
     name = "push"
+    _destroy = "oiva_xchg_destroy"
 
     def __init__(self, device, rank, world, part_ptr, part_bytes, stream_handle):
         if world > 1:
@@ -95,17 +96,6 @@ class PushExchange:
         self.push()
         self.wait()
         return self.gathered_ptr()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.oiva_xchg_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _device_view(torch, ptr, nfloats, device):

@@ -26,12 +26,14 @@ class DeviceX:
         self.ndim = 3
 
 
-class Plan:
+class Plan(_lib.Handle):
     """Owns the device state of one AuxIVA/OverIVA problem (or one bin shard of it).
 
     Mirrors the stages of reference ``overiva.py``: ``set_x`` (:132), ``covariance`` (:87),
     ``set_w`` (:89-123), ``iterate`` (:138-190), ``demix`` (:192-199), ``get_w`` (:201-202).
     """
+
+    _destroy = "oiva_plan_destroy"
 
     def __init__(self, T, F, M, K, model="laplace", device=0, F_total=None, stream=None):
         if model not in _lib.MODEL_IDS:
@@ -48,24 +50,6 @@ class Plan:
                                              C.c_void_p(stream) if stream else None))
         self.h = h
         self._keep = None
-
-    # -- life cycle ---------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.oiva_plan_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # -- input --------------------------------------------------------------------------------
     def set_x(self, X, f0=0):

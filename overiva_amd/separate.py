@@ -60,11 +60,13 @@ def _check_stft_args(n_samples, M, frame, hop):
             raise ValueError(f"room {b} is too large")
 
 
-class BatchSTFT:
+class BatchSTFT(_lib.Handle):
     """one handle = B rooms of ``n_samples[b]`` x M samples, one (frame, hop, windows) configuration, on one GPU (``oiva_bstft``).
 
     ``n_samples``: an int together with ``B`` (rooms of one length: X comes in the dense (B, T, F, M) layout of ``BatchPlan``), or
     a list of B ints (X packed (sum T_b, F, M), the layout of ``RaggedBatchPlan``)."""
+
+    _destroy = "oiva_bstft_destroy"
 
     def __init__(self, n_samples, M, frame, hop=None, win_a=None, win_s=None, device=None, B=None, stream=None):
         self.dense = isinstance(n_samples, (int, np.integer)) and not isinstance(n_samples, bool)
@@ -93,23 +95,6 @@ class BatchSTFT:
         self.frames, self.n_freq = list(fr), f.value
         self.sample_offsets = np.concatenate([[0], np.cumsum(lens)]).astype(int)
         self.out_offsets = np.concatenate([[0], np.cumsum(self.frames)]).astype(int) * self.hop
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.oiva_bstft_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _pack(self, x):
         if isinstance(x, (list, tuple)):
@@ -256,7 +241,8 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
             plan.covariance()
             info = dict(plan.info(), audio=True)
             if algorithm == "ogive":
-                _run_ogive(plan, n_iter, W0, init_eig, model, info, **algo_kwargs)
+                epochs, converged = _batch._run_ogive(plan, n_iter, W0, init_eig, model, **algo_kwargs)
+                info.update(algorithm="ogive", epochs=[int(e) for e in epochs], converged=[bool(c) for c in converged])
             elif algorithm == "auxiva_pca" and K < M:
                 _pca_batch.reduce_and_solve(plan, n_iter, W0, init_eig, model)
             else:
@@ -276,25 +262,3 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
     if out_dtype != np.float32:
         y = [a.astype(out_dtype) for a in y] if ragged else y.astype(out_dtype)
     return (y, W) if return_filters else y
-
-
-def _run_ogive(plan, n_iter, W0, init_eig, model, info, step_size=0.1, tol=1e-3, update="demix"):
-    """the epochs of ``ogive_batch()`` on a plan whose X is set"""
-    B, F, M = plan.B, plan.F, plan.M
-    if W0 is None and init_eig:                                         # ive.py:111-126 per problem (host LAPACK; not conjugated)
-        cx = plan.get_cx(np.complex128)
-        W0 = np.empty((B, F, M, 1), np.complex128)
-        for b in range(B):
-            vals, vecs = np.linalg.eig(cx[b])
-            W0[b, :, :, 0] = np.stack([vecs[f][:, np.argmax(vals[f])] for f in range(F)])
-    plan.set_w(None if W0 is None else np.asarray(W0))
-    plan.ogive_begin(update, model)
-    epochs = np.zeros(B, dtype=int)
-    converged = np.zeros(B, dtype=bool)
-    epoch = 0
-    while epoch < n_iter and not converged.all():
-        step = min(n_iter - epoch, _ive.CHUNK)
-        ran, converged, _ = plan.ogive_iterate(epoch, step, step_size, tol)
-        epochs += ran
-        epoch += step
-    info.update(algorithm="ogive", epochs=[int(e) for e in epochs], converged=[bool(c) for c in converged])

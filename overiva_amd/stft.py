@@ -38,8 +38,10 @@ def compute_synthesis_window(analysis_window, hop):
     return w / norm
 
 
-class STFT:
+class STFT(_lib.Handle):
     """one handle = one (n_samples, n_chan, frame, hop, windows) configuration on one GPU"""
+
+    _destroy = "oiva_stft_destroy"
 
     def __init__(self, n_samples, n_chan, L, hop, win_a=None, win_s=None, device=0):
         self.lib = _lib.load()
@@ -56,23 +58,6 @@ class STFT:
         t, f = C.c_int(), C.c_int()
         _lib.check(self.lib.oiva_stft_shape(self.h, C.byref(t), C.byref(f)))
         self.n_frames, self.n_freq = t.value, f.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.oiva_stft_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def analysis(self, x, to_host=True):
         """x (n_samples, n_chan) real -> X (n_frames, n_freq, n_chan) complex64; with ``to_host=False`` returns the
