@@ -463,6 +463,41 @@ oiva_status oiva_batch_project_dev(oiva_batch *b, void **Xr_dev);
 oiva_status oiva_batch_compose_w(oiva_batch *outer, const oiva_batch *inner);
 
 /*
+ * Batched ILRMA: independent low-rank matrix analysis on B rooms of one shape per set of launches (kernels_ilrma_batch.hip;
+ * DESIGN.md 3.9 states the algorithm, which is the contract: parity with pra.bss.ilrma is not pinned).  Determined: the batch is
+ * made by oiva_batch_create with K = M <= 8; a ragged batch gets OIVA_ERR_ARG ("ragged").  Source model r[s,f,t] = (Tn[s] Vn[s])[f,t]
+ * with n_components columns; all state is float64, W is carried in complex128 as by oiva_batch_iterate.
+ *   oiva_batch_ilrma_begin   : after oiva_batch_set_x_*, oiva_batch_covariance and oiva_batch_set_w; 1 <= n_components <= 16;
+ *                              T0 (B, K, F, L) and V0 (B, K, L, T) host float64, strictly positive.  Allocates the state and
+ *                              forms R = T0 V0 and P = |y|^2 from the W that is set.
+ *   oiva_batch_ilrma_stage   : one stage of an epoch (OIVA_ILRMA_STAGE_*), eager on the batch's stream
+ *   oiva_batch_ilrma_iterate : n epochs = n times the stages in order
+ *   oiva_batch_ilrma_get_nmf : Tn (B, K, F, L), Vn (B, K, L, T); either may be NULL
+ *   oiva_batch_ilrma_get_pr  : test hook: P, R (B, K, F, T); either may be NULL
+ *   oiva_batch_ilrma_get_cov : test hook: C (B, F, K, M*M), the packed Hermitian frame-split partials of the last covariance
+ *                              stage added in split order (sum_t x x^H / r, not divided by T; M real diagonals, then (re, im)
+ *                              of every entry c < d, row-major), and lambda (B, K) of the last normalisation; either may be NULL
+ *   oiva_batch_ilrma_time_stages : n epochs with events around every stage: per_stage_ms[7], ms per epoch by stage
+ * A room's bits do not depend on B or on its place in the batch.  The result is read with oiva_batch_demix / _get_w / _status.
+ */
+enum {
+    OIVA_ILRMA_STAGE_T = 0,         /* Tn of every source from P and R, then its rows of R */
+    OIVA_ILRMA_STAGE_V = 1,         /* Vn of every source */
+    OIVA_ILRMA_STAGE_R = 2,         /* R = Tn Vn */
+    OIVA_ILRMA_STAGE_COV = 3,       /* C_s = (1/T) sum_t x x^H / r[s,f,t], as frame-split partials */
+    OIVA_ILRMA_STAGE_UPDATE = 4,    /* IP1 per bin, the sources in sequence */
+    OIVA_ILRMA_STAGE_POWER = 5,     /* P from the new W */
+    OIVA_ILRMA_STAGE_NORMALISE = 6  /* lambda_s = sqrt(mean P[s]); W / lambda, P, R and Tn / lambda^2 */
+};
+oiva_status oiva_batch_ilrma_begin(oiva_batch *b, int n_components, const double *T0, const double *V0);
+oiva_status oiva_batch_ilrma_stage(oiva_batch *b, int stage);
+oiva_status oiva_batch_ilrma_iterate(oiva_batch *b, int n);
+oiva_status oiva_batch_ilrma_get_nmf(oiva_batch *b, double *T, double *V);
+oiva_status oiva_batch_ilrma_get_pr(oiva_batch *b, double *P, double *R);
+oiva_status oiva_batch_ilrma_get_cov(oiva_batch *b, double *C, double *lambda);
+oiva_status oiva_batch_ilrma_time_stages(oiva_batch *b, int n, float *per_stage_ms);
+
+/*
  * STFT analysis / synthesis on the GPU (hipFFT): time-domain audio in and out next to the solver.
  * Replaces, in the reference's drivers, pra.transform.analysis(mics_signals.T, framesize, framesize // 2, win=win_a)
  * (overiva_oneshot.py:293-295, overiva_sim.py:206-207) and pra.transform.synthesis(Y, framesize, framesize // 2,

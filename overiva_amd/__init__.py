@@ -6,6 +6,7 @@ onolab-tmu/overiva behind the reference's own Python signatures.
     from overiva_amd import ogive_batch        # the same for OGIVE, a stopping rule per problem
     from overiva_amd import overiva_batch_ragged   # problems of different frame counts in one batch
     from overiva_amd import auxiva_pca_batch   # PCA + determined AuxIVA for many rooms per call
+    from overiva_amd import ilrma_batch, ilrma # ILRMA (NMF source model) for many rooms per call; the algorithm of DESIGN.md 3.9
     from overiva_amd import separate_batch     # audio in, audio out for many rooms, X and Y staying on the device
 
 Host code is Python (as the reference is); all arithmetic on the path runs in hand-written HIP
@@ -21,6 +22,7 @@ _lib_mod._set_ipc_env_at_import()
 from ._lib import HipError, HipLibraryMissing  # noqa: E402,F401
 from .auxiva_pca import auxiva_pca  # noqa: F401
 from .batch import BatchPlan, DeviceBatch, RaggedBatchPlan, last_batch_info, ogive_batch, overiva_batch, overiva_batch_ragged  # noqa: F401
+from .ilrma import ilrma, ilrma_batch  # noqa: F401
 from .ive import ogive  # noqa: F401
 from .pca_batch import auxiva_pca_batch  # noqa: F401
 from .overiva import (get_device, get_precision, last_solver_info, overiva, release_cached_buffers, set_device,  # noqa: F401
@@ -29,5 +31,5 @@ from .plan import DeviceX, Plan  # noqa: F401
 from .separate import BatchSTFT, separate_batch  # noqa: F401
 from .sharded import BinShardedSolver, disable_bin_sharding, enable_bin_sharding, shard_bounds  # noqa: F401
 
-__all__ = ["overiva", "separate_batch", "BatchSTFT", "DeviceBatch", "overiva_batch", "overiva_batch_ragged", "ogive_batch", "auxiva_pca_batch", "last_batch_info", "BatchPlan", "RaggedBatchPlan", "auxiva_pca", "ogive", "Plan", "DeviceX", "BinShardedSolver", "enable_bin_sharding", "disable_bin_sharding",
+__all__ = ["overiva", "separate_batch", "BatchSTFT", "DeviceBatch", "overiva_batch", "overiva_batch_ragged", "ogive_batch", "auxiva_pca_batch", "ilrma_batch", "ilrma", "last_batch_info", "BatchPlan", "RaggedBatchPlan", "auxiva_pca", "ogive", "Plan", "DeviceX", "BinShardedSolver", "enable_bin_sharding", "disable_bin_sharding",
            "shard_bounds", "release_cached_buffers", "set_device", "get_device", "set_precision", "get_precision", "last_solver_info", "HipError", "HipLibraryMissing"]

@@ -126,6 +126,13 @@ SIGNATURES = {
     "oiva_batch_set_w_pca": [_vp, _vp],
     "oiva_batch_project_dev": [_vp, C.POINTER(_vp)],
     "oiva_batch_compose_w": [_vp, _vp],
+    "oiva_batch_ilrma_begin": [_vp, _i, _vp, _vp],
+    "oiva_batch_ilrma_stage": [_vp, _i],
+    "oiva_batch_ilrma_iterate": [_vp, _i],
+    "oiva_batch_ilrma_get_nmf": [_vp, _vp, _vp],
+    "oiva_batch_ilrma_get_pr": [_vp, _vp, _vp],
+    "oiva_batch_ilrma_get_cov": [_vp, _vp, _vp],
+    "oiva_batch_ilrma_time_stages": [_vp, _i, _fp],
     "oiva_stft_create": [C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp],
     "oiva_stft_destroy": [_vp],
     "oiva_stft_shape": [_vp, C.POINTER(_i), C.POINTER(_i)],

@@ -25,6 +25,7 @@ from .overiva import _complex_dtype, get_device
 
 _overiva_module = sys.modules[__package__ + ".overiva"]   # (the package's attribute `overiva` is the function)
 MAX_CHANNELS = 8
+ILRMA_STAGES = ("t_update", "v_update", "r_rewrite", "weighted_cov", "ip_update", "power", "normalise")   # OIVA_ILRMA_STAGE_*
 _info = {}
 
 
@@ -32,6 +33,7 @@ def last_batch_info():
     """what the last batched call ran: ``{"precision": "precise", "batched": B, ...}``; after ``auxiva_pca_batch()`` also
     ``algorithm`` ("auxiva_pca") and ``reduced`` (the channel count of the inner solve); after
     ``ogive_batch()`` also ``epochs`` (B ints: epochs each problem ran) and ``converged`` (B bools: its stopping rule fired); after
+    ``ilrma_batch()`` also ``algorithm`` ("ilrma") and ``n_components``; after
     ``overiva_batch_ragged()`` also ``ragged`` (True) and ``frames`` (B ints), ``shape`` then holding the largest T"""
     return dict(_info)
 
@@ -66,13 +68,15 @@ class BatchPlan(_lib.Handle):
     Stages as ``Plan``'s: ``set_x``, ``covariance``, ``set_w`` / ``set_w_eig``, ``iterate``, ``demix``, ``get_w``; ``status``
     reports which problems hold a non-finite W.  ``set_w_pca`` / ``project_device`` / ``compose_w`` are the PCA front end of
     ``auxiva_pca_batch()`` (pca_batch.py).  With K = 1, ``ogive_begin`` / ``ogive_iterate`` run OGIVE instead of
-    ``iterate`` (``get_cx`` reads the input covariance for the host's ``init_eig``).
+    ``iterate`` (``get_cx`` reads the input covariance for the host's ``init_eig``).  With K = M, ``ilrma_begin`` /
+    ``ilrma_iterate`` run ILRMA (ilrma.py); ``ilrma_stage`` runs one stage of an epoch, ``get_nmf`` reads the source model.
 
     On the device X and Y are packed along the frames, (sum T_b, F, .): ``frames`` holds the B frame counts (here B times T)
     and ``offsets`` every problem's first frame."""
 
     _destroy = "oiva_batch_destroy"
     dense = True          # X and Y are handed over as one (B, T, F, .) array
+    n_components = 0      # columns of the ILRMA source model, set by ilrma_begin
 
     def __init__(self, B, T, F, M, K, model="laplace", device=None, stream=None):
         self._open([int(T)] * int(B), int(T), F, M, K, model, device, stream)
@@ -178,6 +182,51 @@ class BatchPlan(_lib.Handle):
         ran, conv, md = (C.c_int * self.B)(), (C.c_int * self.B)(), (C.c_double * self.B)()
         _lib.check(self.lib.oiva_batch_ogive_iterate(self.h, int(first_epoch), int(n), float(step_size), float(tol), ran, conv, md))
         return np.array(list(ran), dtype=int), np.array(list(conv), dtype=bool), np.array(list(md))
+
+    def ilrma_begin(self, T0, V0):
+        """start ILRMA (needs K = M, X, the covariance and W set): T0 (B, K, F, L) and V0 (B, K, L, T) float64, strictly
+        positive; forms R = T0 V0 and P = |y|^2 from the current W"""
+        T0 = np.ascontiguousarray(T0, dtype=np.float64)
+        V0 = np.ascontiguousarray(V0, dtype=np.float64)
+        if T0.ndim != 4 or T0.shape[:3] != (self.B, self.K, self.F) or V0.shape != (self.B, self.K, T0.shape[3], self.T):
+            raise ValueError(f"T0 must be {(self.B, self.K, self.F, 'L')} and V0 {(self.B, self.K, 'L', self.T)}, got {T0.shape} and {V0.shape}")
+        _lib.check(self.lib.oiva_batch_ilrma_begin(self.h, T0.shape[3], _lib.ptr(T0), _lib.ptr(V0)))
+        self.n_components = int(T0.shape[3])
+
+    def ilrma_iterate(self, n=1):
+        _lib.check(self.lib.oiva_batch_ilrma_iterate(self.h, int(n)))
+
+    def ilrma_stage(self, stage):
+        """one stage of an epoch: a name of ``ILRMA_STAGES`` or its index"""
+        _lib.check(self.lib.oiva_batch_ilrma_stage(self.h, ILRMA_STAGES.index(stage) if isinstance(stage, str) else int(stage)))
+
+    def get_nmf(self):
+        """(Tn (B, K, F, L), Vn (B, K, L, T)) of the ILRMA source model"""
+        Tn = np.empty((self.B, self.K, self.F, self.n_components))
+        Vn = np.empty((self.B, self.K, self.n_components, self.T))
+        _lib.check(self.lib.oiva_batch_ilrma_get_nmf(self.h, _lib.ptr(Tn), _lib.ptr(Vn)))
+        return Tn, Vn
+
+    def get_pr(self):
+        """test hook: (P, R), both (B, K, F, T): the source powers |y|^2 and the model Tn Vn as the device holds them"""
+        P = np.empty((self.B, self.K, self.F, self.T))
+        R = np.empty_like(P)
+        _lib.check(self.lib.oiva_batch_ilrma_get_pr(self.h, _lib.ptr(P), _lib.ptr(R)))
+        return P, R
+
+    def get_ilrma_cov(self):
+        """test hook: (C (B, F, K, M*M), lambda (B, K)): the packed Hermitian partials of the last covariance stage added over
+        the frame splits (not divided by T) and the scales of the last normalisation"""
+        Cp = np.empty((self.B, self.F, self.K, self.M * self.M))
+        lam = np.empty((self.B, self.K))
+        _lib.check(self.lib.oiva_batch_ilrma_get_cov(self.h, _lib.ptr(Cp), _lib.ptr(lam)))
+        return Cp, lam
+
+    def ilrma_time_stages(self, n):
+        """n epochs with events around every stage: {stage: ms per epoch}; advances the state"""
+        arr = (C.c_float * len(ILRMA_STAGES))()
+        _lib.check(self.lib.oiva_batch_ilrma_time_stages(self.h, int(n), arr))
+        return dict(zip(ILRMA_STAGES, list(arr)))
 
     def _demix_packed(self, proj_back, dtype):
         out = np.empty((int(self.offsets[-1]), self.F, self.K), dtype)
@@ -432,7 +481,7 @@ class RaggedBatchPlan(BatchPlan):
     The stages are ``BatchPlan``'s, and so is the device state: the two differ in what the caller hands over and gets back.
     ``set_x`` takes the list of B (T_b, F, M) arrays or the packed (sum T_b, F, M) array, ``set_x_device`` borrows a packed
     complex64 device array, and ``demix`` returns the list of B (T_b, F, K) arrays.  W, ``set_w``'s W0 and ``status`` are
-    (B, ...).  OGIVE does not run on a ragged batch: ``ogive_begin`` / ``ogive_iterate`` raise."""
+    (B, ...).  Neither OGIVE nor ILRMA runs on a ragged batch: ``ogive_*`` and ``ilrma_*`` raise."""
 
     dense = False
 
@@ -466,6 +515,11 @@ class RaggedBatchPlan(BatchPlan):
         raise ValueError("OGIVE does not run on a ragged batch (use ogive_batch on same-length problems)")
 
     ogive_iterate = ogive_begin
+
+    def ilrma_begin(self, *args, **kwargs):
+        raise ValueError("ILRMA does not run on a ragged batch (use ilrma_batch on same-length rooms)")
+
+    ilrma_iterate = ilrma_stage = get_nmf = get_pr = get_ilrma_cov = ilrma_time_stages = ilrma_begin
 
     def demix(self, proj_back=True, dtype=np.complex64):
         """the list of B arrays Y_b (T_b, F, K), complex64 or complex128"""

@@ -6,7 +6,9 @@
 // launch arguments (measured 1-4 % faster per stage than reading the table, CHANGELOG), a batch of oiva_batch_create_ragged
 // those of kernels_ragged.hip, which read the table on the device.  The per-bin stages are the single-problem kernels run on
 // B*F bins.  Batched OGIVE (oiva_batch_ogive_*) runs on a batch of oiva_batch_create with K = 1, with its own kernels
-// (kernels_ogive_batch.hip) and a stopping rule per problem.  The PCA front end of auxiva_pca_batch (oiva_batch_set_w_pca,
+// (kernels_ogive_batch.hip) and a stopping rule per problem.  Batched ILRMA (oiva_batch_ilrma_*) runs on a batch of
+// oiva_batch_create with K = M: its NMF stages and its covariance pass are kernels_ilrma_batch.hip, its per-bin step the update.
+// The PCA front end of auxiva_pca_batch (oiva_batch_set_w_pca,
 // _project_dev, _compose_w; kernels_pca_batch.hip) reads the table on the device for every batch.
 #include <algorithm>
 #include <cmath>
@@ -29,6 +31,8 @@ constexpr int kGraphCache = 4;
 constexpr size_t kStageBytes = (size_t)256 << 20;   // staging of complex128 input
 constexpr int kOgFramesPerSplit = 64;     // frame splits of the OGIVE frame sums: ceil(T / 64), a function of T alone
 constexpr int kOgMinGraphEpochs = 8;      // shorter OGIVE chunks run eagerly
+constexpr int kIlrmaMaxComponents = 16;
+constexpr int kIlrmaStages = OIVA_ILRMA_STAGE_NORMALISE + 1;
 
 // geometry of the frame-split passes of a problem of T frames: a function of T alone (never of B or of other problems), so a
 // problem gets the same bits whatever batch it is in
@@ -91,6 +95,10 @@ struct oiva_batch {
     hipGraphExec_t og_graph = nullptr;
     int og_graph_n = 0, og_graph_phase = -1;
     double og_graph_mu = 0., og_graph_tol = 0.;
+    // batched ILRMA: the NMF state (Tn, Vn), the source models R and the powers P, allocated by ilrma_begin
+    IlrmaState il{};
+    std::vector<void*> il_bufs;
+    bool il_ready = false;
 };
 
 namespace {
@@ -227,6 +235,7 @@ void free_all(oiva_batch* b) {
                     (void*)b->wscale, (void*)b->Spart, (void*)b->Y, (void*)b->Y128, (void*)b->Xr, (void*)b->probs_dev})
         if (q) (void)hipFree(q);
     for (void* q : b->og_bufs) (void)hipFree(q);
+    for (void* q : b->il_bufs) (void)hipFree(q);
     for (hipEvent_t& e : b->ev)
         if (e) (void)hipEventDestroy(e);
     if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
@@ -288,6 +297,50 @@ int fill_batch(oiva_batch* b, const std::vector<int>& frames, void* stream) {
     OIVA_TRY_HIP(hipMemset(b->R, 0, r_floats * sizeof(float)));      // (the pad rows behind every problem's r)
     OIVA_TRY_HIP(dev_malloc(&b->wscale, (size_t)B * K * sizeof(float)));
     OIVA_TRY_HIP(dev_malloc(&b->Spart, (size_t)spart_splits * F * K * 3 * sizeof(float)));
+    return OIVA_OK;
+}
+
+// one stage of an ILRMA epoch (OIVA_ILRMA_STAGE_*); an epoch is the stages in order
+int ilrma_stage(oiva_batch* b, int s) {
+    const DenseArgs d = dense_args(b);
+    switch (s) {
+        case OIVA_ILRMA_STAGE_T:
+            OIVA_TRY_HIP(launch_ilrma_t(b->stream, b->il, b->B, d.T, b->F, b->K));
+            break;
+        case OIVA_ILRMA_STAGE_V:
+            OIVA_TRY_HIP(launch_ilrma_v(b->stream, b->il, b->B, d.T, b->F, b->K));
+            break;
+        case OIVA_ILRMA_STAGE_R:
+            OIVA_TRY_HIP(launch_ilrma_r(b->stream, b->il, b->B, d.T, b->F, b->K));
+            break;
+        case OIVA_ILRMA_STAGE_COV:
+            OIVA_TRY_HIP(launch_ilrma_cov(b->stream, b->X, b->il, b->Vpart, b->B, d.T, b->F, b->M, d.nsplit, d.tc));
+            break;
+        case OIVA_ILRMA_STAGE_UPDATE: {
+            UpdateArgs a = update_args(b, false);      // IP1 on V = C_s: no pending scale of W
+            a.wscale = nullptr;
+            OIVA_TRY_HIP(launch_update(b->stream, a));
+            break;
+        }
+        case OIVA_ILRMA_STAGE_POWER:
+            OIVA_TRY_HIP(launch_ilrma_power(b->stream, b->X, b->What64, b->il, b->B, d.T, b->F, b->M));
+            break;
+        case OIVA_ILRMA_STAGE_NORMALISE:
+            OIVA_TRY_HIP(launch_ilrma_normalise(b->stream, b->il, b->What, b->What64, b->B, d.T, b->F, b->M));
+            break;
+        default:
+            return fail_with(OIVA_ERR_ARG, "unknown ILRMA stage");
+    }
+    return OIVA_OK;
+}
+
+int check_ilrma(oiva_batch* b, bool begun) {
+    OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(!b->ragged, OIVA_ERR_ARG, "ILRMA is not supported on a ragged batch");
+    const int rc = check_ready(b);
+    if (rc) return rc;
+    OIVA_NEED(b->K == b->M, OIVA_ERR_ARG, "ILRMA is determined: create the batch with K = M");
+    if (begun) OIVA_NEED(b->il_ready, OIVA_ERR_STATE, "call oiva_batch_ilrma_begin first");
     return OIVA_OK;
 }
 
@@ -668,6 +721,132 @@ oiva_status oiva_batch_ogive_iterate(oiva_batch* b, int first_epoch, int n, doub
         for (int p = 0; p < B; ++p) epochs_run[p] = after[p] - before[p];
     if (converged) OIVA_TRY_HIP(hipMemcpy(converged, b->og.done, B * sizeof(int), hipMemcpyDeviceToHost));
     if (max_delta) OIVA_TRY_HIP(hipMemcpy(max_delta, b->og.maxdelta, B * sizeof(double), hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+// ---- batched ILRMA (one room per batch entry, determined, eager launches) ------------------------------------------
+oiva_status oiva_batch_ilrma_begin(oiva_batch* b, int n_components, const double* T0, const double* V0) {
+    int rc = check_ilrma(b, false);
+    if (rc) return rc;
+    OIVA_NEED(n_components >= 1 && n_components <= kIlrmaMaxComponents, OIVA_ERR_ARG, "n_components must be in 1..16");
+    OIVA_NEED(T0 != nullptr && V0 != nullptr, OIVA_ERR_ARG, "null argument");
+    const size_t B = b->B, K = b->K, F = b->F, T = b->T, L = n_components;
+    const size_t nt = B * K * F * L, nv = B * K * L * T, npr = B * K * F * T;
+    for (size_t i = 0; i < nt; ++i) OIVA_NEED(T0[i] > 0. && std::isfinite(T0[i]), OIVA_ERR_ARG, "T0 must be strictly positive");
+    for (size_t i = 0; i < nv; ++i) OIVA_NEED(V0[i] > 0. && std::isfinite(V0[i]), OIVA_ERR_ARG, "V0 must be strictly positive");
+    DeviceGuard guard(b->device);
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    if (!b->il_bufs.empty() && b->il.L != n_components) {      // (another component count: the state is sized by it)
+        for (void* q : b->il_bufs) (void)hipFree(q);
+        b->il_bufs.clear();
+    }
+    b->il_ready = false;
+    if (b->il_bufs.empty()) {
+        AllocChain alloc;
+        alloc.keep = &b->il_bufs;
+        b->il = IlrmaState{};
+        b->il.L = n_components;
+        alloc(&b->il.Tn, nt * sizeof(double));
+        alloc(&b->il.Vn, nv * sizeof(double));
+        alloc(&b->il.P, npr * sizeof(double));
+        alloc(&b->il.R, npr * sizeof(double));
+        alloc(&b->il.Upart, 2 * (size_t)ilrma_v_chunks(b->F) * nv * sizeof(double));
+        alloc(&b->il.rowsum, B * K * F * sizeof(double));
+        alloc(&b->il.lam, B * K * sizeof(double));
+        if (!alloc.ok()) return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
+    }
+    OIVA_TRY_HIP(hipMemcpy(b->il.Tn, T0, nt * sizeof(double), hipMemcpyHostToDevice));
+    OIVA_TRY_HIP(hipMemcpy(b->il.Vn, V0, nv * sizeof(double), hipMemcpyHostToDevice));
+    OIVA_TRY_HIP(hipMemsetAsync(b->il.lam, 0, B * K * sizeof(double), b->stream));
+    // R = Tn Vn and P from the W that is set
+    rc = ilrma_stage(b, OIVA_ILRMA_STAGE_R);
+    if (rc) return rc;
+    rc = ilrma_stage(b, OIVA_ILRMA_STAGE_POWER);
+    if (rc) return rc;
+    b->il_ready = true;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_ilrma_stage(oiva_batch* b, int stage) {
+    const int rc = check_ilrma(b, true);
+    if (rc) return rc;
+    OIVA_NEED(stage >= 0 && stage < kIlrmaStages, OIVA_ERR_ARG, "unknown ILRMA stage");
+    DeviceGuard guard(b->device);
+    return ilrma_stage(b, stage);
+}
+
+oiva_status oiva_batch_ilrma_iterate(oiva_batch* b, int n) {
+    int rc = check_ilrma(b, true);
+    if (rc) return rc;
+    OIVA_NEED(n >= 0, OIVA_ERR_ARG, "n must be >= 0");
+    DeviceGuard guard(b->device);
+    for (int e = 0; e < n; ++e)
+        for (int s = 0; s < kIlrmaStages; ++s)
+            if ((rc = ilrma_stage(b, s))) return rc;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_ilrma_get_nmf(oiva_batch* b, double* T, double* V) {
+    const int rc = check_ilrma(b, true);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    const size_t BK = (size_t)b->B * b->K, L = b->il.L;
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    if (T) OIVA_TRY_HIP(hipMemcpy(T, b->il.Tn, BK * b->F * L * sizeof(double), hipMemcpyDeviceToHost));
+    if (V) OIVA_TRY_HIP(hipMemcpy(V, b->il.Vn, BK * L * b->T * sizeof(double), hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_ilrma_get_pr(oiva_batch* b, double* P, double* R) {
+    const int rc = check_ilrma(b, true);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    const size_t n = (size_t)b->B * b->K * b->F * b->T;
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    if (P) OIVA_TRY_HIP(hipMemcpy(P, b->il.P, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (R) OIVA_TRY_HIP(hipMemcpy(R, b->il.R, n * sizeof(double), hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_ilrma_get_cov(oiva_batch* b, double* C, double* lambda) {
+    const int rc = check_ilrma(b, true);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    if (C) {
+        // the frame-split partials of the last covariance stage, added in split order
+        const size_t n = nbins(b) * b->K * b->M * b->M;
+        const int nsplit = dense_args(b).nsplit;
+        std::vector<double> part((size_t)nsplit * n);
+        OIVA_TRY_HIP(hipMemcpy(part.data(), b->Vpart, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) {
+            double s = 0.;
+            for (int p = 0; p < nsplit; ++p) s += part[(size_t)p * n + i];
+            C[i] = s;
+        }
+    }
+    if (lambda) OIVA_TRY_HIP(hipMemcpy(lambda, b->il.lam, (size_t)b->B * b->K * sizeof(double), hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_ilrma_time_stages(oiva_batch* b, int n, float* per_stage_ms) {
+    int rc = check_ilrma(b, true);
+    if (rc) return rc;
+    OIVA_NEED(n >= 1 && per_stage_ms, OIVA_ERR_ARG, "n must be >= 1");
+    DeviceGuard guard(b->device);
+    double acc[kIlrmaStages] = {};
+    for (int e = 0; e < n; ++e) {
+        for (int s = 0; s < kIlrmaStages; ++s) {
+            OIVA_TRY_HIP(hipEventRecord(b->ev[0], b->stream));
+            if ((rc = ilrma_stage(b, s))) return rc;
+            OIVA_TRY_HIP(hipEventRecord(b->ev[1], b->stream));
+            OIVA_TRY_HIP(hipEventSynchronize(b->ev[1]));
+            float ms = 0.f;
+            OIVA_TRY_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+            acc[s] += ms;
+        }
+    }
+    for (int s = 0; s < kIlrmaStages; ++s) per_stage_ms[s] = (float)(acc[s] / n);
     return OIVA_OK;
 }
 

@@ -435,6 +435,29 @@ hipError_t launch_batch_ogive_framesum(hipStream_t s, const float2* X, const dou
 hipError_t launch_batch_ogive_step(hipStream_t s, const OgiveBatchState& st, const double* Opart, int osplit, int B, int F, int M, double mu,
                                    double tol);
 
+// Batched ILRMA (kernels_ilrma_batch.hip, batch.hip): B rooms of one shape, K = M <= 8, L <= 16 components, float64 state.
+//   Tn (B, K, F, L); Vn (B, K, L, T); P, R (B, K, F, T), t fastest; Upart [2][ilrma_v_chunks(F)][B*K][L][T]; rowsum (B, K, F);
+//   lam (B, K).  The per-bin IP1 step is launch_update on the partials launch_ilrma_cov leaves in the batch's Vpart.
+struct IlrmaState {
+    double* Tn;
+    double* Vn;
+    double* P;
+    double* R;
+    double* Upart;
+    double* rowsum;
+    double* lam;
+    int L;
+};
+int ilrma_v_chunks(int F);
+hipError_t launch_ilrma_power(hipStream_t s, const float2* X, const double2* What64, const IlrmaState& st, int B, int T, int F, int M);
+hipError_t launch_ilrma_t(hipStream_t s, const IlrmaState& st, int B, int T, int F, int K);          // Tn, then its rows of R
+hipError_t launch_ilrma_v(hipStream_t s, const IlrmaState& st, int B, int T, int F, int K);          // Vn (two launches)
+hipError_t launch_ilrma_r(hipStream_t s, const IlrmaState& st, int B, int T, int F, int K);          // R = Tn Vn
+hipError_t launch_ilrma_cov(hipStream_t s, const float2* X, const IlrmaState& st, double* Vpart, int B, int T, int F, int M, int nsplit,
+                            int tc);
+//   rowsum, lam = sqrt(mean P), then P, R, Tn / lam^2 and W / lam (three launches)
+hipError_t launch_ilrma_normalise(hipStream_t s, const IlrmaState& st, float2* What, double2* What64, int B, int T, int F, int M);
+
 // The batched STFT (kernels_bstft.hip, bstft.hip): the passes around hipFFT for B rooms at once.  One record per room; a dense
 // batch is the special case of equal records.
 struct BstftRoom {
