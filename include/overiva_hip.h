@@ -551,6 +551,39 @@ oiva_status oiva_bstft_phase_ms(oiva_bstft *p, float *ms);
 oiva_status oiva_batch_demix_dev(oiva_batch *b, int proj_back, void **Y_dev);
 oiva_status oiva_device_to_host(void *host, const void *dev, long long bytes);
 
+/*
+ * BSS Eval on the device (bsseval.hip, kernels_bsseval.hip): SDR, SIR and SAR of B rooms of N sources (1..8) with
+ * a filter of filter_length taps (1..512), rooms of their own lengths, all arithmetic in float64.  One handle = one
+ * (lengths, N, filter_length).  With diag_only only the pairs (estimate k, reference k) are evaluated.  max_group: 0, or the most
+ * rooms whose two copies of the Gram matrix may be held at once (the handle halves the group by itself when the allocation
+ * fails); a room's bits do not depend on B, on its place, on the other rooms' lengths or on the grouping.
+ *   ref / est packed (sum_b N * n_b) float64: room b's (N, n_b) signals, row-major, room after room.
+ *   oiva_bsseval_stage       : stage 0 correlate (lag sums), 1 factor (assembly + Cholesky of G and of its N diagonal blocks),
+ *                              2 solve, 3 criteria; in order; stages 1..3 need all rooms in one group (OIVA_ERR_STATE otherwise)
+ *   oiva_bsseval_run         : all four stages, group by group
+ *   oiva_bsseval_get_gram    : G (B, N Lf, N Lf) (after factor; may be NULL), D (B, N, N Lf), E (B, N) (after correlate)
+ *   oiva_bsseval_get_filters : C (B, N, N Lf) = G^-1 D_k and c (B, N[j], N[k], Lf) = G_jj^-1 D_k[j]
+ *   oiva_bsseval_get_criteria: sdr, sir, sar (B, N, N) indexed [room][estimate][reference], NaN where not evaluated; copies them
+ *                              out even when it returns OIVA_ERR_NUMERIC (a room's factorisation met a pivot that is not finite
+ *                              or <= N Lf eps max_diag(G); the message names the rooms as "problem(s) ...")
+ *   oiva_bsseval_status      : status[B], 1 for a flagged room
+ *   oiva_bsseval_time_stages : n full runs with events around every stage: per_stage_ms[4], ms per run
+ * Every entry checks its arguments before any device call and is synchronous.
+ */
+typedef struct oiva_bsseval oiva_bsseval;
+oiva_status oiva_bsseval_create(oiva_bsseval **out, int device, int B, const int *n_samples, int N, int filter_length,
+                                int diag_only, int max_group, void *stream);
+oiva_status oiva_bsseval_destroy(oiva_bsseval *p);
+oiva_status oiva_bsseval_groups(oiva_bsseval *p, int *rooms_per_group);
+oiva_status oiva_bsseval_set_signals(oiva_bsseval *p, const double *ref_host_packed, const double *est_host_packed);
+oiva_status oiva_bsseval_stage(oiva_bsseval *p, int stage);
+oiva_status oiva_bsseval_run(oiva_bsseval *p);
+oiva_status oiva_bsseval_get_gram(oiva_bsseval *p, double *G_host, double *D_host, double *E_host);
+oiva_status oiva_bsseval_get_filters(oiva_bsseval *p, double *C_host, double *c_host);
+oiva_status oiva_bsseval_get_criteria(oiva_bsseval *p, double *sdr, double *sir, double *sar);
+oiva_status oiva_bsseval_status(oiva_bsseval *p, int *status);
+oiva_status oiva_bsseval_time_stages(oiva_bsseval *p, int n, float *per_stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,17 @@ SIGNATURES = {
     "oiva_bstft_phase_ms": [_vp, _fp],
     "oiva_batch_demix_dev": [_vp, _i, C.POINTER(_vp)],
     "oiva_device_to_host": [_vp, _vp, _ll],
+    "oiva_bsseval_create": [C.POINTER(_vp), _i, _i, C.POINTER(_i), _i, _i, _i, _i, _vp],
+    "oiva_bsseval_destroy": [_vp],
+    "oiva_bsseval_groups": [_vp, C.POINTER(_i)],
+    "oiva_bsseval_set_signals": [_vp, _vp, _vp],
+    "oiva_bsseval_stage": [_vp, _i],
+    "oiva_bsseval_run": [_vp],
+    "oiva_bsseval_get_gram": [_vp, _vp, _vp, _vp],
+    "oiva_bsseval_get_filters": [_vp, _vp, _vp],
+    "oiva_bsseval_get_criteria": [_vp, _vp, _vp, _vp],
+    "oiva_bsseval_status": [_vp, C.POINTER(_i)],
+    "oiva_bsseval_time_stages": [_vp, _i, _fp],
 }
 
 

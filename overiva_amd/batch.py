@@ -34,7 +34,9 @@ def last_batch_info():
     ``algorithm`` ("auxiva_pca") and ``reduced`` (the channel count of the inner solve); after
     ``ogive_batch()`` also ``epochs`` (B ints: epochs each problem ran) and ``converged`` (B bools: its stopping rule fired); after
     ``ilrma_batch()`` also ``algorithm`` ("ilrma") and ``n_components``; after
-    ``overiva_batch_ragged()`` also ``ragged`` (True) and ``frames`` (B ints), ``shape`` then holding the largest T"""
+    ``overiva_batch_ragged()`` also ``ragged`` (True) and ``frames`` (B ints), ``shape`` then holding the largest T; after
+    ``bss_eval_batch()`` ``algorithm`` ("bss_eval"), ``batched``, ``n_sources``, ``filter_length`` and, for rooms of different
+    lengths, ``ragged`` (True) and ``lengths`` (B ints)"""
     return dict(_info)
 
 
