@@ -352,6 +352,9 @@ int oiva_test_power_order(int nsplit, int tcp, int cov_splits, int cov_tc, int *
 /* average duration of `reps` back-to-back launches of one stage (0 power, 1 activation, 2 covariance,
  * 3 update) on the plan's current state, HIP events on the plan's stream */
 int oiva_test_time_stage(oiva_plan *p, int stage, int reps, float *avg_ms);
+/* Test hook: device and pinned buffers the library has handed to its handles and temporaries and not yet taken back, and their
+ * bytes, over all handles of the process.  A large buffer resting in the pool (oiva_pool_trim) counts as taken back. */
+int oiva_test_live_buffers(long long *count, long long *bytes);
 
 /*
  * OGIVE -- orthogonally constrained independent vector extraction of ONE source by gradient steps, the reference's

@@ -16,6 +16,7 @@
 #include <utility>
 #include <vector>
 
+#include "host_io.h"
 #include "host_util.h"
 #include "oiva_internal.h"
 
@@ -28,7 +29,6 @@ constexpr int kCovFramesPerSplit = 256;   // frame splits of the covariance pass
 constexpr int kPowFramesPerSplit = 64;    // frame splits of the power pass (each partial power is one workgroup's: any split gives the same bits)
 constexpr int kGraphMaxIters = 32;        // longest captured graph: an iterate(n) call is ceil(n / 32) replays
 constexpr int kGraphCache = 4;
-constexpr size_t kStageBytes = (size_t)256 << 20;   // staging of complex128 input
 constexpr int kOgFramesPerSplit = 64;     // frame splits of the OGIVE frame sums: ceil(T / 64), a function of T alone
 constexpr int kOgMinGraphEpochs = 8;      // shorter OGIVE chunks run eagerly
 constexpr int kIlrmaMaxComponents = 16;
@@ -55,8 +55,8 @@ FrameGeom frame_geom(int T) {
 struct oiva_batch {
     int device = 0;
     int B = 0, T = 0, F = 0, M = 0, K = 0, model = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    HandleStream stream;           // five events: one iteration's four stages (oiva_batch_time_stages), [0] and [1] any bracket
+    DeviceArena mem;               // every device buffer below
     const float2* X = nullptr;     // (sum T_b, F, M) packed: (B, T, F, M) when the lengths are equal
     float2* X_owned = nullptr;
     float2* What = nullptr;        // (B*F, M, M) complex64: what the streaming kernels read
@@ -83,10 +83,8 @@ struct oiva_batch {
     bool ragged = false;           // made by oiva_batch_create_ragged: the kernels that read the table (dense_args otherwise)
     bool have_x = false, have_cx = false, have_w = false;
     GraphCache graphs{kGraphCache};    // by iterations per replay
-    hipEvent_t ev[5] = {};
     // batched OGIVE (ive.py:33-256): per-bin state of B*F bins and the per-problem stopping rule, allocated by ogive_begin
     OgiveBatchState og{};
-    std::vector<void*> og_bufs;
     double* Opart = nullptr;       // [osplit][B*F][2M+1] frame-sum partials
     int osplit = 1, otc = 1;
     bool og_ready = false;
@@ -97,7 +95,6 @@ struct oiva_batch {
     double og_graph_mu = 0., og_graph_tol = 0.;
     // batched ILRMA: the NMF state (Tn, Vn), the source models R and the powers P, allocated by ilrma_begin
     IlrmaState il{};
-    std::vector<void*> il_bufs;
     bool il_ready = false;
 };
 
@@ -214,7 +211,7 @@ int download_w(oiva_batch* b, void* W_host, int f64, std::vector<int>& bad) {
 int demix_on_device(oiva_batch* b, int proj_back) {
     const int F = b->F, M = b->M, K = b->K;
     const size_t ny = b->frames_total * F * K;
-    if (!b->Y) OIVA_TRY_HIP(dev_malloc(&b->Y, ny * sizeof(float2)));
+    if (!b->Y) OIVA_TRY_HIP(b->mem.take_one(&b->Y, ny * sizeof(float2)));
     // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0]):
     // every problem at its packed frame offset with the statistics geometry of its own T_b
     for (int p = 0; p < b->B; ++p) {
@@ -229,29 +226,24 @@ int demix_on_device(oiva_batch* b, int proj_back) {
     return OIVA_OK;
 }
 
-void free_all(oiva_batch* b) {
-    (void)drop_graphs(b);
-    for (void* q : {(void*)b->X_owned, (void*)b->What, (void*)b->What64, (void*)b->Cx, (void*)b->Vpart, (void*)b->Ppart, (void*)b->R,
-                    (void*)b->wscale, (void*)b->Spart, (void*)b->Y, (void*)b->Y128, (void*)b->Xr, (void*)b->probs_dev})
-        if (q) (void)hipFree(q);
-    for (void* q : b->og_bufs) (void)hipFree(q);
-    for (void* q : b->il_bufs) (void)hipFree(q);
-    for (hipEvent_t& e : b->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
+// X of the batch is now the array at X (its own copy or the caller's): captured graphs hold the pointer, Cx is of the old one
+int install_x(oiva_batch* b, const float2* X) {
+    if (b->X != X) {
+        OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+        const int rc = drop_graphs(b);
+        if (rc) return rc;
+    }
+    b->X = X;
+    b->have_x = true;
+    b->have_cx = false;
+    return OIVA_OK;
 }
 
 // stream, events, the problem table and the buffers of a new batch of frames[p] frames per problem; whatever it made before a
 // failure is the caller's to free
 int fill_batch(oiva_batch* b, const std::vector<int>& frames, void* stream) {
     const int device = b->device, B = b->B, T = b->T, F = b->F, M = b->M, K = b->K;
-    if (stream) {
-        b->stream = static_cast<hipStream_t>(stream);
-    } else {
-        OIVA_TRY_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-        b->own_stream = true;
-    }
-    for (hipEvent_t& e : b->ev) OIVA_TRY_HIP(hipEventCreate(&e));
+    OIVA_TRY_HIP(b->stream.open(stream, 5));
     // every problem's record from its own T_b: functions of T_b, F, M, K alone (never of B); the grids (nsplit, pw_nsplit, tcp,
     // rblocks) take the largest
     b->kp = pow_sources_per_pass(M, K);
@@ -285,18 +277,18 @@ int fill_batch(oiva_batch* b, const std::vector<int>& frames, void* stream) {
     }
     b->frames_total = x_off;
     const size_t ppart_floats = p_off, r_floats = r_off;
-    OIVA_TRY_HIP(dev_malloc(&b->probs_dev, (size_t)B * sizeof(RaggedProblem)));
+    OIVA_TRY_HIP(b->mem.take_one(&b->probs_dev, (size_t)B * sizeof(RaggedProblem)));
     OIVA_TRY_HIP(hipMemcpy(b->probs_dev, b->probs.data(), (size_t)B * sizeof(RaggedProblem), hipMemcpyHostToDevice));
     const size_t MM = (size_t)M * M;
-    OIVA_TRY_HIP(dev_malloc(&b->What, nbins(b) * MM * sizeof(float2)));
-    OIVA_TRY_HIP(dev_malloc(&b->What64, nbins(b) * MM * sizeof(double2)));
-    OIVA_TRY_HIP(dev_malloc(&b->Cx, nbins(b) * MM * sizeof(double)));
-    OIVA_TRY_HIP(dev_malloc(&b->Vpart, ((size_t)b->nsplit * nbins(b) * K * MM + 2) * sizeof(double)));   // sum_vpart reads idx + 1
-    OIVA_TRY_HIP(dev_malloc(&b->Ppart, ppart_floats * sizeof(float)));
-    OIVA_TRY_HIP(dev_malloc(&b->R, r_floats * sizeof(float)));
+    OIVA_TRY_HIP(b->mem.take_one(&b->What, nbins(b) * MM * sizeof(float2)));
+    OIVA_TRY_HIP(b->mem.take_one(&b->What64, nbins(b) * MM * sizeof(double2)));
+    OIVA_TRY_HIP(b->mem.take_one(&b->Cx, nbins(b) * MM * sizeof(double)));
+    OIVA_TRY_HIP(b->mem.take_one(&b->Vpart, ((size_t)b->nsplit * nbins(b) * K * MM + 2) * sizeof(double)));   // sum_vpart reads idx + 1
+    OIVA_TRY_HIP(b->mem.take_one(&b->Ppart, ppart_floats * sizeof(float)));
+    OIVA_TRY_HIP(b->mem.take_one(&b->R, r_floats * sizeof(float)));
     OIVA_TRY_HIP(hipMemset(b->R, 0, r_floats * sizeof(float)));      // (the pad rows behind every problem's r)
-    OIVA_TRY_HIP(dev_malloc(&b->wscale, (size_t)B * K * sizeof(float)));
-    OIVA_TRY_HIP(dev_malloc(&b->Spart, (size_t)spart_splits * F * K * 3 * sizeof(float)));
+    OIVA_TRY_HIP(b->mem.take_one(&b->wscale, (size_t)B * K * sizeof(float)));
+    OIVA_TRY_HIP(b->mem.take_one(&b->Spart, (size_t)spart_splits * F * K * 3 * sizeof(float)));
     return OIVA_OK;
 }
 
@@ -348,12 +340,11 @@ int check_ilrma(oiva_batch* b, bool begun) {
 int create_batch(oiva_batch** out, int device, const std::vector<int>& frames, int F, int M, int K, int model, void* stream) {
     DeviceGuard guard(device);
     oiva_batch* b = new oiva_batch;
-    b->device = device;
+    b->device = b->mem.device = device;
     b->B = (int)frames.size(), b->T = *std::max_element(frames.begin(), frames.end()), b->F = F, b->M = M, b->K = K, b->model = model;
     const int rc = fill_batch(b, frames, stream);
     if (rc) {
-        free_all(b);
-        delete b;
+        oiva_batch_destroy(b);
         return rc;
     }
     *out = b;
@@ -401,7 +392,9 @@ int oiva_batch_destroy(oiva_batch* b) {
     if (!b) return OIVA_OK;
     DeviceGuard guard(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    free_all(b);
+    (void)drop_graphs(b);
+    b->mem.clear();
+    b->stream.close();
     delete b;
     return OIVA_OK;
 }
@@ -410,47 +403,22 @@ int oiva_batch_set_x_host(oiva_batch* b, const void* X, int f64) {
     OIVA_NEED(b && X, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(b->device);
     const size_t n = b->frames_total * b->F * b->M;
-    if (!b->X_owned) OIVA_TRY_HIP(dev_malloc(&b->X_owned, n * sizeof(float2)));
+    if (!b->X_owned) OIVA_TRY_HIP(b->mem.take_one(&b->X_owned, n * sizeof(float2)));
     OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
     if (f64) {
-        // converted on the device, through a bounded staging buffer
-        const size_t chunk = std::min(n, kStageBytes / sizeof(double2));
-        double2* stage_buf = nullptr;
-        OIVA_TRY_HIP(dev_malloc(&stage_buf, chunk * sizeof(double2)));
-        hipError_t e = hipSuccess;
-        for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += chunk) {
-            const size_t m = std::min(chunk, n - i0);
-            e = hipMemcpy(stage_buf, static_cast<const double2*>(X) + i0, m * sizeof(double2), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = launch_cast_c128_to_c64(b->stream, stage_buf, b->X_owned + i0, (long long)m);
-            if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-        }
-        (void)hipFree(stage_buf);
-        OIVA_TRY_HIP(e);
+        // converted on the device, through a bounded staging buffer: flat, "rows" of one element
+        OIVA_TRY_HIP(staged_copy_c128(true, b->stream, const_cast<void*>(X), 0, b->X_owned, 1, (long long)n, kStageBytes,
+                                      b->device, Mem::plain));
     } else {
         OIVA_TRY_HIP(hipMemcpy(b->X_owned, X, n * sizeof(float2), hipMemcpyHostToDevice));
     }
-    if (b->X != b->X_owned) {          // captured graphs hold the pointer of X
-        const int rc = drop_graphs(b);
-        if (rc) return rc;
-    }
-    b->X = b->X_owned;
-    b->have_x = true;
-    b->have_cx = false;
-    return OIVA_OK;
+    return install_x(b, b->X_owned);
 }
 
 int oiva_batch_set_x_dev(oiva_batch* b, const void* X_dev) {
     OIVA_NEED(b && X_dev, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(b->device);
-    if (b->X != X_dev) {
-        OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
-        const int rc = drop_graphs(b);
-        if (rc) return rc;
-    }
-    b->X = static_cast<const float2*>(X_dev);
-    b->have_x = true;
-    b->have_cx = false;
-    return OIVA_OK;
+    return install_x(b, static_cast<const float2*>(X_dev));
 }
 
 int oiva_batch_covariance(oiva_batch* b) {
@@ -523,7 +491,7 @@ int oiva_batch_demix(oiva_batch* b, void* Y_host, int f64, int proj_back) {
     if (rc) return rc;
     const size_t ny = b->frames_total * b->F * b->K;
     if (f64) {
-        if (!b->Y128) OIVA_TRY_HIP(dev_malloc(&b->Y128, ny * sizeof(double2)));
+        if (!b->Y128) OIVA_TRY_HIP(b->mem.take_one(&b->Y128, ny * sizeof(double2)));
         OIVA_TRY_HIP(launch_cast_c64_to_c128(b->stream, b->Y, b->Y128, (long long)ny));
     }
     OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
@@ -579,16 +547,18 @@ int oiva_batch_time_stages(oiva_batch* b, int n, float* total_ms, float* per_sta
     if (per_stage_ms) {
         double acc[4] = {0., 0., 0., 0.};
         for (int i = 0; i < n; ++i) {
-            OIVA_TRY_HIP(hipEventRecord(b->ev[0], b->stream));
+            // (back to back, one wait for the last: not four brackets with a wait each)
+            const std::vector<hipEvent_t>& ev = b->stream.events;
+            OIVA_TRY_HIP(hipEventRecord(ev[0], b->stream));
             for (int s = 0; s < 4; ++s) {
                 rc = stage(b, s);
                 if (rc) return rc;
-                OIVA_TRY_HIP(hipEventRecord(b->ev[s + 1], b->stream));
+                OIVA_TRY_HIP(hipEventRecord(ev[s + 1], b->stream));
             }
-            OIVA_TRY_HIP(hipEventSynchronize(b->ev[4]));
+            OIVA_TRY_HIP(hipEventSynchronize(ev[4]));
             for (int s = 0; s < 4; ++s) {
                 float ms = 0.f;
-                OIVA_TRY_HIP(hipEventElapsedTime(&ms, b->ev[s], b->ev[s + 1]));
+                OIVA_TRY_HIP(hipEventElapsedTime(&ms, ev[s], ev[s + 1]));
                 acc[s] += ms;
             }
         }
@@ -598,12 +568,9 @@ int oiva_batch_time_stages(oiva_batch* b, int n, float* total_ms, float* per_sta
     rc = graph_for(b, std::min(n, kGraphMaxIters), &g);
     if (rc) return rc;
     OIVA_TRY_HIP(hipGraphLaunch(g, b->stream));          // (warm)
-    OIVA_TRY_HIP(hipEventRecord(b->ev[0], b->stream));
-    OIVA_TRY_HIP(hipGraphLaunch(g, b->stream));
-    OIVA_TRY_HIP(hipEventRecord(b->ev[1], b->stream));
-    OIVA_TRY_HIP(hipEventSynchronize(b->ev[1]));
     float ms = 0.f;
-    OIVA_TRY_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+    rc = b->stream.elapsed_ms(0, 1, [&] { OIVA_TRY_HIP(hipGraphLaunch(g, b->stream)); return (int)OIVA_OK; }, &ms);
+    if (rc) return rc;
     *total_ms = ms / (float)std::min(n, kGraphMaxIters);
     return OIVA_OK;
 }
@@ -616,12 +583,11 @@ oiva_status oiva_batch_get_cx(oiva_batch* b, void* Cx_host, int f64) {
     const size_t n = nbins(b) * b->M * b->M;
     const size_t bytes = n * (f64 ? sizeof(double2) : sizeof(float2));
     void* full = nullptr;
-    OIVA_TRY_HIP(dev_malloc(&full, bytes));
-    hipError_t e = launch_unpack_herm(b->stream, b->Cx, full, f64 != 0, (long long)nbins(b), b->M);
-    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-    if (e == hipSuccess) e = hipMemcpy(Cx_host, full, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(full);
-    OIVA_TRY_HIP(e);
+    ScopedDev scratch;
+    OIVA_TRY_HIP(scratch.take_one(&full, bytes));
+    OIVA_TRY_HIP(launch_unpack_herm(b->stream, b->Cx, full, f64 != 0, (long long)nbins(b), b->M));
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(Cx_host, full, bytes, hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 
@@ -635,17 +601,20 @@ oiva_status oiva_batch_ogive_begin(oiva_batch* b, int update_mode, int model) {
     OIVA_NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
     DeviceGuard guard(b->device);
     const size_t nb = nbins(b), M = b->M, B = b->B;
-    if (b->og_bufs.empty()) {
-        AllocChain alloc;
-        alloc.keep = &b->og_bufs;
-        alloc_ogive_state(b->og.bin, nb, M, alloc);      // (its ctrl / maxdelta: reset by ogive_init_kernel; the batch keeps its own per problem)
-        alloc(&b->og.done, B * sizeof(int));
-        alloc(&b->og.epochs, B * sizeof(int));
-        alloc(&b->og.maxdelta, B * sizeof(double));
-        alloc(&b->og.runmax, B * sizeof(unsigned long long));
-        alloc(&b->og.ticket, B * sizeof(unsigned));
-        alloc(&b->Opart, (size_t)b->osplit * nb * (2 * M + 1) * sizeof(double));
-        if (!alloc.ok()) return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
+    if (!b->Opart) {                     // (the last of the state: all of it or none)
+        DeviceArena& mem = b->mem;
+        const size_t before = mem.mark();
+        alloc_ogive_state(b->og.bin, nb, M, mem);        // (its ctrl / maxdelta: reset by ogive_init_kernel; the batch keeps its own per problem)
+        mem.take(&b->og.done, B * sizeof(int));
+        mem.take(&b->og.epochs, B * sizeof(int));
+        mem.take(&b->og.maxdelta, B * sizeof(double));
+        mem.take(&b->og.runmax, B * sizeof(unsigned long long));
+        mem.take(&b->og.ticket, B * sizeof(unsigned));
+        mem.take(&b->Opart, (size_t)b->osplit * nb * (2 * M + 1) * sizeof(double));
+        if (!mem.ok()) {
+            mem.release_to(before);
+            return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(mem.status()));
+        }
     }
     OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
     if (b->og_graph) {                   // captured for the previous update mode / model
@@ -736,24 +705,26 @@ oiva_status oiva_batch_ilrma_begin(oiva_batch* b, int n_components, const double
     for (size_t i = 0; i < nv; ++i) OIVA_NEED(V0[i] > 0. && std::isfinite(V0[i]), OIVA_ERR_ARG, "V0 must be strictly positive");
     DeviceGuard guard(b->device);
     OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
-    if (!b->il_bufs.empty() && b->il.L != n_components) {      // (another component count: the state is sized by it)
-        for (void* q : b->il_bufs) (void)hipFree(q);
-        b->il_bufs.clear();
-    }
+    DeviceArena& mem = b->mem;
+    IlrmaState& il = b->il;
+    if (il.lam && il.L != n_components)                        // (another component count: the state is sized by it)
+        for (double** q : {&il.Tn, &il.Vn, &il.P, &il.R, &il.Upart, &il.rowsum, &il.lam}) mem.release(q);
     b->il_ready = false;
-    if (b->il_bufs.empty()) {
-        AllocChain alloc;
-        alloc.keep = &b->il_bufs;
-        b->il = IlrmaState{};
-        b->il.L = n_components;
-        alloc(&b->il.Tn, nt * sizeof(double));
-        alloc(&b->il.Vn, nv * sizeof(double));
-        alloc(&b->il.P, npr * sizeof(double));
-        alloc(&b->il.R, npr * sizeof(double));
-        alloc(&b->il.Upart, 2 * (size_t)ilrma_v_chunks(b->F) * nv * sizeof(double));
-        alloc(&b->il.rowsum, B * K * F * sizeof(double));
-        alloc(&b->il.lam, B * K * sizeof(double));
-        if (!alloc.ok()) return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
+    if (!il.lam) {                       // (the last of the state: all of it or none)
+        const size_t before = mem.mark();
+        il = IlrmaState{};
+        il.L = n_components;
+        mem.take(&il.Tn, nt * sizeof(double));
+        mem.take(&il.Vn, nv * sizeof(double));
+        mem.take(&il.P, npr * sizeof(double));
+        mem.take(&il.R, npr * sizeof(double));
+        mem.take(&il.Upart, 2 * (size_t)ilrma_v_chunks(b->F) * nv * sizeof(double));
+        mem.take(&il.rowsum, B * K * F * sizeof(double));
+        mem.take(&il.lam, B * K * sizeof(double));
+        if (!mem.ok()) {
+            mem.release_to(before);
+            return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(mem.status()));
+        }
     }
     OIVA_TRY_HIP(hipMemcpy(b->il.Tn, T0, nt * sizeof(double), hipMemcpyHostToDevice));
     OIVA_TRY_HIP(hipMemcpy(b->il.Vn, V0, nv * sizeof(double), hipMemcpyHostToDevice));
@@ -837,12 +808,8 @@ oiva_status oiva_batch_ilrma_time_stages(oiva_batch* b, int n, float* per_stage_
     double acc[kIlrmaStages] = {};
     for (int e = 0; e < n; ++e) {
         for (int s = 0; s < kIlrmaStages; ++s) {
-            OIVA_TRY_HIP(hipEventRecord(b->ev[0], b->stream));
-            if ((rc = ilrma_stage(b, s))) return rc;
-            OIVA_TRY_HIP(hipEventRecord(b->ev[1], b->stream));
-            OIVA_TRY_HIP(hipEventSynchronize(b->ev[1]));
             float ms = 0.f;
-            OIVA_TRY_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+            if ((rc = b->stream.elapsed_ms(0, 1, [&] { return ilrma_stage(b, s); }, &ms))) return rc;
             acc[s] += ms;
         }
     }
@@ -874,7 +841,7 @@ oiva_status oiva_batch_project_dev(oiva_batch* b, void** Xr_dev) {
     const int rc = check_ready(b);
     if (rc) return rc;
     DeviceGuard guard(b->device);
-    if (!b->Xr) OIVA_TRY_HIP(dev_malloc(&b->Xr, b->frames_total * b->F * b->K * sizeof(float2)));
+    if (!b->Xr) OIVA_TRY_HIP(b->mem.take_one(&b->Xr, b->frames_total * b->F * b->K * sizeof(float2)));
     // auxiva_pca.py:79-81 for every problem in one launch, from the problem table
     OIVA_TRY_HIP(launch_pca_project(b->stream, b->X, b->What, b->Xr, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit));
     OIVA_TRY_HIP(hipStreamSynchronize(b->stream));

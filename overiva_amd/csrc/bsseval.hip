@@ -23,10 +23,6 @@ namespace {
 constexpr int kStages = 4;           // correlate, factor, solve, criteria
 constexpr int kMaxVec = kBssMaxSrc * kBssMaxSrc + kBssMaxSrc;
 constexpr int kMaxGridZ = 65535;
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
 }  // namespace
 
 struct oiva_bsseval {
@@ -36,48 +32,34 @@ struct oiva_bsseval {
     int done = -1;                 // last stage completed on all rooms (staged use), -1: none; signals set: have_sig
     bool have_sig = false, have_result = false;
     long long sig_total = 0, seg_total = 0, part_total = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    HandleStream stream;           // two events: the bracket of oiva_bsseval_time_stages
+    DeviceArena mem;               // every buffer below, pooled
     std::vector<BssRoom> rooms;
-    std::vector<Buf> bufs;
     BssRoom* rooms_dev = nullptr;
     int2* segs_dev = nullptr;
     double *ref = nullptr, *est = nullptr, *part = nullptr, *Epart = nullptr, *lag = nullptr, *E = nullptr;
     double *G = nullptr, *Gf = nullptr, *Hf = nullptr, *thr = nullptr, *C = nullptr, *c = nullptr, *qL = nullptr, *qS = nullptr;
     double* crit = nullptr;        // sdr, sir, sar: 3 x (B, N, N)
     int* flag = nullptr;
-    hipEvent_t ev[2] = {};
 };
 
 namespace {
 
 template <class P>
-hipError_t take(oiva_bsseval* p, P** out, size_t bytes) {
-    void* v = nullptr;
-    const hipError_t e = big_alloc(p->device, &v, std::max<size_t>(bytes, 8));
-    if (e != hipSuccess) return e;
-    p->bufs.push_back({v, std::max<size_t>(bytes, 8)});
-    *out = static_cast<P*>(v);
-    return hipSuccess;
-}
-
-void give_back(oiva_bsseval* p, size_t keep) {
-    while (p->bufs.size() > keep) {
-        big_free(p->device, p->bufs.back().p, p->bufs.back().bytes);
-        p->bufs.pop_back();
-    }
+void take(oiva_bsseval* p, P** out, size_t bytes) {
+    p->mem.take(out, std::max<size_t>(bytes, 8), Mem::pooled);
 }
 
 // the buffers whose size follows the group: both copies of G, the diagonal blocks, the block sums of the quadratic forms
 hipError_t alloc_group(oiva_bsseval* p, int group) {
     const size_t nt = (size_t)p->N * p->Lf, Lf = p->Lf, N = p->N;
     const size_t nrbL = (nt + kBssBlock - 1) / kBssBlock, nrbS = (Lf + kBssBlock - 1) / kBssBlock;
-    hipError_t e = take(p, &p->G, group * nt * nt * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->Gf, group * nt * nt * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->Hf, group * N * Lf * Lf * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->qL, group * kMaxVec * nrbL * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->qS, group * N * kMaxVec * nrbS * sizeof(double));
-    return e;
+    take(p, &p->G, group * nt * nt * sizeof(double));
+    take(p, &p->Gf, group * nt * nt * sizeof(double));
+    take(p, &p->Hf, group * N * Lf * Lf * sizeof(double));
+    take(p, &p->qL, group * kMaxVec * nrbL * sizeof(double));
+    take(p, &p->qS, group * N * kMaxVec * nrbS * sizeof(double));
+    return p->mem.status();
 }
 
 int stage_correlate(oiva_bsseval* p) {
@@ -151,7 +133,7 @@ oiva_status oiva_bsseval_create(oiva_bsseval** out, int device, int B, const int
     OIVA_NEED(device >= 0 && device < ndev, OIVA_ERR_ARG, "no such device");
     DeviceGuard guard(device);
     oiva_bsseval* p = new oiva_bsseval();
-    p->device = device;
+    p->device = p->mem.device = device;
     p->B = B, p->N = N, p->Lf = filter_length, p->diag_only = diag_only ? 1 : 0;
     const size_t per_seg = (size_t)2 * N * N * filter_length;
     p->rooms.resize(B);
@@ -169,41 +151,34 @@ oiva_status oiva_bsseval_create(oiva_bsseval** out, int device, int B, const int
         p->seg_total += r.nseg;
         for (int g = 0; g < r.nseg; ++g) segs_host.push_back(make_int2(b, g));
     }
-    hipError_t e = hipSuccess;
-    if (stream) {
-        p->stream = static_cast<hipStream_t>(stream);
-    } else {
-        e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-        p->own_stream = e == hipSuccess;
-    }
-    for (hipEvent_t& ev : p->ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
+    p->mem.note(p->stream.open(stream, 2));
     const size_t nt = (size_t)N * filter_length, nn = (size_t)B * N * N;
-    if (e == hipSuccess) e = take(p, &p->rooms_dev, (size_t)B * sizeof(BssRoom));
-    if (e == hipSuccess) e = take(p, &p->segs_dev, segs_host.size() * sizeof(int2));
-    if (e == hipSuccess) e = take(p, &p->ref, (size_t)p->sig_total * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->est, (size_t)p->sig_total * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->part, (size_t)p->part_total * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->Epart, (size_t)p->seg_total * N * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->lag, (size_t)B * per_seg * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->E, (size_t)B * N * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->thr, (size_t)B * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->C, (size_t)B * N * nt * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->c, (size_t)B * N * nt * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->crit, 3 * nn * sizeof(double));
-    if (e == hipSuccess) e = take(p, &p->flag, (size_t)B * sizeof(int));
+    take(p, &p->rooms_dev, (size_t)B * sizeof(BssRoom));
+    take(p, &p->segs_dev, segs_host.size() * sizeof(int2));
+    take(p, &p->ref, (size_t)p->sig_total * sizeof(double));
+    take(p, &p->est, (size_t)p->sig_total * sizeof(double));
+    take(p, &p->part, (size_t)p->part_total * sizeof(double));
+    take(p, &p->Epart, (size_t)p->seg_total * N * sizeof(double));
+    take(p, &p->lag, (size_t)B * per_seg * sizeof(double));
+    take(p, &p->E, (size_t)B * N * sizeof(double));
+    take(p, &p->thr, (size_t)B * sizeof(double));
+    take(p, &p->C, (size_t)B * N * nt * sizeof(double));
+    take(p, &p->c, (size_t)B * N * nt * sizeof(double));
+    take(p, &p->crit, 3 * nn * sizeof(double));
+    take(p, &p->flag, (size_t)B * sizeof(int));
+    hipError_t e = p->mem.status();
     if (e == hipSuccess) e = hipMemcpy(p->rooms_dev, p->rooms.data(), (size_t)B * sizeof(BssRoom), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->segs_dev, segs_host.data(), segs_host.size() * sizeof(int2), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         // as many rooms per group as the grid admits and the memory holds: halve until the allocation succeeds
         int group = std::min(B, kMaxGridZ / N);
         if (max_group > 0) group = std::min(group, max_group);
-        const size_t keep = p->bufs.size();
+        const size_t keep = p->mem.mark();
         for (;;) {
             e = alloc_group(p, group);
             if (e != hipErrorOutOfMemory || group == 1) break;
             (void)hipGetLastError();
-            give_back(p, keep);
+            p->mem.release_to(keep);
             group = (group + 1) / 2;
         }
         p->group = group;
@@ -220,10 +195,8 @@ oiva_status oiva_bsseval_destroy(oiva_bsseval* p) {
     if (!p) return OIVA_OK;
     DeviceGuard guard(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    give_back(p, 0);
-    for (hipEvent_t& ev : p->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (p->own_stream && p->stream) (void)hipStreamDestroy(p->stream);
+    p->mem.clear();
+    p->stream.close();
     delete p;
     return OIVA_OK;
 }
@@ -355,13 +328,8 @@ oiva_status oiva_bsseval_time_stages(oiva_bsseval* p, int n, float* per_stage_ms
         for (int g0 = -1; g0 < p->B; g0 = g0 < 0 ? 0 : g0 + p->group) {       // (-1: the one pass over all rooms, correlate)
             const int rooms = std::min(p->group, p->B - std::max(g0, 0));
             for (int stage = g0 < 0 ? 0 : 1; stage < (g0 < 0 ? 1 : kStages); ++stage) {
-                OIVA_TRY_HIP(hipEventRecord(p->ev[0], p->stream));
-                rc = run_stage(p, stage, std::max(g0, 0), rooms);
-                if (rc) return rc;
-                OIVA_TRY_HIP(hipEventRecord(p->ev[1], p->stream));
-                OIVA_TRY_HIP(hipEventSynchronize(p->ev[1]));
                 float ms = 0.f;
-                OIVA_TRY_HIP(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
+                if ((rc = p->stream.elapsed_ms(0, 1, [&] { return run_stage(p, stage, std::max(g0, 0), rooms); }, &ms))) return rc;
                 sum[stage] += ms;
             }
         }

@@ -30,8 +30,8 @@ struct oiva_bstft {
     int device = 0;
     int B = 0, M = 0, L = 0, hop = 0, F = 0;
     long long samples_total = 0, frames_total = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    HandleStream stream;      // events of the analysis: [0..4], of the synthesis: [5..9]
+    DeviceArena mem;
     std::vector<BstftRoom> rooms;
     BstftRoom* rooms_dev = nullptr;
     hipfftHandle fwd = 0, inv = 0;
@@ -43,7 +43,6 @@ struct oiva_bstft {
     float* frames = nullptr;  // (frames_total * M, L)
     float2* spec = nullptr;   // (frames_total * M, F)
     float2* X = nullptr;      // (frames_total, F, M)
-    hipEvent_t ev[10] = {};   // analysis: ev[0..4], synthesis: ev[5..9]
     bool timed_a = false, timed_s = false;
 };
 
@@ -89,33 +88,20 @@ oiva_status oiva_bstft_create(oiva_bstft** out, int device, int B, const int* n_
         p->samples_total += r.n;
         p->frames_total += r.T;
     }
-    AllocChain alloc;
-    if (stream) {
-        p->stream = static_cast<hipStream_t>(stream);
-    } else {
-        alloc.err = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-        p->own_stream = alloc.ok();
-    }
-    for (hipEvent_t& ev : p->ev)
-        if (alloc.ok()) alloc.err = hipEventCreate(&ev);
+    DeviceArena& mem = p->mem;
+    mem.note(p->stream.open(stream, 10));
     const size_t rows = (size_t)p->frames_total * M;
-    alloc(&p->x, (size_t)std::max(p->samples_total, p->frames_total * hop) * M * sizeof(float));
-    alloc(&p->frames, rows * frame * sizeof(float));
-    alloc(&p->spec, rows * F * sizeof(float2));
-    alloc(&p->X, rows * F * sizeof(float2));
-    alloc(&p->rooms_dev, (size_t)B * sizeof(BstftRoom));
-    if (alloc.ok()) alloc.err = hipMemcpy(p->rooms_dev, p->rooms.data(), (size_t)B * sizeof(BstftRoom), hipMemcpyHostToDevice);
-    if (win_a) {
-        alloc(&p->win_a, frame * sizeof(float));
-        if (alloc.ok()) alloc.err = hipMemcpy(p->win_a, win_a, frame * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (win_s) {
-        alloc(&p->win_s, frame * sizeof(float));
-        if (alloc.ok()) alloc.err = hipMemcpy(p->win_s, win_s, frame * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (!alloc.ok()) {
+    mem.take(&p->x, (size_t)std::max(p->samples_total, p->frames_total * hop) * M * sizeof(float));
+    mem.take(&p->frames, rows * frame * sizeof(float));
+    mem.take(&p->spec, rows * F * sizeof(float2));
+    mem.take(&p->X, rows * F * sizeof(float2));
+    mem.take_filled(&p->rooms_dev, p->rooms.data(), (size_t)B * sizeof(BstftRoom));
+    if (win_a) mem.take_filled(&p->win_a, win_a, frame * sizeof(float));
+    if (win_s) mem.take_filled(&p->win_s, win_s, frame * sizeof(float));
+    if (!mem.ok()) {
+        const hipError_t e = mem.status();
         oiva_bstft_destroy(p);
-        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
+        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(e));
     }
     *out = p;
     return OIVA_OK;
@@ -127,12 +113,8 @@ oiva_status oiva_bstft_destroy(oiva_bstft* p) {
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     if (p->have_fwd) (void)hipfftDestroy(p->fwd);
     if (p->have_inv) (void)hipfftDestroy(p->inv);
-    void* bufs[] = {p->win_a, p->win_s, p->x, p->frames, p->spec, p->X, p->rooms_dev};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (hipEvent_t& ev : p->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (p->own_stream && p->stream) (void)hipStreamDestroy(p->stream);
+    p->mem.clear();
+    p->stream.close();
     delete p;
     return OIVA_OK;
 }
@@ -155,15 +137,15 @@ oiva_status oiva_bstft_analysis(oiva_bstft* p, const float* x_host, void** X_dev
         OIVA_TRY_FFT(hipfftSetStream(p->fwd, p->stream));
         p->have_fwd = true;
     }
-    OIVA_TRY_HIP(hipEventRecord(p->ev[0], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[0], p->stream));
     OIVA_TRY_HIP(hipMemcpyAsync(p->x, x_host, (size_t)p->samples_total * M * sizeof(float), hipMemcpyHostToDevice, p->stream));
-    OIVA_TRY_HIP(hipEventRecord(p->ev[1], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[1], p->stream));
     OIVA_TRY_HIP(launch_bstft_frame(p->stream, p->x, p->win_a, p->frames, p->rooms_dev, p->B, p->frames_total, M, L, p->hop));
-    OIVA_TRY_HIP(hipEventRecord(p->ev[2], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[2], p->stream));
     OIVA_TRY_FFT(hipfftExecR2C(p->fwd, p->frames, reinterpret_cast<hipfftComplex*>(p->spec)));
-    OIVA_TRY_HIP(hipEventRecord(p->ev[3], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[3], p->stream));
     OIVA_TRY_HIP(launch_bstft_to_tfc(p->stream, p->spec, p->X, p->frames_total, F, M));
-    OIVA_TRY_HIP(hipEventRecord(p->ev[4], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[4], p->stream));
     OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     p->timed_a = true;
     *X_dev = p->X;
@@ -186,15 +168,15 @@ oiva_status oiva_bstft_synthesis_dev(oiva_bstft* p, const void* Y_dev, int K, fl
         p->inv_chan = K;
     }
     const long long n_out = p->frames_total * p->hop;
-    OIVA_TRY_HIP(hipEventRecord(p->ev[5], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[5], p->stream));
     OIVA_TRY_HIP(launch_bstft_from_tfc(p->stream, static_cast<const float2*>(Y_dev), p->spec, p->frames_total, F, K));
-    OIVA_TRY_HIP(hipEventRecord(p->ev[6], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[6], p->stream));
     OIVA_TRY_FFT(hipfftExecC2R(p->inv, reinterpret_cast<hipfftComplex*>(p->spec), p->frames));
-    OIVA_TRY_HIP(hipEventRecord(p->ev[7], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[7], p->stream));
     OIVA_TRY_HIP(launch_bstft_overlap_add(p->stream, p->frames, p->win_s, p->x, p->rooms_dev, p->B, n_out, K, L, p->hop));
-    OIVA_TRY_HIP(hipEventRecord(p->ev[8], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[8], p->stream));
     OIVA_TRY_HIP(hipMemcpyAsync(y_host, p->x, (size_t)n_out * K * sizeof(float), hipMemcpyDeviceToHost, p->stream));
-    OIVA_TRY_HIP(hipEventRecord(p->ev[9], p->stream));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[9], p->stream));
     OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     p->timed_s = true;
     return OIVA_OK;
@@ -205,9 +187,9 @@ oiva_status oiva_bstft_phase_ms(oiva_bstft* p, float* ms) {
     DeviceGuard guard(p->device);
     for (int i = 0; i < kPhases; ++i) ms[i] = 0.f;
     if (p->timed_a)
-        for (int i = 0; i < 4; ++i) OIVA_TRY_HIP(hipEventElapsedTime(&ms[i], p->ev[i], p->ev[i + 1]));
+        for (int i = 0; i < 4; ++i) OIVA_TRY_HIP(hipEventElapsedTime(&ms[i], p->stream.events[i], p->stream.events[i + 1]));
     if (p->timed_s)
-        for (int i = 0; i < 4; ++i) OIVA_TRY_HIP(hipEventElapsedTime(&ms[4 + i], p->ev[5 + i], p->ev[6 + i]));
+        for (int i = 0; i < 4; ++i) OIVA_TRY_HIP(hipEventElapsedTime(&ms[4 + i], p->stream.events[5 + i], p->stream.events[6 + i]));
     return OIVA_OK;
 }
 

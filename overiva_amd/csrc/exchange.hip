@@ -26,6 +26,7 @@ extern "C" {
 struct oiva_xchg {
     int device = 0, rank = 0, world = 0;
     size_t slot_bytes = 0;       // one rank's part (slots are contiguous: the result is a plain concatenation)
+    oiva::DeviceArena mem;       // block and ticket
     char* block = nullptr;       // fine-grained: [2][world][slot_bytes] then 2 counters (64 bytes apart)
     unsigned* ticket = nullptr;  // workgroups of the push kernel that have stored their chunk
     char* peer[OIVA_XCHG_MAX_RANKS] = {};   // every rank's block as mapped here (own = block)
@@ -91,20 +92,18 @@ int oiva_xchg_create(oiva_xchg** out, int device, int rank, int world, long long
     DeviceGuard guard(device);
     OIVA_TRY_HIP(hipSetDevice(device));      // (the validation of `device`; the guard puts the caller's back)
     auto* x = new oiva_xchg;
-    x->device = device;
+    x->device = x->mem.device = device;
     x->rank = rank;
     x->world = world;
     x->slot_bytes = (size_t)part_bytes;
     const size_t total = buffers_bytes(world, x->slot_bytes) + 2 * kCounterStride;
-    hipError_t e = hipExtMallocWithFlags((void**)&x->block, total, hipDeviceMallocFinegrained);
+    hipError_t e = x->mem.take_one(&x->block, total, Mem::fine);
     if (e == hipSuccess) e = hipMemset(x->block, 0, total);
-    if (e == hipSuccess) e = dev_malloc(&x->ticket, sizeof(unsigned));
+    if (e == hipSuccess) e = x->mem.take_one(&x->ticket, sizeof(unsigned));
     if (e == hipSuccess) e = hipMemset(x->ticket, 0, sizeof(unsigned));
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        if (x->block) (void)hipFree(x->block);
-        if (x->ticket) (void)hipFree(x->ticket);
-        delete x;
+        oiva_xchg_destroy(x);
         return fail_with(OIVA_ERR_HIP, std::string("exchange allocation: ") + hipGetErrorString(e));
     }
     x->peer[rank] = x->block;
@@ -204,11 +203,10 @@ int oiva_xchg_force(oiva_xchg* x, int epoch) {
     // nothing here may synchronise with it)
     unsigned* counter = reinterpret_cast<unsigned*>(x->block + buffers_bytes(x->world, x->slot_bytes) + (epoch & 1) * kCounterStride);
     const unsigned v = expected_count(x, epoch);
-    hipStream_t s = nullptr;
-    OIVA_TRY_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    HandleStream s;
+    OIVA_TRY_HIP(s.open(nullptr, 0));
     hipError_t e = hipMemcpyAsync(counter, &v, sizeof(v), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipStreamDestroy(s);
     OIVA_TRY_HIP(e);
     return OIVA_OK;
 }
@@ -219,8 +217,7 @@ int oiva_xchg_destroy(oiva_xchg* x) {
     (void)hipDeviceSynchronize();
     for (int r = 0; r < x->world; ++r)
         if (x->opened[r]) (void)hipIpcCloseMemHandle(x->peer[r]);
-    if (x->block) (void)hipFree(x->block);
-    if (x->ticket) (void)hipFree(x->ticket);
+    x->mem.clear();
     delete x;
     return OIVA_OK;
 }

@@ -8,6 +8,7 @@
 // while slab k + 1 is computed and while the copy threads move slab k - 1 from the ring into the caller's array, whose pages
 // overiva() had faulted in by the same threads while the iterations ran (oiva_host_prefault).
 #include "host_io.h"
+#include "host_util.h"
 
 #include <sys/mman.h>
 #include <unistd.h>
@@ -141,6 +142,35 @@ void host_copy_rows(void* dst, size_t dst_pitch, const void* src, size_t src_pit
 }
 
 int host_io_threads() { return pool().size(); }
+
+hipError_t staged_copy_c128(bool to_device, hipStream_t s, void* host, size_t pitch, float2* dev, size_t row_elems, long long rows,
+                            size_t stage_bound, int device, Mem kind) {
+    const size_t row = row_elems * sizeof(double2);
+    const long long slab = (long long)std::max<size_t>(1, std::min<size_t>((size_t)rows, stage_bound / row));
+    double2* stage = nullptr;
+    ScopedDev scratch(device);
+    hipError_t e = scratch.take_one(&stage, row * (size_t)slab, kind);
+    const bool flat = pitch == 0;      // one flat copy per slab, else a pitched one (also where the pitch is the row)
+    if (flat) pitch = row;
+    auto copy = [&](void* dst, size_t dpitch, const void* src, size_t spitch, long long nr, hipMemcpyKind dir) {
+        return flat ? hipMemcpy(dst, src, (size_t)nr * row, dir) : hipMemcpy2D(dst, dpitch, src, spitch, row, (size_t)nr, dir);
+    };
+    for (long long r0 = 0; r0 < rows && e == hipSuccess; r0 += slab) {
+        const long long nr = std::min(slab, rows - r0);
+        char* h = static_cast<char*>(host) + (size_t)r0 * pitch;
+        float2* d = dev + (size_t)r0 * row_elems;
+        if (to_device) {
+            e = copy(stage, row, h, pitch, nr, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = launch_cast_c128_to_c64(s, stage, d, nr * (long long)row_elems);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+        } else {
+            e = launch_cast_c64_to_c128(s, d, stage, nr * (long long)row_elems);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e == hipSuccess) e = copy(h, pitch, stage, row, nr, hipMemcpyDeviceToHost);
+        }
+    }
+    return e;
+}
 
 void host_prefault(void* ptr, size_t bytes, bool may_touch) {
     if (!ptr || bytes == 0) return;

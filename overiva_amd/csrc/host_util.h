@@ -1,9 +1,13 @@
-// The host layer shared by plan.hip, batch.hip, stft.hip, bstft.hip and exchange.hip: error plumbing, the current-device guard,
-// device allocation, graph capture and its cache, W_hat packing, the statistics geometry and the OGIVE per-bin state.  Host code
-// only: no kernels, no translation unit of its own (the allocation pool behind dev_malloc / big_alloc lives in plan.hip).
+// The host layer shared by plan.hip, batch.hip, bsseval.hip, stft.hip, bstft.hip and exchange.hip: error plumbing, the
+// current-device guard, the owner of a handle's device and pinned memory (DeviceArena) and of its stream and events (HandleStream),
+// graph capture and its cache, W_hat packing, the statistics geometry and the OGIVE per-bin state.  Host code only, no kernels.
+// What is state -- the last error, the allocators and their process-wide pool of large buffers, the count of live buffers --
+// is defined in host_util.hip; nothing else in the library frees device memory, an event or a stream (host_io.hip keeps its
+// process-wide pinned ring).
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -50,29 +54,157 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
-// ---- device allocation (defined next to the pool in plan.hip) ------------------------------------------------------------
+// ---- device allocation (host_util.hip) -------------------------------------------------------------------------------------
 // hipMalloc of the library: before an allocation fails for want of memory the pool's idle buffers go back to the driver and
-// the allocation is tried once more
+// the allocation is tried once more.  fine_malloc: fine-grained device memory (system-scope atomics, IPC exchange buffers).
+// Every free takes the byte count of its allocation: the library counts what it has handed out (oiva_test_live_buffers).
 hipError_t dev_malloc(void** out, size_t bytes);
-template <class P>
-hipError_t dev_malloc(P** out, size_t bytes) {
-    return dev_malloc(reinterpret_cast<void**>(out), bytes);
-}
+hipError_t fine_malloc(void** out, size_t bytes);
+void dev_free(void* ptr, size_t bytes);
+hipError_t pinned_malloc(void** out, size_t bytes);
+void pinned_free(void* ptr, size_t bytes);
 // buffers of >= 16 MB come from and go back to the process-wide pool (exact-size reuse, per device)
 hipError_t big_alloc(int dev, void** out, size_t bytes);
 void big_free(int dev, void* ptr, size_t bytes);
 
-// "allocate these N buffers, the first error wins": every call after a failure does nothing.  With `keep` every pointer is
-// also remembered there, for an owner that frees its buffers from one list.
-struct AllocChain {
-    hipError_t err = hipSuccess;
-    std::vector<void*>* keep = nullptr;
+enum class Mem { plain, pooled, pinned, fine };      // dev_malloc | big_alloc | pinned_malloc | fine_malloc
+
+// The one owner of a handle's device and pinned memory (or, on the stack, of a call's temporaries: ScopedDev).  The handle keeps
+// raw pointers; the arena remembers each buffer with its size and kind and gives all of them back in clear(), newest first.
+// take() chains as "allocate these N buffers, the first error wins": after a failure every take does nothing until status()
+// has handed the error over.  The pointer a buffer is taken into lives at least as long as the arena holds the buffer.
+class DeviceArena {
+public:
+    explicit DeviceArena(int device = 0) : device(device) {}
+    ~DeviceArena() { clear(); }
+    DeviceArena(const DeviceArena&) = delete;
+    DeviceArena& operator=(const DeviceArena&) = delete;
+
+    int device;                       // of the pooled kind
     bool ok() const { return err == hipSuccess; }
+    // a step between the takes of a chain (a memset, a copy, opening the stream) joins it: the first error wins
+    void note(hipError_t e) { err = ok() ? e : err; }
+    // the chain's error, which it hands over: the next chain starts clean
+    hipError_t status() { return std::exchange(err, hipSuccess); }
+
     template <class P>
-    void operator()(P** out, size_t bytes) {
+    void take(P** out, size_t bytes, Mem kind = Mem::plain) {
         if (!ok()) return;
-        err = dev_malloc(out, bytes);
-        if (keep && *out) keep->push_back(*out);
+        void* v = nullptr;
+        switch (kind) {
+            case Mem::plain: err = dev_malloc(&v, bytes); break;
+            case Mem::pooled: err = big_alloc(device, &v, bytes); break;
+            case Mem::pinned: err = pinned_malloc(&v, bytes); break;
+            case Mem::fine: err = fine_malloc(&v, bytes); break;
+        }
+        if (!ok()) return;
+        held.push_back({v, bytes, kind, out});
+        *out = static_cast<P*>(v);
+    }
+    // ... and filled from `bytes` of host memory (synchronous)
+    template <class P>
+    void take_filled(P** out, const void* host, size_t bytes) {
+        take(out, bytes);
+        if (ok()) err = hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice);
+    }
+    // one buffer outside a chain: its status at once
+    template <class P>
+    hipError_t take_one(P** out, size_t bytes, Mem kind = Mem::plain) {
+        take(out, bytes, kind);
+        return status();
+    }
+    size_t mark() const { return held.size(); }
+    // frees what was taken after mark(), newest first; a pointer that still holds such a buffer is nulled
+    void release_to(size_t mark) {
+        while (held.size() > mark) {
+            const Held h = held.back();
+            held.pop_back();
+            void* now = nullptr;      // (the slot is a P* of some P: read and nulled as bytes, not through a void* lvalue)
+            std::memcpy(&now, h.slot, sizeof now);
+            if (now == h.p) std::memset(h.slot, 0, sizeof now);
+            give_back(h);
+        }
+    }
+    // frees the buffer *ptr now and nulls the pointer; a pointer that is null or holds nothing of this arena is left alone
+    template <class P>
+    void release(P** ptr) {
+        for (size_t i = held.size(); i-- > 0;)
+            if (held[i].p == static_cast<const void*>(*ptr)) {
+                give_back(held[i]);
+                held.erase(held.begin() + (long)i);
+                *ptr = nullptr;
+                return;
+            }
+    }
+    void clear() { release_to(0); }
+
+private:
+    hipError_t err = hipSuccess;
+    struct Held {
+        void* p;
+        size_t bytes;
+        Mem kind;
+        void* slot;       // the owner's pointer it was taken into (the owner may have swapped it with another since)
+    };
+    std::vector<Held> held;
+    void give_back(const Held& h) {
+        switch (h.kind) {
+            case Mem::pooled: big_free(device, h.p, h.bytes); break;
+            case Mem::pinned: pinned_free(h.p, h.bytes); break;
+            default: dev_free(h.p, h.bytes);
+        }
+    }
+};
+using ScopedDev = DeviceArena;      // on the stack: a call's staging and scratch buffers, gone on every way out
+
+// A handle's stream -- the caller's, borrowed, or a non-blocking one of its own -- and its events.  Converts to hipStream_t, so
+// launch code passes it as the stream.
+struct HandleStream {
+    hipStream_t stream = nullptr;
+    bool own = false;
+    std::vector<hipEvent_t> events;
+    operator hipStream_t() const { return stream; }
+    HandleStream() = default;
+    ~HandleStream() { close(); }
+    HandleStream(const HandleStream&) = delete;
+    HandleStream& operator=(const HandleStream&) = delete;
+
+    hipError_t open(void* user_stream, int n_events, bool timing = true) {
+        if (user_stream) {
+            stream = static_cast<hipStream_t>(user_stream);
+        } else {
+            const hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+            if (e != hipSuccess) return e;
+            own = true;
+        }
+        return add_events(n_events, timing);
+    }
+    hipError_t add_events(int n, bool timing = true) {
+        for (int i = 0; i < n; ++i) {
+            hipEvent_t ev = nullptr;
+            const hipError_t e = timing ? hipEventCreate(&ev) : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+            if (e != hipSuccess) return e;
+            events.push_back(ev);
+        }
+        return hipSuccess;
+    }
+    void close() {
+        for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+        events.clear();
+        if (own && stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+        own = false;
+    }
+    // record event i, run body (an int status), record event j, wait for it: *ms is the time between the two
+    template <class Body>
+    int elapsed_ms(int i, int j, Body&& body, float* ms) {
+        OIVA_TRY_HIP(hipEventRecord(events[i], stream));
+        const int rc = body();
+        if (rc) return rc;
+        OIVA_TRY_HIP(hipEventRecord(events[j], stream));
+        OIVA_TRY_HIP(hipEventSynchronize(events[j]));
+        OIVA_TRY_HIP(hipEventElapsedTime(ms, events[i], events[j]));
+        return OIVA_OK;
     }
 };
 
@@ -194,17 +326,17 @@ inline CovGeom stats_geom(int T, int F, int K, int n_cu) {
 }
 
 // ---- the per-bin state of OGIVE for nbins bins of M channels (Cx, What and What64 are the owner's own buffers) ---------------
-inline void alloc_ogive_state(OgiveState& st, size_t nbins, size_t M, AllocChain& alloc) {
-    alloc(&st.CxInv, nbins * M * M * sizeof(double2));
-    alloc(&st.CxNorm, nbins * sizeof(double));
-    alloc(&st.A, nbins * M * sizeof(double2));
-    alloc(&st.Delta, nbins * M * sizeof(double2));
-    alloc(&st.Lambda, nbins * sizeof(double));
-    alloc(&st.DoA, nbins * sizeof(int));
-    alloc(&st.DoW, nbins * sizeof(int));
-    alloc(&st.Dnorm, nbins * sizeof(double));
-    alloc(&st.ctrl, 4 * sizeof(int));
-    alloc(&st.maxdelta, 2 * sizeof(double));
+inline void alloc_ogive_state(OgiveState& st, size_t nbins, size_t M, DeviceArena& mem) {
+    mem.take(&st.CxInv, nbins * M * M * sizeof(double2));
+    mem.take(&st.CxNorm, nbins * sizeof(double));
+    mem.take(&st.A, nbins * M * sizeof(double2));
+    mem.take(&st.Delta, nbins * M * sizeof(double2));
+    mem.take(&st.Lambda, nbins * sizeof(double));
+    mem.take(&st.DoA, nbins * sizeof(int));
+    mem.take(&st.DoW, nbins * sizeof(int));
+    mem.take(&st.Dnorm, nbins * sizeof(double));
+    mem.take(&st.ctrl, 4 * sizeof(int));
+    mem.take(&st.maxdelta, 2 * sizeof(double));
 }
 
 }  // namespace oiva

@@ -14,7 +14,7 @@ namespace oiva {
 constexpr int kNarrowMax = 16;
 constexpr int kWideMax = OIVA_MAX_CHANNELS;
 
-// records the thread-local message oiva_last_error() returns and hands back `code` (defined in plan.hip)
+// records the thread-local message oiva_last_error() returns and hands back `code` (host_util.hip)
 int fail_with(int code, const std::string& msg);
 // exchange.hip: rank / world / slot size and every rank's gather buffer as mapped in this process; -1 unless connected
 int xchg_peers(oiva_xchg* x, char** peers, int* rank, int* world, size_t* slot_bytes);

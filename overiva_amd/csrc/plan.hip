@@ -18,114 +18,20 @@ using namespace oiva;
 
 namespace {
 
-thread_local std::string g_err;
-
 constexpr int kGraphBatch = 8;       // iterations of the graph captured ahead of time (oiva_plan_use_graph)
 constexpr int kGraphMaxIters = 32;   // longest graph captured on demand: an iterate(n) call is ceil(n / 32) replays
 constexpr int kGraphCache = 6;       // captured lengths kept per plan
 
 }  // namespace
 
-int oiva::fail_with(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-oiva::KernelTimer& oiva::kernel_timer() {
-    static thread_local KernelTimer t;
-    return t;
-}
-
-// ---- large device buffers (X, Y, staging) come from a process-wide pool -------------------------------------------
-// The drop-in call creates and destroys a plan per call; hipMalloc + hipFree of the 524 MB of X and the 131 MB of Y at the
-// headline shape were ~2.5 ms of a 22 ms call.  Buffers of >= 16 MB go back to the pool instead of the driver (exact-size
-// reuse, per device), at most $OIVA_POOL_MB (default 2048) held; oiva_pool_trim() releases them.
-namespace {
-struct BigPool {
-    struct Entry {
-        void* p;
-        size_t bytes;
-        int dev;
-    };
-    std::mutex m;
-    std::vector<Entry> held;      // oldest first
-    size_t total = 0;
-};
-BigPool& big_pool() {
-    static BigPool* bp = new BigPool;      // (never destroyed: the HIP runtime may be gone when static destructors run)
-    return *bp;
-}
-constexpr size_t kPoolMinBytes = (size_t)16 << 20;
-size_t pool_cap_bytes() {
-    static const size_t cap = [] {
-        const char* v = std::getenv("OIVA_POOL_MB");
-        return (size_t)(v ? std::max(0, std::atoi(v)) : 2048) << 20;
-    }();
-    return cap;
-}
-// every buffer the pool holds goes back to the driver (oiva_pool_trim; dev_malloc when the driver is out of memory)
-void pool_release_all() {
-    BigPool& bp = big_pool();
-    std::lock_guard<std::mutex> g(bp.m);
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    for (auto& e : bp.held) {
-        (void)hipSetDevice(e.dev);
-        (void)hipFree(e.p);
-    }
-    if (prev >= 0) (void)hipSetDevice(prev);
-    bp.held.clear();
-    bp.total = 0;
-}
-}  // namespace
-// hipMalloc of the library: the pool's idle buffers are memory the caller thinks is free, so before an allocation fails for
-// want of memory they are handed back and the allocation is tried once more
-hipError_t oiva::dev_malloc(void** out, size_t bytes) {
-    hipError_t e = hipMalloc(out, bytes);
-    if (e != hipErrorOutOfMemory) return e;
-    (void)hipGetLastError();
-    pool_release_all();
-    return hipMalloc(out, bytes);
-}
-hipError_t oiva::big_alloc(int dev, void** out, size_t bytes) {
-    if (bytes >= kPoolMinBytes) {
-        BigPool& bp = big_pool();
-        std::lock_guard<std::mutex> g(bp.m);
-        for (size_t i = bp.held.size(); i-- > 0;)
-            if (bp.held[i].dev == dev && bp.held[i].bytes == bytes) {
-                *out = bp.held[i].p;
-                bp.total -= bytes;
-                bp.held.erase(bp.held.begin() + (long)i);
-                return hipSuccess;
-            }
-    }
-    return dev_malloc(out, bytes);
-}
-void oiva::big_free(int dev, void* ptr, size_t bytes) {
-    if (!ptr) return;
-    if (bytes >= kPoolMinBytes && bytes <= pool_cap_bytes()) {
-        BigPool& bp = big_pool();
-        std::lock_guard<std::mutex> g(bp.m);
-        while (!bp.held.empty() && bp.total + bytes > pool_cap_bytes()) {
-            (void)hipFree(bp.held.front().p);
-            bp.total -= bp.held.front().bytes;
-            bp.held.erase(bp.held.begin());
-        }
-        bp.held.push_back({ptr, bytes, dev});
-        bp.total += bytes;
-        return;
-    }
-    (void)hipFree(ptr);
-}
-
 struct oiva_plan {
     int device = 0;
     int T = 0, F = 0, M = 0, K = 0, model = 0, F_total = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    HandleStream stream;        // two events: the bracket of the timers
+    DeviceArena mem;            // every device and pinned buffer below (X_owned, Y and io_c128 pooled)
 
     const float2* X = nullptr;  // (T,F,M)
     float2* X_owned = nullptr;
-    size_t x_owned_bytes = 0, y_bytes = 0;      // (big_alloc / big_free)
     float2* X_pad = nullptr;    // (T, F, M + 1): X with a zero channel behind every bin's M, for the vector-ALU covariance kernels at 9/11/13/15 channels
     float2* What = nullptr;     // (F,M,M) complex64: what the streaming kernels read
     double2* What64 = nullptr;  // (F,M,M) complex128: carried between iterations by the float64 update
@@ -168,7 +74,6 @@ struct oiva_plan {
     int use_graph = 0;
     // OGIVE (ive.py): per-bin state, allocated by oiva_plan_ogive_begin
     OgiveState og{};
-    std::vector<void*> og_bufs;
     bool og_ready = false;
     int og_mode = 0, og_model = 0;
     // captured chunk of OGIVE epochs (five launches per epoch are latency bound on the reference's problem sizes)
@@ -212,16 +117,14 @@ struct oiva_plan {
     int fx_timeout_ms = 0, fx_stall = 0;
     // hand-over of Y to a host array in slabs of frames (demix_to_host): a second stream for the device-to-host copies, one
     // event pair per slot of the pinned ring, a device staging ring for complex128 output
-    hipStream_t io_stream = nullptr;
-    hipEvent_t io_written[kHostRingSlots] = {}, io_copied[kHostRingSlots] = {};
+    HandleStream io_stream;                     // untimed events: [s] slab written, [kHostRingSlots + s] slab copied, per slot s
     double2* io_c128[kHostRingSlots] = {};
-    size_t io_c128_bytes = 0;
+    size_t io_c128_bytes = 0;                   // of each slot (all three or none)
     size_t io_slab_bytes = 0;                   // oiva_plan_set_io_slab (0: 8 MB)
     float2* ck_what = nullptr;                  // oiva_plan_save_w: a copy of W_hat (and of its complex128 form) on the device
     double2* ck_what64 = nullptr;
     bool ck_valid = false, ck_what64_valid = false;
     GraphCache graphs{kGraphCache};             // by iterations per replay
-    hipEvent_t ev[2] = {};
 };
 
 namespace {
@@ -458,9 +361,8 @@ size_t vpart_floats(const oiva_plan* p, int nsplit) { return (size_t)nsplit * p-
 
 int ensure_vpart(oiva_plan* p) {
     if (p->cov.nsplit > p->vpart_splits_alloc) {
-        if (p->Vpart) OIVA_TRY_HIP(hipFree(p->Vpart));
-        p->Vpart = nullptr;
-        OIVA_TRY_HIP(dev_malloc(&p->Vpart, (vpart_floats(p, p->cov.nsplit) + 2) * sizeof(double)));   // either element type; sum_vpart reads idx + 1
+        p->mem.release(&p->Vpart);
+        OIVA_TRY_HIP(p->mem.take_one(&p->Vpart, (vpart_floats(p, p->cov.nsplit) + 2) * sizeof(double)));   // either element type; sum_vpart reads idx + 1
         p->vpart_splits_alloc = p->cov.nsplit;
     }
     return OIVA_OK;
@@ -577,10 +479,10 @@ int resident_alloc(oiva_plan* p) {
     const size_t b_flags = up((16 + (size_t)g.NB * g.NS) * sizeof(unsigned));      // ctrl words, then the XCD table
     const size_t b_stamps = up((size_t)kResidentStampIters * kResidentStamps * sizeof(unsigned long long));
     const size_t total = b_parts + b_psum + b_vpart + b_rsum + b_wpub + b_flags + b_stamps;
-    if (!p->res_what) OIVA_TRY_HIP(dev_malloc(&p->res_what, (size_t)p->F * NA * sizeof(float2)));
-    if (!p->res_what64) OIVA_TRY_HIP(dev_malloc(&p->res_what64, (size_t)p->F * NA * sizeof(double2)));
-    if (!p->res_code_host) OIVA_TRY_HIP(hipHostMalloc((void**)&p->res_code_host, sizeof(unsigned), hipHostMallocDefault));
-    OIVA_TRY_HIP(dev_malloc(&p->res_block, total));
+    if (!p->res_what) OIVA_TRY_HIP(p->mem.take_one(&p->res_what, (size_t)p->F * NA * sizeof(float2)));
+    if (!p->res_what64) OIVA_TRY_HIP(p->mem.take_one(&p->res_what64, (size_t)p->F * NA * sizeof(double2)));
+    if (!p->res_code_host) OIVA_TRY_HIP(p->mem.take_one(&p->res_code_host, sizeof(unsigned), Mem::pinned));
+    OIVA_TRY_HIP(p->mem.take_one(&p->res_block, total));
     OIVA_TRY_HIP(hipMemsetAsync(p->res_block, 0, total, p->stream));
     char* c = static_cast<char*>(p->res_block);
     p->res_parts = reinterpret_cast<float*>(c);
@@ -627,9 +529,8 @@ int run_resident(oiva_plan* p, int n, bool* ran) {
     a.stamp_all = 0;
     if (p->res_trace && n <= 64) {
         const size_t bytes = (size_t)g.NB * g.NS * n * kResidentStamps * sizeof(unsigned long long);
-        if (p->res_trace_buf) OIVA_TRY_HIP(hipFree(p->res_trace_buf));
-        p->res_trace_buf = nullptr;
-        OIVA_TRY_HIP(dev_malloc(&p->res_trace_buf, bytes));
+        p->mem.release(&p->res_trace_buf);
+        OIVA_TRY_HIP(p->mem.take_one(&p->res_trace_buf, bytes));
         OIVA_TRY_HIP(hipMemsetAsync(p->res_trace_buf, 0, bytes, p->stream));
         a.stamps = p->res_trace_buf;
         a.stamp_all = 1;
@@ -751,13 +652,36 @@ int check_ready(oiva_plan* p) {
     return OIVA_OK;
 }
 
+// X of the plan is now the array at X (its own copy or the caller's): captured graphs hold the old pointer, Cx and the padded
+// copy are of the old array
+int install_x(oiva_plan* p, const float2* X) {
+    if (p->X != X) {
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+        const int rc = drop_graph(p);
+        if (rc) return rc;
+    }
+    p->X = X;
+    p->have_x = true;
+    p->have_cx = false;
+    p->pad_valid = false;
+    return OIVA_OK;
+}
+// what every setter of the iteration's geometry does around its change: the stream idle, no captured graph of the old
+// geometry, `change` (a status; it re-chooses the geometry it touches), covariance partials for the splits there are now
+template <class Change>
+int change_geometry(oiva_plan* p, Change&& change) {
+    DeviceGuard guard(p->device);
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    int rc = drop_graph(p);
+    if (rc || (rc = change())) return rc;
+    return ensure_vpart(p);
+}
+
 }  // namespace
 
 extern "C" {
 
 int oiva_version(void) { return 100; }
-
-const char* oiva_last_error(void) { return g_err.c_str(); }
 
 int oiva_device_count(int* n) {
     OIVA_NEED(n != nullptr, OIVA_ERR_ARG, "null pointer");
@@ -780,22 +704,17 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
     DeviceGuard guard(device);
 
     oiva_plan* p = new oiva_plan();
-    p->device = device;
+    p->device = p->mem.device = device;
     p->T = T;
     p->F = F;
     p->M = M;
     p->K = K;
     p->model = model;
     p->F_total = F_total;
-    if (stream) {
-        p->stream = (hipStream_t)stream;
-    } else {
-        hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            delete p;
-            return fail_with(OIVA_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-        }
-        p->own_stream = true;
+    const hipError_t es = p->stream.open(stream, 0);
+    if (es != hipSuccess) {
+        oiva_plan_destroy(p);
+        return fail_with(OIVA_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(es));
     }
     {
         hipDeviceProp_t prop;
@@ -805,7 +724,7 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
     if (M > 8 && M <= kNarrowMax && M % 2 == 1) {
         // 9 / 11 / 13 / 15 channels: the vector-ALU covariance kernels read 16-byte pieces at an even channel pitch, so
         // they get their own copy of X with one zero channel per bin (filled by oiva_plan_covariance; + (M + 1) / M of X)
-        hipError_t ep = dev_malloc((void**)&p->X_pad, (size_t)T * F * (M + 1) * sizeof(float2));
+        const hipError_t ep = p->mem.take_one(&p->X_pad, (size_t)T * F * (M + 1) * sizeof(float2));
         if (ep != hipSuccess) {
             oiva_plan_destroy(p);
             return fail_with(OIVA_ERR_HIP, std::string("allocation of the padded copy of X failed: ") + hipGetErrorString(ep));
@@ -825,26 +744,25 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
     p->res_ok = resident_geometry(T, F, M, K, p->n_cu, 0, &p->rg);
     const size_t nTK = (size_t)T * K;
     const size_t nFMM = (size_t)F * M * M;
-    AllocChain alloc;
-    alloc(&p->What, nFMM * sizeof(float2));
-    alloc(&p->What64, nFMM * sizeof(double2));
-    alloc(&p->Cx, nFMM * sizeof(double));
-    alloc(&p->Ppart, (size_t)p->pw.nb * nTK * sizeof(float));
+    DeviceArena& mem = p->mem;
+    mem.take(&p->What, nFMM * sizeof(float2));
+    mem.take(&p->What64, nFMM * sizeof(double2));
+    mem.take(&p->Cx, nFMM * sizeof(double));
+    mem.take(&p->Ppart, (size_t)p->pw.nb * nTK * sizeof(float));
     p->ppart_alloc = p->pw.nb;
-    alloc(&p->Plocal, std::max(nTK, ((size_t)T + 1) * 32) * sizeof(float));   // also the (T + 1, 16) weights scratch (floats or doubles)
-    if (M > kNarrowMax) alloc(&p->Wwide, nTK * sizeof(double));                // the wide path's (T, K) float64 weights
-    alloc(&p->R, r_buffer_bytes(T, K));   // activations, zeroed pad rows, per-block sums (rsum_offset_floats)
-    if (alloc.ok()) alloc.err = hipMemset(p->R, 0, r_buffer_bytes(T, K));
-    alloc(&p->wscale, (size_t)K * sizeof(float));
-    alloc(&p->Spart, (size_t)p->stg.nsplit * F * K * 3 * sizeof(float));
-    alloc(&p->scratch_c, (size_t)K * nFMM * sizeof(double2));
-    alloc(&p->scratch_p, std::max((size_t)K * nFMM, nTK) * sizeof(double));
-    for (auto& ev : p->ev) {
-        if (alloc.ok()) alloc.err = hipEventCreate(&ev);
-    }
-    if (!alloc.ok()) {
+    mem.take(&p->Plocal, std::max(nTK, ((size_t)T + 1) * 32) * sizeof(float));   // also the (T + 1, 16) weights scratch (floats or doubles)
+    if (M > kNarrowMax) mem.take(&p->Wwide, nTK * sizeof(double));                // the wide path's (T, K) float64 weights
+    mem.take(&p->R, r_buffer_bytes(T, K));   // activations, zeroed pad rows, per-block sums (rsum_offset_floats)
+    if (mem.ok()) mem.note(hipMemset(p->R, 0, r_buffer_bytes(T, K)));
+    mem.take(&p->wscale, (size_t)K * sizeof(float));
+    mem.take(&p->Spart, (size_t)p->stg.nsplit * F * K * 3 * sizeof(float));
+    mem.take(&p->scratch_c, (size_t)K * nFMM * sizeof(double2));
+    mem.take(&p->scratch_p, std::max((size_t)K * nFMM, nTK) * sizeof(double));
+    if (mem.ok()) mem.note(p->stream.add_events(2));
+    if (!mem.ok()) {
+        const hipError_t e = mem.status();
         oiva_plan_destroy(p);
-        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
+        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(e));
     }
     int rc = ensure_vpart(p);
     if (rc) {
@@ -859,36 +777,12 @@ int oiva_plan_destroy(oiva_plan* p) {
     if (!p) return OIVA_OK;
     DeviceGuard guard(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
+    if (p->io_stream) (void)hipStreamSynchronize(p->io_stream);
     (void)p->graphs.clear();
     if (p->og_graph) (void)hipGraphExecDestroy(p->og_graph);
-    if (p->res_code_host) (void)hipHostFree(p->res_code_host);
-    if (p->io_stream) (void)hipStreamSynchronize(p->io_stream);
-    big_free(p->device, p->X_owned, p->x_owned_bytes);
-    big_free(p->device, p->Y, p->y_bytes);
-    for (int i = 0; i < kHostRingSlots; ++i) {
-        big_free(p->device, p->io_c128[i], p->io_c128_bytes);
-        p->io_c128[i] = nullptr;
-    }
-    void* bufs[] = {p->X_pad, p->What, p->What64, p->Cx,        p->Vpart,    p->Ppart, p->Plocal, p->res_block, p->res_trace_buf, p->res_what, p->res_what64,
-                    p->R,       p->wscale, p->Spart, p->scratch_c, p->scratch_p, p->Wwide};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (void* b : p->og_bufs)
-        if (b) (void)hipFree(b);
-    if (p->res_loop_buf) (void)hipFree(p->res_loop_buf);
-    if (p->fx_loop_buf) (void)hipFree(p->fx_loop_buf);
-    if (p->fx_state) (void)hipFree(p->fx_state);
-    if (p->fx_flag_host) (void)hipHostFree(p->fx_flag_host);
-    if (p->io_stream) (void)hipStreamDestroy(p->io_stream);
-    for (int i = 0; i < kHostRingSlots; ++i) {
-        if (p->io_written[i]) (void)hipEventDestroy(p->io_written[i]);
-        if (p->io_copied[i]) (void)hipEventDestroy(p->io_copied[i]);
-    }
-    if (p->ck_what) (void)hipFree(p->ck_what);
-    if (p->ck_what64) (void)hipFree(p->ck_what64);
-    for (auto& ev : p->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (p->own_stream && p->stream) (void)hipStreamDestroy(p->stream);
+    p->mem.clear();
+    p->io_stream.close();
+    p->stream.close();
     delete p;
     return OIVA_OK;
 }
@@ -899,21 +793,10 @@ int oiva_plan_set_x_host(oiva_plan* p, const void* X, long long row_pitch_bytes)
     const size_t row = (size_t)p->F * p->M * sizeof(float2);
     const size_t pitch = row_pitch_bytes > 0 ? (size_t)row_pitch_bytes : row;
     OIVA_NEED(pitch >= row, OIVA_ERR_ARG, "row pitch smaller than one frame of this plan's bins");
-    if (!p->X_owned) {
-        OIVA_TRY_HIP(big_alloc(p->device, (void**)&p->X_owned, row * p->T));
-        p->x_owned_bytes = row * p->T;
-    }
+    if (!p->X_owned) OIVA_TRY_HIP(p->mem.take_one(&p->X_owned, row * p->T, Mem::pooled));
     OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     OIVA_TRY_HIP(hipMemcpy2D(p->X_owned, row, X, pitch, row, p->T, hipMemcpyHostToDevice));
-    if (p->X != p->X_owned) {             // switching from a borrowed array: captured graphs hold its pointer
-        int rc = drop_graph(p);
-        if (rc) return rc;
-    }
-    p->X = p->X_owned;
-    p->have_x = true;
-    p->have_cx = false;
-    p->pad_valid = false;
-    return OIVA_OK;
+    return install_x(p, p->X_owned);
 }
 
 int oiva_plan_set_x_host_c128(oiva_plan* p, const void* X, long long row_pitch_bytes) {
@@ -923,50 +806,19 @@ int oiva_plan_set_x_host_c128(oiva_plan* p, const void* X, long long row_pitch_b
     const size_t row = n_row * sizeof(double2);
     const size_t pitch = row_pitch_bytes > 0 ? (size_t)row_pitch_bytes : row;
     OIVA_NEED(pitch >= row, OIVA_ERR_ARG, "row pitch smaller than one frame of this plan's bins");
-    if (!p->X_owned) {
-        OIVA_TRY_HIP(big_alloc(p->device, (void**)&p->X_owned, n_row * sizeof(float2) * p->T));
-        p->x_owned_bytes = n_row * sizeof(float2) * p->T;
-    }
+    if (!p->X_owned) OIVA_TRY_HIP(p->mem.take_one(&p->X_owned, n_row * sizeof(float2) * p->T, Mem::pooled));
     OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     // in slabs of frames through a staging buffer (<= 256 MB): the conversion of one slab overlaps nothing, but the
     // footprint stays bounded and the host never touches the data (a NumPy astype of 1 GB costs 60 ms)
-    const int slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)p->T, ((size_t)256 << 20) / row));
-    double2* stage = nullptr;
-    OIVA_TRY_HIP(big_alloc(p->device, (void**)&stage, row * slab));
-    hipError_t e = hipSuccess;
-    for (int t0 = 0; t0 < p->T && e == hipSuccess; t0 += slab) {
-        const int nt = std::min(slab, p->T - t0);
-        e = hipMemcpy2D(stage, row, static_cast<const char*>(X) + (size_t)t0 * pitch, pitch, row, nt, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = launch_cast_c128_to_c64(p->stream, stage, p->X_owned + (size_t)t0 * n_row, (long long)nt * n_row);
-        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    }
-    if (e == hipSuccess) big_free(p->device, stage, row * slab); else (void)hipFree(stage);
-    OIVA_TRY_HIP(e);
-    if (p->X != p->X_owned) {             // switching from a borrowed array: captured graphs hold its pointer
-        int rc = drop_graph(p);
-        if (rc) return rc;
-    }
-    p->X = p->X_owned;
-    p->have_x = true;
-    p->have_cx = false;
-    p->pad_valid = false;
-    return OIVA_OK;
+    OIVA_TRY_HIP(staged_copy_c128(true, p->stream, const_cast<void*>(X), pitch, p->X_owned, n_row, p->T, kStageBytes, p->device, Mem::pooled));
+    return install_x(p, p->X_owned);
 }
 
 int oiva_plan_set_x_dev(oiva_plan* p, const void* X_dev) {
     OIVA_NEED(p && X_dev, OIVA_ERR_ARG, "null argument");
     OIVA_NEED(((uintptr_t)X_dev & 15) == 0, OIVA_ERR_ARG, "device X must be 16-byte aligned");
-    if (p->X != (const float2*)X_dev) {   // captured graphs hold the old pointer
-        DeviceGuard guard(p->device);
-        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-        int rc = drop_graph(p);
-        if (rc) return rc;
-    }
-    p->X = (const float2*)X_dev;
-    p->have_x = true;
-    p->have_cx = false;
-    p->pad_valid = false;
-    return OIVA_OK;
+    DeviceGuard guard(p->device);
+    return install_x(p, (const float2*)X_dev);
 }
 
 int oiva_plan_covariance(oiva_plan* p) {
@@ -1043,11 +895,7 @@ int oiva_plan_demix_dev(oiva_plan* p, int proj_back, void** Y_dev) {
     OIVA_NEED(Y_dev, OIVA_ERR_ARG, "null output");
     DeviceGuard guard(p->device);
     if ((rc = check_fused(p))) return rc;
-    const size_t row = (size_t)p->F * p->K * sizeof(float2);
-    if (!p->Y) {
-        OIVA_TRY_HIP(big_alloc(p->device, (void**)&p->Y, row * p->T));
-        p->y_bytes = row * p->T;
-    }
+    if (!p->Y) OIVA_TRY_HIP(p->mem.take_one(&p->Y, (size_t)p->F * p->K * sizeof(float2) * p->T, Mem::pooled));
     const float* sp = nullptr;
     if (proj_back) {
         OIVA_TRY_HIP(launch_demix_stats(p->stream, p->X, p->What, p->Spart, p->T, p->F, p->M, p->K, p->stg));
@@ -1109,9 +957,8 @@ int oiva_plan_power_buffer(oiva_plan* p, int parts_per_rank, void** parts_dev, l
         OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
         int rc = drop_graph(p);
         if (rc) return rc;
-        if (p->Ppart) OIVA_TRY_HIP(hipFree(p->Ppart));
-        p->Ppart = nullptr;
-        OIVA_TRY_HIP(dev_malloc(&p->Ppart, part * parts_per_rank));
+        p->mem.release(&p->Ppart);
+        OIVA_TRY_HIP(p->mem.take_one(&p->Ppart, part * parts_per_rank));
         // parts beyond nb stay zero; on the plan's own stream, so that it is ordered before the next power pass
         OIVA_TRY_HIP(hipMemsetAsync(p->Ppart, 0, part * parts_per_rank, p->stream));
         p->ppart_alloc = parts_per_rank;
@@ -1150,10 +997,7 @@ static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
     const size_t pitch = row_pitch_bytes > 0 ? (size_t)row_pitch_bytes : row;
     OIVA_NEED(pitch >= row, OIVA_ERR_ARG, "row pitch smaller than one frame of this plan's bins");
     if ((rc = check_fused(p))) return rc;
-    if (!p->Y) {
-        OIVA_TRY_HIP(big_alloc(p->device, (void**)&p->Y, row_dev * p->T));
-        p->y_bytes = row_dev * p->T;
-    }
+    if (!p->Y) OIVA_TRY_HIP(p->mem.take_one(&p->Y, row_dev * p->T, Mem::pooled));
     const float* sp = nullptr;
     if (proj_back) {
         OIVA_TRY_HIP(launch_demix_stats(p->stream, p->X, p->What, p->Spart, p->T, p->F, p->M, p->K, p->stg));
@@ -1174,47 +1018,27 @@ static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
             OIVA_TRY_HIP(hipMemcpy2D(Y_host, pitch, p->Y, row, row, p->T, hipMemcpyDeviceToHost));
             return OIVA_OK;
         }
-        const int slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)p->T, ((size_t)256 << 20) / row));
-        double2* stage = nullptr;
-        OIVA_TRY_HIP(dev_malloc(&stage, row * slab));
-        hipError_t e = hipSuccess;
-        for (int t0 = 0; t0 < p->T && e == hipSuccess; t0 += slab) {
-            const int nt = std::min(slab, p->T - t0);
-            e = launch_cast_c64_to_c128(p->stream, p->Y + (size_t)t0 * n_row, stage, (long long)nt * n_row);
-            if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-            if (e == hipSuccess)
-                e = hipMemcpy2D(static_cast<char*>(Y_host) + (size_t)t0 * pitch, pitch, stage, row, row, nt, hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(stage);
-        OIVA_TRY_HIP(e);
+        OIVA_TRY_HIP(staged_copy_c128(false, p->stream, Y_host, pitch, p->Y, n_row, p->T, kStageBytes, p->device, Mem::plain));
         return OIVA_OK;
     }
     // ---- slabs of about 8 MB of output
     const int slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)p->T, slab_target / row));
     const int nslab = ceil_div(p->T, slab);
     const size_t slab_bytes = (size_t)slab * row;
-    if (!p->io_stream) OIVA_TRY_HIP(hipStreamCreateWithFlags(&p->io_stream, hipStreamNonBlocking));
-    for (int i = 0; i < kHostRingSlots; ++i) {
-        if (!p->io_written[i]) OIVA_TRY_HIP(hipEventCreateWithFlags(&p->io_written[i], hipEventDisableTiming));
-        if (!p->io_copied[i]) OIVA_TRY_HIP(hipEventCreateWithFlags(&p->io_copied[i], hipEventDisableTiming));
-    }
+    if (!p->io_stream) OIVA_TRY_HIP(p->io_stream.open(nullptr, 0));
+    if (p->io_stream.events.size() < 2 * kHostRingSlots)
+        OIVA_TRY_HIP(p->io_stream.add_events(2 * kHostRingSlots - (int)p->io_stream.events.size(), /*timing*/ false));
+    hipEvent_t* io_written = p->io_stream.events.data();
+    hipEvent_t* io_copied = io_written + kHostRingSlots;
     if (c128 && p->io_c128_bytes < slab_bytes) {
         OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
         // all three or none: the recorded size is that of every non-null slot, also after a failed allocation
-        for (auto& b : p->io_c128) {
-            big_free(p->device, b, p->io_c128_bytes);
-            b = nullptr;
-        }
+        for (auto& b : p->io_c128) p->mem.release(&b);
         p->io_c128_bytes = 0;
-        for (auto& b : p->io_c128) {
-            hipError_t e = big_alloc(p->device, (void**)&b, slab_bytes);
-            if (e != hipSuccess) {
-                for (auto& c : p->io_c128) {
-                    if (c) (void)hipFree(c);
-                    c = nullptr;
-                }
-                OIVA_TRY_HIP(e);
-            }
+        for (auto& b : p->io_c128) p->mem.take(&b, slab_bytes, Mem::pooled);
+        if (!p->mem.ok()) {
+            for (auto& b : p->io_c128) p->mem.release(&b);
+            OIVA_TRY_HIP(p->mem.status());
         }
         p->io_c128_bytes = slab_bytes;
     }
@@ -1248,15 +1072,15 @@ static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
             e = launch_cast_c64_to_c128(p->stream, ydev, p->io_c128[s], (long long)nt * n_row);
             src = p->io_c128[s];
         }
-        if (e == hipSuccess) e = hipEventRecord(p->io_written[s], p->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(p->io_stream, p->io_written[s], 0);
+        if (e == hipSuccess) e = hipEventRecord(io_written[s], p->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(p->io_stream, io_written[s], 0);
         if (e == hipSuccess) {
             if (registered)
                 e = hipMemcpy2DAsync(static_cast<char*>(Y_host) + (size_t)t0 * pitch, pitch, src, row, row, nt, hipMemcpyDeviceToHost, p->io_stream);
             else
                 e = hipMemcpyAsync(pinned[s], src, (size_t)nt * row, hipMemcpyDeviceToHost, p->io_stream);
         }
-        if (e == hipSuccess) e = hipEventRecord(p->io_copied[s], p->io_stream);
+        if (e == hipSuccess) e = hipEventRecord(io_copied[s], p->io_stream);
         // (slot s -- the pinned buffer and, for complex128, the device staging buffer -- is rewritten by slab k + slots, which
         //  the loop below issues only after it has waited for THIS copy and moved its data on)
         return e;
@@ -1272,7 +1096,7 @@ static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
             // are computed and cross PCIe.
             host_prefault(Y_host, pitch * (size_t)(p->T - 1) + row, /*may_touch*/ pitch == row);
         }
-        if (e == hipSuccess) e = hipEventSynchronize(p->io_copied[k % kHostRingSlots]);
+        if (e == hipSuccess) e = hipEventSynchronize(io_copied[k % kHostRingSlots]);
         if (e != hipSuccess) return finish(e);
         if (!registered) {
             const int t0 = k * slab, nt = std::min(slab, p->T - t0);
@@ -1280,11 +1104,6 @@ static int demix_to_host(oiva_plan* p, void* Y_host, long long row_pitch_bytes, 
         }
     }
     return finish(hipStreamSynchronize(p->stream));
-}
-
-int oiva_pool_trim(void) {
-    pool_release_all();
-    return OIVA_OK;
 }
 
 int oiva_plan_set_io_slab(oiva_plan* p, long long bytes) {
@@ -1320,7 +1139,7 @@ int oiva_plan_get_w(oiva_plan* p, void* W_host, int f64) {
 // work already queued on the plan's stream and read after ONE wait for that stream.
 static int check_fused(oiva_plan* p) {
     if (!p->fx_state || !p->fx_on) return OIVA_OK;
-    if (!p->fx_flag_host) OIVA_TRY_HIP(hipHostMalloc((void**)&p->fx_flag_host, sizeof(unsigned), hipHostMallocDefault));
+    if (!p->fx_flag_host) OIVA_TRY_HIP(p->mem.take_one(&p->fx_flag_host, sizeof(unsigned), Mem::pinned));
     OIVA_TRY_HIP(hipMemcpyAsync(p->fx_flag_host, p->fx_state, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
     OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     const unsigned code = *p->fx_flag_host;
@@ -1343,8 +1162,8 @@ int oiva_plan_save_w(oiva_plan* p) {
     OIVA_NEED(p->have_w, OIVA_ERR_STATE, "demixing matrix not set");
     DeviceGuard guard(p->device);
     const size_t n = (size_t)p->F * p->M * p->M;
-    if (!p->ck_what) OIVA_TRY_HIP(dev_malloc((void**)&p->ck_what, n * sizeof(float2)));
-    if (!p->ck_what64) OIVA_TRY_HIP(dev_malloc((void**)&p->ck_what64, n * sizeof(double2)));
+    if (!p->ck_what) OIVA_TRY_HIP(p->mem.take_one(&p->ck_what, n * sizeof(float2)));
+    if (!p->ck_what64) OIVA_TRY_HIP(p->mem.take_one(&p->ck_what64, n * sizeof(double2)));
     // on the plan's stream: ordered behind the iterations already queued, in front of the ones that follow
     OIVA_TRY_HIP(hipMemcpyAsync(p->ck_what, p->What, n * sizeof(float2), hipMemcpyDeviceToDevice, p->stream));
     OIVA_TRY_HIP(hipMemcpyAsync(p->ck_what64, p->What64, n * sizeof(double2), hipMemcpyDeviceToDevice, p->stream));
@@ -1368,7 +1187,7 @@ int oiva_plan_restore_w(oiva_plan* p) {
 
 static int fused_setup(oiva_plan* p) {
     const size_t words = 16 + (size_t)rsum_blocks(p->T) * p->K;
-    if (!p->fx_state) OIVA_TRY_HIP(dev_malloc((void**)&p->fx_state, words * sizeof(unsigned)));
+    if (!p->fx_state) OIVA_TRY_HIP(p->mem.take_one(&p->fx_state, words * sizeof(unsigned)));
     OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     OIVA_TRY_HIP(hipMemset(p->fx_state, 0, words * sizeof(unsigned)));
     return drop_graph(p);                       // captured graphs hold the other activation kernel
@@ -1418,10 +1237,7 @@ int oiva_plan_fused_loopback(oiva_plan* p, int world) {
     OIVA_NEED(world >= 0 && world <= OIVA_XCHG_MAX_RANKS, OIVA_ERR_ARG, "bad number of ranks");
     DeviceGuard guard(p->device);
     OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-    if (p->fx_loop_buf) {
-        OIVA_TRY_HIP(hipFree(p->fx_loop_buf));
-        p->fx_loop_buf = nullptr;
-    }
+    p->mem.release(&p->fx_loop_buf);
     if (p->fx_loopback) {
         p->fx_on = p->fx_loopback = false;
         p->fx_world = 1;
@@ -1439,7 +1255,7 @@ int oiva_plan_fused_loopback(oiva_plan* p, int world) {
     p->fx_nblk_peer = std::max(1, kCanonBlocks / world);
     OIVA_NEED((world - 1) * p->fx_nblk_peer <= kCanonBlocks, OIVA_ERR_ARG, "at most 9 ranks");
     const size_t bytes = (size_t)2 * world * p->fx_nblk_peer * p->T * p->K * 8;
-    OIVA_TRY_HIP(hipExtMallocWithFlags((void**)&p->fx_loop_buf, bytes, hipDeviceMallocFinegrained));
+    OIVA_TRY_HIP(p->mem.take_one(&p->fx_loop_buf, bytes, Mem::fine));
     OIVA_TRY_HIP(hipMemset(p->fx_loop_buf, 0, bytes));
     int rc = fused_setup(p);
     if (rc) return rc;
@@ -1466,36 +1282,21 @@ int oiva_plan_iterate_timed(oiva_plan* p, int n, float* total_ms, float* per_ker
     OIVA_NEED(n >= 1 && total_ms, OIVA_ERR_ARG, "bad arguments");
     OIVA_NEED(p->F == p->F_total, OIVA_ERR_STATE, "timed iterate needs a plan that owns all bins");
     DeviceGuard guard(p->device);
-    hipEvent_t e_begin = p->ev[0], e_end = p->ev[1];
-    if (!per_kernel_ms) {
-        OIVA_TRY_HIP(hipEventRecord(e_begin, p->stream));
-        if ((rc = oiva_plan_iterate(p, n))) return rc;
-        OIVA_TRY_HIP(hipEventRecord(e_end, p->stream));
-        OIVA_TRY_HIP(hipEventSynchronize(e_end));
-        OIVA_TRY_HIP(hipEventElapsedTime(total_ms, e_begin, e_end));
-        return OIVA_OK;
-    }
+    if (!per_kernel_ms) return p->stream.elapsed_ms(0, 1, [&] { return oiva_plan_iterate(p, n); }, total_ms);
     // per-kernel: an event before every launch and one after the last launch of each iteration, all
     // recorded without draining the stream; elapsed times are read after one final synchronisation.
     for (int s = 0; s < OIVA_N_STAGES; ++s) per_kernel_ms[s] = 0.f;
     *total_ms = 0.f;
     const int per_it = OIVA_N_STAGES + 1;
-    std::vector<hipEvent_t> pool((size_t)n * per_it, nullptr);
-    auto destroy = [&]() {
-        for (hipEvent_t e : pool)
-            if (e) (void)hipEventDestroy(e);
-    };
-    for (auto& e : pool) {
-        hipError_t err = hipEventCreate(&e);
-        if (err != hipSuccess) {
-            destroy();
-            return fail_with(OIVA_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(err));
-        }
-    }
-    std::vector<hipEvent_t> kev((size_t)2 * n, nullptr);
-    for (auto& e : kev)
-        if (hipEventCreate(&e) != hipSuccess) e = nullptr;
-    hipError_t err = hipSuccess;
+    // (two local event owners: the bracketing events, which must all exist, and the covariance kernel's own pairs, of which
+    //  as many are used as could be made)
+    HandleStream bracket, kern;
+    hipError_t err = bracket.add_events(n * per_it);
+    if (err != hipSuccess) return fail_with(OIVA_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(err));
+    if (kern.add_events(2 * n) != hipSuccess) (void)hipGetLastError();
+    std::vector<hipEvent_t>& pool = bracket.events;
+    std::vector<hipEvent_t> kev = kern.events;
+    kev.resize((size_t)2 * n, nullptr);
     for (int it = 0; it < n && err == hipSuccess && rc == OIVA_OK; ++it) {
         hipEvent_t* e = pool.data() + (size_t)it * per_it;
         err = hipEventRecord(e[0], p->stream);
@@ -1532,9 +1333,6 @@ int oiva_plan_iterate_timed(oiva_plan* p, int n, float* total_ms, float* per_ker
         }
     }
     if (err == hipSuccess && rc == OIVA_OK) err = hipEventElapsedTime(total_ms, pool[0], pool[(size_t)n * per_it - 1]);
-    destroy();
-    for (hipEvent_t e : kev)
-        if (e) (void)hipEventDestroy(e);
     if (rc) return rc;
     OIVA_TRY_HIP(err);
     return OIVA_OK;
@@ -1549,34 +1347,24 @@ int oiva_plan_get_cov_splits(oiva_plan* p, int* nsplit) {
 int oiva_plan_set_cov_splits(oiva_plan* p, int nsplit) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     OIVA_NEED(nsplit >= 0 && nsplit <= p->T, OIVA_ERR_ARG, "bad split count");
-    DeviceGuard guard(p->device);
-    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-    int rc = drop_graph(p);
-    if (rc) return rc;
-    choose_cov_geom(p, nsplit);
-    return ensure_vpart(p);
+    return change_geometry(p, [&] { choose_cov_geom(p, nsplit); return OIVA_OK; });
 }
 
 int oiva_plan_set_cov_quad(oiva_plan* p, int enable, int* active) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
-    DeviceGuard guard(p->device);
-    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-    int rc = drop_graph(p);
-    if (rc) return rc;
-    p->cov_quad_on = enable != 0;
-    choose_cov_geom(p, 0);
-    if (active) *active = p->cov.quad || p->cov.half16;
-    return ensure_vpart(p);
+    return change_geometry(p, [&] {
+        p->cov_quad_on = enable != 0;
+        choose_cov_geom(p, 0);
+        if (active) *active = p->cov.quad || p->cov.half16;
+        return OIVA_OK;
+    });
 }
 
 int oiva_plan_set_fuse_cov_update(oiva_plan* p, int enable, int* active) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
-    DeviceGuard guard(p->device);
     if (enable >= 0) {
-        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-        int rc = drop_graph(p);
+        const int rc = change_geometry(p, [&] { p->fuse_cov_update = enable != 0; return OIVA_OK; });
         if (rc) return rc;
-        p->fuse_cov_update = enable != 0;
     }
     if (active) *active = cov_update_applies(p) ? 1 : 0;
     return OIVA_OK;
@@ -1584,34 +1372,18 @@ int oiva_plan_set_fuse_cov_update(oiva_plan* p, int enable, int* active) {
 
 int oiva_plan_set_cov_hmfma(oiva_plan* p, int enable) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
-    DeviceGuard guard(p->device);
-    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-    int rc = drop_graph(p);
-    if (rc) return rc;
-    p->cov_hmfma_on = enable != 0;
-    choose_cov_geom(p, 0);
-    return ensure_vpart(p);
+    return change_geometry(p, [&] { p->cov_hmfma_on = enable != 0; choose_cov_geom(p, 0); return OIVA_OK; });
 }
 
 int oiva_plan_set_pow_splits(oiva_plan* p, int nsplit) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     OIVA_NEED(nsplit >= 0 && nsplit <= p->T, OIVA_ERR_ARG, "bad split count");
-    DeviceGuard guard(p->device);
-    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-    int rc = drop_graph(p);
-    if (rc) return rc;
-    choose_pow_geom(p, nsplit);
-    return OIVA_OK;
+    return change_geometry(p, [&] { choose_pow_geom(p, nsplit); return OIVA_OK; });
 }
 
 int oiva_plan_set_power_reverse(oiva_plan* p, int enable) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
-    DeviceGuard guard(p->device);
-    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-    int rc = drop_graph(p);
-    if (rc) return rc;
-    p->power_reverse = enable < 0 ? 0 : enable > 2 ? 2 : enable;
-    return OIVA_OK;
+    return change_geometry(p, [&] { p->power_reverse = enable < 0 ? 0 : enable > 2 ? 2 : enable; return OIVA_OK; });
 }
 
 int oiva_plan_use_graph(oiva_plan* p, int enable) {
@@ -1626,24 +1398,20 @@ int oiva_plan_use_graph(oiva_plan* p, int enable) {
 int oiva_plan_set_precision(oiva_plan* p, int flags) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     OIVA_NEED((flags & ~(OIVA_PREC_UPDATE_F64 | OIVA_PREC_UPDATE_ROWS | OIVA_PREC_COV_F64)) == 0, OIVA_ERR_ARG, "unknown precision flag");
-    DeviceGuard guard(p->device);
-    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-    int rc = drop_graph(p);
-    if (rc) return rc;
-    if ((flags & OIVA_PREC_UPDATE_F64) && p->have_w && !p->what64_valid) {
-        // switching the update to float64 mid-run: seed the complex128 copy from the complex64 state
-        std::vector<double2> wh;
-        if ((rc = download_what(p, wh)) || (rc = upload_what(p, wh))) return rc;
-    }
-    // (more than 8 channels: which float32 kernel takes the pass also depends on the arithmetic of the per-bin algebra;
-    // 8 channels with three or more sources: the number of frame splits does)
-    const bool cov_changed = ((flags ^ p->prec) & (OIVA_PREC_COV_F64 | ((p->M > 8 || p->cov.pair32) ? OIVA_PREC_UPDATE_F64 : 0))) != 0;
-    p->prec = flags;
-    if (cov_changed) {
-        choose_cov_geom(p, 0);            // sources per pass and residency depend on the accumulator type
-        if ((rc = ensure_vpart(p))) return rc;
-    }
-    return OIVA_OK;
+    return change_geometry(p, [&] {
+        if ((flags & OIVA_PREC_UPDATE_F64) && p->have_w && !p->what64_valid) {
+            // switching the update to float64 mid-run: seed the complex128 copy from the complex64 state
+            std::vector<double2> wh;
+            int rc;
+            if ((rc = download_what(p, wh)) || (rc = upload_what(p, wh))) return rc;
+        }
+        // (more than 8 channels: which float32 kernel takes the pass also depends on the arithmetic of the per-bin algebra;
+        // 8 channels with three or more sources: the number of frame splits does)
+        const bool cov_changed = ((flags ^ p->prec) & (OIVA_PREC_COV_F64 | ((p->M > 8 || p->cov.pair32) ? OIVA_PREC_UPDATE_F64 : 0))) != 0;
+        p->prec = flags;
+        if (cov_changed) choose_cov_geom(p, 0);            // sources per pass and residency depend on the accumulator type
+        return (int)OIVA_OK;
+    });
 }
 
 // ---- X-resident iteration ------------------------------------------------------------------------------
@@ -1672,8 +1440,7 @@ int oiva_plan_set_resident_splits(oiva_plan* p, int nsplit) {
     OIVA_NEED(ok || nsplit == 0, OIVA_ERR_ARG, "the shape does not fit on chip with that many frame splits");
     if (p->res_block) {                        // buffers were sized for the old geometry
         OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-        OIVA_TRY_HIP(hipFree(p->res_block));
-        p->res_block = nullptr;
+        p->mem.release(&p->res_block);
     }
     p->res_ok = ok;
     if (ok) p->rg = g;
@@ -1687,8 +1454,7 @@ int oiva_plan_resident_loopback(oiva_plan* p, int world) {
     DeviceGuard guard(p->device);
     if (p->res_loop_buf) {
         OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-        OIVA_TRY_HIP(hipFree(p->res_loop_buf));
-        p->res_loop_buf = nullptr;
+        p->mem.release(&p->res_loop_buf);
     }
     p->res_loopback = false;
     p->res_world = 1;
@@ -1700,7 +1466,7 @@ int oiva_plan_resident_loopback(oiva_plan* p, int world) {
     // the gather buffer of the multi-GPU exchange, same kind of memory (fine-grained, system-scope atomics), but nobody else
     // maps it: [2 (epoch parity)][world][NS * TW][K] floats
     const size_t bytes = (size_t)2 * world * p->rg.NS * p->rg.TW * p->K * sizeof(float);
-    OIVA_TRY_HIP(hipExtMallocWithFlags((void**)&p->res_loop_buf, bytes, hipDeviceMallocFinegrained));
+    OIVA_TRY_HIP(p->mem.take_one(&p->res_loop_buf, bytes, Mem::fine));
     OIVA_TRY_HIP(hipMemset(p->res_loop_buf, 0, bytes));
     for (int r = 0; r < world; ++r) p->res_gath[r] = p->res_loop_buf;
     p->res_world = world;
@@ -1805,11 +1571,13 @@ int oiva_plan_ogive_begin(oiva_plan* p, int update_mode, int model) {
     OIVA_NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
     DeviceGuard guard(p->device);
     const size_t F = p->F, M = p->M;
-    if (p->og_bufs.empty()) {
-        AllocChain alloc;
-        alloc.keep = &p->og_bufs;
-        alloc_ogive_state(p->og, F, M, alloc);
-        if (!alloc.ok()) return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
+    if (!p->og.maxdelta) {               // (the last of the state: all of it or none)
+        const size_t before = p->mem.mark();
+        alloc_ogive_state(p->og, F, M, p->mem);
+        if (!p->mem.ok()) {
+            p->mem.release_to(before);
+            return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(p->mem.status()));
+        }
     }
     if (!p->what64_valid) {              // the step kernel reads and writes the complex128 copy of w
         std::vector<double2> wh;
@@ -2003,13 +1771,13 @@ int oiva_test_time_stage(oiva_plan* p, int stage, int reps, float* avg_ms) {
         }
     };
     if ((rc = run())) return rc;  // warm
-    OIVA_TRY_HIP(hipEventRecord(p->ev[0], p->stream));
-    for (int i = 0; i < reps; ++i)
-        if ((rc = run())) return rc;
-    OIVA_TRY_HIP(hipEventRecord(p->ev[1], p->stream));
-    OIVA_TRY_HIP(hipEventSynchronize(p->ev[1]));
     float ms = 0.f;
-    OIVA_TRY_HIP(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
+    rc = p->stream.elapsed_ms(0, 1, [&] {
+        int r = OIVA_OK;
+        for (int i = 0; i < reps && r == OIVA_OK; ++i) r = run();
+        return r;
+    }, &ms);
+    if (rc) return rc;
     *avg_ms = ms / reps;
     return OIVA_OK;
 }

@@ -88,7 +88,8 @@ __global__ __launch_bounds__(kBlock) void overlap_add_kernel(const float* __rest
 struct oiva_stft {
     int device = 0;
     int n_samples = 0, C = 0, L = 0, hop = 0, T = 0, F = 0;
-    hipStream_t stream = nullptr;
+    HandleStream stream;
+    DeviceArena mem;
     hipfftHandle fwd = 0, inv = 0;
     bool have_fwd = false, have_inv = false;
     int inv_chan = -1;        // channel count the inverse plan was made for
@@ -121,24 +122,19 @@ int oiva_stft_create(oiva_stft** out, int device, int n_samples, int n_chan, int
     p->hop = hop;
     p->T = n_samples / hop;
     p->F = frame / 2 + 1;
-    AllocChain alloc;
-    alloc.err = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+    DeviceArena& mem = p->mem;
+    mem.note(p->stream.open(nullptr, 0));
     const size_t nx = (size_t)std::max(n_samples, p->T * hop) * n_chan;
-    alloc(&p->x, nx * sizeof(float));
-    alloc(&p->frames, (size_t)p->T * n_chan * frame * sizeof(float));
-    alloc(&p->spec, (size_t)p->T * n_chan * p->F * sizeof(float2));
-    alloc(&p->X, (size_t)p->T * n_chan * p->F * sizeof(float2));
-    if (win_a) {
-        alloc(&p->win_a, frame * sizeof(float));
-        if (alloc.ok()) alloc.err = hipMemcpy(p->win_a, win_a, frame * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (win_s) {
-        alloc(&p->win_s, frame * sizeof(float));
-        if (alloc.ok()) alloc.err = hipMemcpy(p->win_s, win_s, frame * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (!alloc.ok()) {
+    mem.take(&p->x, nx * sizeof(float));
+    mem.take(&p->frames, (size_t)p->T * n_chan * frame * sizeof(float));
+    mem.take(&p->spec, (size_t)p->T * n_chan * p->F * sizeof(float2));
+    mem.take(&p->X, (size_t)p->T * n_chan * p->F * sizeof(float2));
+    if (win_a) mem.take_filled(&p->win_a, win_a, frame * sizeof(float));
+    if (win_s) mem.take_filled(&p->win_s, win_s, frame * sizeof(float));
+    if (!mem.ok()) {
+        const hipError_t e = mem.status();
         oiva_stft_destroy(p);
-        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(alloc.err));
+        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(e));
     }
     *out = p;
     return OIVA_OK;
@@ -150,10 +146,8 @@ int oiva_stft_destroy(oiva_stft* p) {
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     if (p->have_fwd) (void)hipfftDestroy(p->fwd);
     if (p->have_inv) (void)hipfftDestroy(p->inv);
-    void* bufs[] = {p->win_a, p->win_s, p->x, p->frames, p->spec, p->X};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (p->stream) (void)hipStreamDestroy(p->stream);
+    p->mem.clear();
+    p->stream.close();
     delete p;
     return OIVA_OK;
 }

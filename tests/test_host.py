@@ -157,6 +157,24 @@ def test_plain_c_program_links_against_the_abi(lib, tmp_path):
         assert run.returncode == 2 and "no GPU" in run.stderr      # loud failure, no CPU path
 
 
+def test_device_arena_ownership_logic(tmp_path):
+    """DeviceArena (csrc/host_util.h), the one owner of every handle's device memory, against counting fake allocators in a
+    stand-alone program: every buffer freed once, by its kind's deallocator and with its size; the first error of a chain wins;
+    release_to / release free what they should and nothing else; the halve-and-retry allocation of bss_eval"""
+    import subprocess
+
+    from overiva_amd import build
+
+    exe = tmp_path / "arena_main"
+    host_flags = [f for f in build.FLAGS if not f.startswith("--offload-arch")]
+    r = subprocess.run([build._hipcc(), *host_flags, os.path.join(REPO, "tests", "helpers", "arena_main.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert run.stdout.strip() == "arena ok"
+
+
 def test_resident_kernels_use_no_scratch_memory(lib):
     """the X-resident kernels hold 128 covariance accumulators in the architectural registers and up to 128 floats of X in
     the accumulator file; a build whose register allocation falls over into scratch memory (per-lane stack in HBM) would
