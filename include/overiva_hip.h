@@ -355,6 +355,14 @@ int oiva_test_time_stage(oiva_plan *p, int stage, int reps, float *avg_ms);
 /* Test hook: device and pinned buffers the library has handed to its handles and temporaries and not yet taken back, and their
  * bytes, over all handles of the process.  A large buffer resting in the pool (oiva_pool_trim) counts as taken back. */
 int oiva_test_live_buffers(long long *count, long long *bytes);
+/* Test hook: the kernels and geometry a plan of this shape and these settings would run on `device` (csrc/kernel_choice.h), by
+ * the functions a plan chooses with; nothing is allocated.  prec_flags: OIVA_PREC_*; quad_on / hmfma_on: the switches of
+ * oiva_plan_set_cov_quad / _hmfma; *_splits_req: 0 or the splits asked for.  out (18): covariance kind, nsplit, tc, kc, nbg, pad,
+ * part32, partials are float64, kind of the unit-weights pass; power kind, nb, nsplit, tcp, kp, rounds; the two occupancy
+ * figures the choice asked the device for (covariance, power; -1: not asked, 0: the query failed); the device's CU count.
+ * Kinds count from 0 in the order of CovKind / PowKind. */
+int oiva_test_kernel_choice(int device, int T, int F, int F_total, int M, int K, int prec_flags, int quad_on, int hmfma_on,
+                            int cov_splits_req, int pow_splits_req, int *out);
 
 /*
  * OGIVE -- orthogonally constrained independent vector extraction of ONE source by gradient steps, the reference's

@@ -34,9 +34,6 @@
 
 namespace oiva {
 
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
-
 // makes `dev` the calling thread's current device for the life of the guard and puts back what it found: every entry point
 // leaves the caller's current device alone
 struct DeviceGuard {

@@ -419,29 +419,6 @@ hipError_t dispatch_cov(int M, int kc, bool unit, Fn&& fn) {
 
 }  // namespace
 
-bool cov_supported(int M) { return M >= 1 && M <= kWideMax; }
-
-// sources handled per pass over X
-int cov_sources_per_pass(int M, int K, bool f64, bool short_axis) {
-    if (f64 && cov_pair64_supported(M)) return cov_pair64_sources_per_pass(K);
-    if (!f64 && cov_pair32_supported(M, K)) return cov_pair32_sources_per_pass();
-    const int regs = M * M * (f64 ? 2 : 1);   // as many as fit the accumulator budget (KC * M^2 <= 144 registers)
-    int kc = 1;
-    if (K >= 2 && regs * 2 <= 144) kc = 2;
-    if (K >= 3 && regs * 4 <= 144) kc = 4;
-    // 7 channels / 3+ sources and 5 / 5: a third / fifth source per pass (147 / 125 accumulators: two waves per SIMD instead of
-    // three, a pass of 7 channels 100 us instead of 75 at 2048 x 4000) where that saves a whole pass over X.  Measured (covariance
-    // pass, iteration): 2048 x 4000 x 7 / 3 162 -> 105 us (239 -> 198), 5 / 5 121 -> 93 (203 -> 181), 2049 x 235 x 7 / 3 22.0 ->
-    // 16.5 (51.8 -> 47.6), 7 / 7 34.0 -> 27.2 (73.8 -> 66.6); not 7 / 4 (two passes either way: 21.8 -> 23.4) and 7 / 7 only on
-    // a short frame axis (2048 x 4000: three passes of three 294 us, four of two 283).  $OIVA_COV_KC_WIDE=0: off.
-    static const bool wide = [] { const char* v = std::getenv("OIVA_COV_KC_WIDE"); return !(v && v[0] == '0'); }();
-    if (!f64 && wide) {
-        if (M == 7 && (K == 3 || K == 5 || K == 6 || (K == 7 && short_axis))) kc = 3;
-        if (M == 5 && K >= 5) kc = 5;
-    }
-    return kc;
-}
-
 // one zero channel behind every (frame, bin)'s M: the even channel pitch the vector-ALU kernels of 10..16 channels read
 __global__ __launch_bounds__(kBlock) void pad_channels_kernel(const float2* __restrict__ X, float2* __restrict__ Xpad, long long n, int M) {
     const long long e = (long long)blockIdx.x * kBlock + threadIdx.x;          // element of the padded tensor
@@ -459,17 +436,31 @@ hipError_t launch_pad_channels(hipStream_t s, const float2* X, float2* Xpad, lon
 
 hipError_t launch_cov(hipStream_t s, const float2* X, const float2* Xpad, const float* R, float* Wt, float* wscale, int model, int raw,
                       void* Vpart, bool f64, int T, int F, int M, int K, const CovGeom& g) {
-    if (M > kNarrowMax) return launch_cov_wide(s, X, R, Wt, wscale, model, raw, static_cast<double*>(Vpart), T, F, M, K, g);
-    if (g.pad && Xpad == nullptr) return hipErrorInvalidValue;
-    const float2* Xv = g.pad ? Xpad : X;        // what the vector-ALU kernels of 10..16 channels read, at a pitch of Mp channels
-    const int Mp = g.pad ? M + 1 : M;
-    if (M > 8 && g.half16 && !f64) return launch_cov_half16(s, Xv, R, Wt, wscale, model, raw, static_cast<double*>(Vpart), T, F, Mp, M, K, g);
-    if (M > 8 && g.half16 && f64 && R != nullptr)
-        return launch_cov_half16_f64(s, Xv, R, Wt, wscale, model, raw, static_cast<double*>(Vpart), T, F, Mp, M, K, g);
-    if (M > 8 && g.quad && !f64) return launch_cov_quad(s, Xv, R, Wt, wscale, model, raw, static_cast<double*>(Vpart), T, F, Mp, M, K, g);
-    if (M > 8) return launch_cov_mfma(s, X, R, Wt, wscale, model, raw, Vpart, f64, T, F, M, K, g.nsplit, g.tc);
-    if (!f64 && g.pair32) return launch_cov_pair32(s, X, R, Wt, wscale, model, raw, static_cast<double*>(Vpart), T, F, M, K, g);
-    if (f64 && cov_pair64_supported(M)) return launch_cov_pair64(s, X, R, Wt, wscale, model, raw, static_cast<double*>(Vpart), T, F, M, K, g);
+    const CovTraits& t = traits(g.kind);
+    if (g.tc % t.quantum != 0 || (g.pad && Xpad == nullptr)) return hipErrorInvalidValue;
+    const float2* Xv = g.pad && t.padded_x ? Xpad : X;        // what the vector-ALU kernels of 10..16 channels read, at a pitch of Mp channels
+    const int Mp = g.pad && t.padded_x ? M + 1 : M;
+    double* const V64 = static_cast<double*>(Vpart);
+    switch (g.kind) {
+        case CovKind::Wide: return launch_cov_wide(s, X, R, Wt, wscale, model, raw, V64, T, F, M, K, g);
+        case CovKind::Half16: return launch_cov_half16(s, Xv, R, Wt, wscale, model, raw, V64, T, F, Mp, M, K, g);
+        case CovKind::Hmfma: {
+            // nine and more sources: the weighted sums of all sources as one small GEMM per bin on the fp32 matrix cores, the
+            // Hermitian products on the vector ALU beside it (kernels_cov_hmfma.hip), behind the weights pre-pass of its sibling
+            const hipError_t e = launch_cov_half16_weights(s, R, Wt, wscale, model, raw, T, K);
+            return e != hipSuccess ? e : launch_cov_hmfma(s, Xv, Wt, V64, T, F, Mp, M, K, g);
+        }
+        case CovKind::Half16F64: return launch_cov_half16_f64(s, Xv, R, Wt, wscale, model, raw, V64, T, F, Mp, M, K, g);
+        case CovKind::Hmfma64: {
+            const hipError_t e = launch_cov_half16_weights_f64(s, R, Wt, wscale, model, raw, T, K);
+            return e != hipSuccess ? e : launch_cov_hmfma64(s, Xv, reinterpret_cast<const double*>(Wt), V64, T, F, Mp, M, K, g);
+        }
+        case CovKind::Quad: return launch_cov_quad(s, Xv, R, Wt, wscale, model, raw, V64, T, F, Mp, M, K, g);
+        case CovKind::Mfma: return launch_cov_mfma(s, X, R, Wt, wscale, model, raw, Vpart, f64, T, F, M, K, g.nsplit, g.tc);
+        case CovKind::Pair32: return launch_cov_pair32(s, X, R, Wt, wscale, model, raw, V64, T, F, M, K, g);
+        case CovKind::Pair64: return launch_cov_pair64(s, X, R, Wt, wscale, model, raw, V64, T, F, M, K, g);
+        case CovKind::Lane: break;
+    }
     const int kc = R == nullptr ? 1 : g.kc;
     if (f64)
         return dispatch_cov<double>(M, kc, R == nullptr, [&](CovKernel<double> kern, int KC) {
@@ -485,10 +476,6 @@ hipError_t launch_cov(hipStream_t s, const float2* X, const float2* Xpad, const 
 
 // workgroups of this instantiation that one CU holds at once (registers / LDS limited)
 hipError_t cov_blocks_per_cu(int M, int kc, bool f64, int* n) {
-    if ((f64 && cov_pair64_supported(M)) || (!f64 && M == 8 && kc == 4)) {
-        *n = 2;
-        return hipSuccess;
-    }
     if (f64)
         return dispatch_cov<double>(M, kc, false, [&](CovKernel<double> kern, int) {
             return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, kern, kBlock, 0);

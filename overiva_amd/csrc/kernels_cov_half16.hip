@@ -431,25 +431,26 @@ __global__ __launch_bounds__(kBlock, NS == 8 ? 2 : 4) void cov_half16f64_kernel(
 
 }  // namespace
 
-bool cov_half16_supported(int M, int K) { return M >= 10 && M <= 16 && M % 2 == 0 && K >= 1 && K <= 16; }
-int cov_half16_sources_per_pass(int K) { return K <= 8 ? 8 : (K <= 12 ? 12 : 16); }
+static_assert(traits(CovKind::Half16).quantum == 4 * kH16Frames && traits(CovKind::Half16F64).quantum == 4 * kH16Frames, "kernel_choice.h");
+
+// the weights pre-pass of Half16 and Hmfma: Wt (T + 1, 16) floats, row T zeroed
+hipError_t launch_cov_half16_weights(hipStream_t s, const float* R, float* Wt, float* wscale, int model, int raw, int T, int K) {
+    if (R == nullptr || Wt == nullptr) return hipErrorInvalidValue;
+    const hipError_t e = launch_cov_weights(s, R, Wt, wscale, model, raw, T, K, kH16WeightStride);
+    return e != hipSuccess ? e : hipMemsetAsync(Wt + (size_t)T * kH16WeightStride, 0, kH16WeightStride * sizeof(float), s);
+}
 
 // Wt: (T + 1, 16) scratch for the final weights (row T zeroed here); R == nullptr: unit weights (K = 1)
 hipError_t launch_cov_half16(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                              double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g) {
-    if (!cov_half16_supported(M, K) || Mv > M || Mv < M - 1 || g.tc % (4 * kH16Frames) != 0) return hipErrorInvalidValue;
+    if (!traits(CovKind::Half16).supported(M, K) || Mv > M || Mv < M - 1) return hipErrorInvalidValue;
     const dim3 grid((F + 1) / 2, g.nsplit, 1), block(kBlock);
     if (R == nullptr) {
         if (K != 1) return hipErrorInvalidValue;
         return launch_dominant(cov_half16_kernel<1, true>, grid, block, 0, s, X, (const float*)nullptr, Vpart, T, F, M, Mv, K, g.tc);
     }
-    if (Wt == nullptr) return hipErrorInvalidValue;
-    hipError_t e = launch_cov_weights(s, R, Wt, wscale, model, raw, T, K, kH16WeightStride);
-    if (e == hipSuccess) e = hipMemsetAsync(Wt + (size_t)T * kH16WeightStride, 0, kH16WeightStride * sizeof(float), s);
+    const hipError_t e = launch_cov_half16_weights(s, R, Wt, wscale, model, raw, T, K);
     if (e != hipSuccess) return e;
-    // nine and more sources: the weighted sums of all sources as one small GEMM per bin on the fp32 matrix cores, the
-    // Hermitian products on the vector ALU beside it (kernels_cov_hmfma.hip; CovGeom::hmfma, on by default)
-    if (g.hmfma && cov_hmfma_supported(M, K)) return launch_cov_hmfma(s, X, Wt, Vpart, T, F, M, Mv, K, g);
     if (K <= 8)
         return launch_dominant(cov_half16_kernel<4, false>, grid, block, 0, s, X, (const float*)Wt, Vpart, T, F, M, Mv, K, g.tc);
     if (K <= 12)
@@ -457,24 +458,23 @@ hipError_t launch_cov_half16(hipStream_t s, const float2* X, const float* R, flo
     return launch_dominant(cov_half16_kernel<8, false>, grid, block, 0, s, X, (const float*)Wt, Vpart, T, F, M, Mv, K, g.tc);
 }
 
-// float64 sums (the `precise` arithmetic): 4 or 8 sources per pass.  Wt: scratch of (T + 1) x 16 doubles.
-// (one or two sources stay on the fp64 matrix-core kernel: a two-source instantiation of this one measured 523-590 us against
-//  474 at 2048 bins x 4000 frames x 16 channels -- the 34 conversion and product instructions per lane and frame are then
-//  two thirds of the work; three or four sources: 692 against 836 us, five to eight 1.06 against 1.57 ms, sixteen 2.08 against 3.10)
-bool cov_half16_f64_supported(int M, int K) { return M >= 10 && M <= 16 && M % 2 == 0 && K >= 3 && K <= 16; }
-int cov_half16_f64_sources_per_pass(int K) { return K <= 4 ? 4 : 8; }
+// the weights pre-pass of Half16F64 and Hmfma64: Wt as (T + 1, 16) doubles, row T zero
+hipError_t launch_cov_half16_weights_f64(hipStream_t s, const float* R, float* Wt, float* wscale, int model, int raw, int T, int K) {
+    if (R == nullptr || Wt == nullptr) return hipErrorInvalidValue;
+    h64_weights_kernel<<<dim3(((T + 1) * kH64WeightStride + kBlock - 1) / kBlock), dim3(kBlock), 0, s>>>(R, reinterpret_cast<double*>(Wt), wscale, model, raw, T, K);
+    return hipGetLastError();
+}
 
+// float64 sums (the `precise` arithmetic): 4 or 8 sources per pass.  Wt: scratch of (T + 1) x 16 doubles.
 hipError_t launch_cov_half16_f64(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                                  double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g) {
-    if (!cov_half16_f64_supported(M, K) || Mv > M || Mv < M - 1 || R == nullptr || Wt == nullptr || (!g.hmfma && g.tc % (4 * kH16Frames) != 0)) return hipErrorInvalidValue;
-    double* wt = reinterpret_cast<double*>(Wt);
-    h64_weights_kernel<<<dim3(((T + 1) * kH64WeightStride + kBlock - 1) / kBlock), dim3(kBlock), 0, s>>>(R, wt, wscale, model, raw, T, K);
-    hipError_t e = hipGetLastError();
+    if (!traits(CovKind::Half16F64).supported(M, K) || Mv > M || Mv < M - 1) return hipErrorInvalidValue;
+    const hipError_t e = launch_cov_half16_weights_f64(s, R, Wt, wscale, model, raw, T, K);
     if (e != hipSuccess) return e;
-    if (g.hmfma && cov_hmfma64_supported(M, K)) return launch_cov_hmfma64(s, X, wt, Vpart, T, F, M, Mv, K, g);
-    const int ns = cov_half16_f64_sources_per_pass(K);
+    const double* wt = reinterpret_cast<const double*>(Wt);
+    const int ns = traits(CovKind::Half16F64).sources(K);
     const dim3 grid((F + 1) / 2, g.nsplit, (K + ns - 1) / ns);
-    if (ns == 4) return launch_dominant(cov_half16f64_kernel<4>, grid, dim3(kBlock), 0, s, X, (const double*)wt, Vpart, T, F, M, Mv, K, g.tc);
+    if (ns == 4) return launch_dominant(cov_half16f64_kernel<4>, grid, dim3(kBlock), 0, s, X, wt, Vpart, T, F, M, Mv, K, g.tc);
     return launch_dominant(cov_half16f64_kernel<8>, grid, dim3(kBlock), 0, s, X, (const double*)wt, Vpart, T, F, M, Mv, K, g.tc);
 }
 

@@ -681,16 +681,12 @@ __global__ __launch_bounds__(kBlock, 2) void cov_hmfma64_kernel(const float2* __
 
 }  // namespace
 
-// 9..16 sources on 10/12/14/16 channels (odd counts: the padded copy of X).  Wt: the (T + 1, 16) table of final weights of
-// launch_cov_weights, row T zeroed (kernels_cov_half16.hip fills it and calls this).
-bool cov_hmfma_supported(int M, int K) { return M >= 10 && M <= 16 && M % 2 == 0 && K >= 9 && K <= 16; }
+static_assert(traits(CovKind::Hmfma).quantum == 8 * kHmFrames && traits(CovKind::Hmfma64).quantum == 8 * kHmFrames, "kernel_choice.h");
 
-// float64 sums (`precise`): exactly 16 channels (15: the padded copy of X), 9..16 sources.  Wt: the (T + 1, 16) table of float64
-// weights of kernels_cov_half16.hip (h64_weights_kernel), row T zero.
-bool cov_hmfma64_supported(int M, int K) { return M == 16 && K >= 9 && K <= 16; }
+// Wt: the (T + 1, 16) table of final weights, row T zero, float32 (launch_cov_half16_weights) or float64 (.._weights_f64)
 
 hipError_t launch_cov_hmfma64(hipStream_t s, const float2* X, const double* Wt, double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g) {
-    if (!cov_hmfma64_supported(M, K) || Mv > M || Mv < M - 1 || Wt == nullptr || g.tc % (8 * kHmFrames) != 0) return hipErrorInvalidValue;
+    if (!traits(CovKind::Hmfma64).supported(M, K) || Mv > M || Mv < M - 1 || Wt == nullptr) return hipErrorInvalidValue;
     const char* flat = std::getenv("OIVA_HMFMA_FLAT");
     if (!(flat && flat[0] == '1') && (size_t)36 * F * M * 8 < 0xffffffffull)
         return launch_dominant(cov_hmfma64_kernel<true>, dim3(F, g.nsplit, 1), dim3(kBlock), 0, s, X, Wt, Vpart, T, F, Mv, K, g.tc);
@@ -698,7 +694,7 @@ hipError_t launch_cov_hmfma64(hipStream_t s, const float2* X, const double* Wt, 
 }
 
 hipError_t launch_cov_hmfma(hipStream_t s, const float2* X, const float* Wt, double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g) {
-    if (!cov_hmfma_supported(M, K) || Mv > M || Mv < M - 1 || Wt == nullptr || g.tc % (8 * kHmFrames) != 0) return hipErrorInvalidValue;
+    if (!traits(CovKind::Hmfma).supported(M, K) || Mv > M || Mv < M - 1 || Wt == nullptr) return hipErrorInvalidValue;
     const dim3 grid(F, g.nsplit, 1), block(kBlock);
     // the buffer form of the DMAs: a lane's offset from the first frame of a stage is 32 bits
     // ($OIVA_HMFMA_FLAT=1, read at every launch: the flat form whatever the size -- tests compare the two bit for bit)

@@ -266,19 +266,18 @@ __global__ __launch_bounds__(kBlock, 2) void cov_pair32_kernel(const float2* __r
 
 }  // namespace
 
-bool cov_pair32_supported(int M, int K) { return M == 8 && K >= 3; }
-int cov_pair32_sources_per_pass() { return kP32Sources; }
-int cov_pair32_bins_per_block() { return kP32Bins; }
+static_assert(traits(CovKind::Pair32).quantum == 4 * kP32Frames && traits(CovKind::Pair32).bins == kP32Bins && traits(CovKind::Pair32).sources(8) == kP32Sources,
+              "kernel_choice.h");
 
 hipError_t launch_cov_pair32(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                              double* Vpart, int T, int F, int M, int K, const CovGeom& g) {
-    if (M != 8 || g.tc % (4 * kP32Frames) != 0) return hipErrorInvalidValue;
+    if (M != 8) return hipErrorInvalidValue;
     if (R == nullptr) {       // unit weights (Cx of a plan whose weighted pass runs here): one "source"
         if (K != 1) return hipErrorInvalidValue;
         return launch_dominant(cov_pair32_kernel<true>, dim3(g.nbg, g.nsplit, 1), dim3(kBlock), 0, s, X, (const float*)nullptr, Vpart, T,
                                F, K, g.tc);
     }
-    if (!cov_pair32_supported(M, K) || Wt == nullptr) return hipErrorInvalidValue;
+    if (!traits(CovKind::Pair32).supported(M, K) || Wt == nullptr) return hipErrorInvalidValue;
     hipError_t e = launch_cov_weights(s, R, Wt, wscale, model, raw, T, K, kP32WeightStride);
     if (e != hipSuccess) return e;
     return launch_dominant(cov_pair32_kernel<false>, dim3(g.nbg, g.nsplit, (K + kP32Sources - 1) / kP32Sources), dim3(kBlock), 0, s, X,

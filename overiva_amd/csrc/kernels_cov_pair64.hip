@@ -273,13 +273,11 @@ __global__ __launch_bounds__(kBlock, 2) void cov_pair64_kernel(const float2* __r
 
 }  // namespace
 
-bool cov_pair64_supported(int M) { return M == 8; }
-int cov_pair64_sources_per_pass(int K) { return K >= 2 ? 2 : 1; }
-int cov_pair64_bins_per_block() { return kPairBins; }
+static_assert(traits(CovKind::Pair64).quantum == 4 * kPairFrames && traits(CovKind::Pair64).bins == kPairBins, "kernel_choice.h");
 
 hipError_t launch_cov_pair64(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                              double* Vpart, int T, int F, int M, int K, const CovGeom& g) {
-    if (!cov_pair64_supported(M) || g.tc % (4 * kPairFrames) != 0 || K > kPairWeightStride) return hipErrorInvalidValue;
+    if (!traits(CovKind::Pair64).supported(M, K) || K > kPairWeightStride) return hipErrorInvalidValue;
     const dim3 block(kBlock);
     if (R == nullptr) {
         if (K != 1) return hipErrorInvalidValue;

@@ -342,13 +342,11 @@ __global__ __launch_bounds__(kBlock, 2) void cov_quad_kernel(const float2* __res
 }  // namespace
 
 // M: channel pitch of X (even); Mv <= M: channels of the matrices (an odd channel count runs on a copy of X padded by one zero channel)
-bool cov_quad_supported(int M, int K) { return M >= 10 && M <= 16 && M % 2 == 0 && K >= 1 && K <= 4; }
-
-int cov_quad_sources_per_pass(int K) { return K >= 2 ? 2 : 1; }
+static_assert(traits(CovKind::Quad).quantum == 4 * kQuadFrames && traits(CovKind::Quad).bins == kBinsPerWave, "kernel_choice.h");
 
 hipError_t launch_cov_quad(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                            double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g) {
-    if (!cov_quad_supported(M, K) || Mv > M || Mv < M - 1 || g.tc % (4 * kQuadFrames) != 0) return hipErrorInvalidValue;
+    if (!traits(CovKind::Quad).supported(M, K) || Mv > M || Mv < M - 1) return hipErrorInvalidValue;
     if (R == nullptr) {
         if (K != 1) return hipErrorInvalidValue;
         return launch_dominant(cov_quad_kernel<1, true>, dim3(g.nbg, g.nsplit, 1), dim3(kBlock), 0, s, X, (const float*)nullptr, Vpart,

@@ -252,15 +252,6 @@ hipError_t launch_write_one(hipStream_t s, const float2* X, const float2* What, 
 
 }  // namespace
 
-int pow_sources_per_pass(int M, int K) {
-    // (round 5, measured and dropped: all of 5..8 sources in ONE pass, power_kernel<M, 8> -- 2049 x 235: 5 / 5 10.3 -> 11.7 us,
-    //  6 / 6 11.9 -> 12.8, 7 / 7 13.5 -> 14.5, 8 / 8 17.8 -> 18.9; 2048 x 4000: 8 / 8 121 -> 129, 5 / 5 75 -> 76, only 8 / 5
-    //  140 -> 111: eight demixing products per frame make the pass arithmetic-bound, two passes of four overlap)
-    if (K >= 3) return 4;
-    if (K >= 2) return 2;
-    return 1;
-}
-
 hipError_t pow_blocks_per_cu(int M, int kp, int tcp, int* n) {
     const size_t shmem = (size_t)kWaves * tcp * kp * sizeof(float);
 #define CALL(MM)                                                                                                   \
@@ -274,11 +265,13 @@ hipError_t pow_blocks_per_cu(int M, int kp, int tcp, int* n) {
 
 hipError_t launch_power(hipStream_t s, const float2* X, const float2* Xpad, const float2* What, float* Ppart, int T, int F, int M,
                         int K, const PowGeom& g) {
-    if (M > kNarrowMax) return launch_power_wide(s, X, What, Ppart, T, F, M, K, g);
-    // more than 4 sources would take several VALU passes over X (register budget): one MFMA pass instead
-    // (measured at 16 channels: 16 sources 770 -> 325 us; 2 sources 191 us VALU vs 332 us MFMA); an odd channel count
-    // reads the copy of X padded by one zero channel (16-byte loads instead of 8-byte ones)
-    if (M > 8 && K > 4) return Xpad ? launch_power_mfma(s, Xpad, What, Ppart, T, F, M, M + 1, K) : launch_power_mfma(s, X, What, Ppart, T, F, M, M, K);
+    if (!traits(g.kind).supported(M, K)) return hipErrorInvalidValue;
+    switch (g.kind) {
+        case PowKind::Wide: return launch_power_wide(s, X, What, Ppart, T, F, M, K, g);
+        case PowKind::Mfma: return Xpad ? launch_power_mfma(s, Xpad, What, Ppart, T, F, M, M + 1, K) : launch_power_mfma(s, X, What, Ppart, T, F, M, M, K);
+        case PowKind::Lds: return launch_power_lds(s, X, What, Ppart, T, F, M, K);
+        case PowKind::Lane: break;
+    }
 #define CALL(MM)                                                                                        \
     if (g.kp == 1) return launch_power_one<MM, 1>(s, X, What, Ppart, T, F, K, g);                       \
     if (g.kp == 2) return launch_power_one<MM, 2>(s, X, What, Ppart, T, F, K, g);                       \

@@ -336,13 +336,14 @@ hipError_t launch_power_mfma(hipStream_t s, const float2* X, const float2* What,
     // measured at 2048 x 4000 x 16 / 16 (tiles x bins per group): 4x1 252 us, 2x1 252, 2x2 267, 1x2 279, 1x4 306 -- the
     // W operands come from L2 once per wave and bin, so more frames per wave is less W traffic (W-only 81 us at 1x4);
     // X alone streams in 199 us, the MFMAs alone take 134 us
-    // 16 channels, at least 64 bins: X staged through LDS in 2 KB runs (power_lds_kernel above); $OIVA_POWER_LDS=0: off
-    static const bool lds = [] { const char* v = getenv("OIVA_POWER_LDS"); return !(v && v[0] == '0'); }();
-    if (lds && M == 16 && Mp == 16 && F >= kBinsPerBatch && T >= 16) {
-        power_lds_kernel<<<dim3((F + kBinsPerBatch - 1) / kBinsPerBatch, (T + kPlFrames - 1) / kPlFrames), dim3(kBlock), 0, s>>>(X, What, Ppart, T, F, K);
-        return hipGetLastError();
-    }
     return launch_shape<4, 1>(s, X, What, Ppart, T, F, M, Mp, K);
+}
+
+// 16 channels, at least 64 bins: X staged through LDS in 2 KB runs (power_lds_kernel above; PowKind::Lds)
+hipError_t launch_power_lds(hipStream_t s, const float2* X, const float2* What, float* Ppart, int T, int F, int M, int K) {
+    if (M != 16 || F < kBinsPerBatch || T < 16) return hipErrorInvalidValue;
+    power_lds_kernel<<<dim3((F + kBinsPerBatch - 1) / kBinsPerBatch, (T + kPlFrames - 1) / kPlFrames), dim3(kBlock), 0, s>>>(X, What, Ppart, T, F, K);
+    return hipGetLastError();
 }
 
 }  // namespace oiva

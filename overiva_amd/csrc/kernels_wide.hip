@@ -469,9 +469,8 @@ __global__ __launch_bounds__(kBlock) void wide_update_kernel(UpdateArgs a) {
 
 }  // namespace
 
-bool wide_channels(int M) { return M > kNarrowMax && M <= kWideMax; }
-
-int wide_cov_sources_per_pass(int K) { return std::min(K, kWideKc64); }
+static bool wide_channels(int M) { return M > kNarrowMax && M <= kWideMax; }
+static_assert(traits(CovKind::Wide).sources(kWideMax) == kWideKc64, "kernel_choice.h");
 
 hipError_t launch_cov_wide(hipStream_t s, const float2* X, const float* R, void* Wt, float* wscale, int model, int raw, double* Vpart,
                            int T, int F, int M, int K, const CovGeom& g) {
@@ -490,8 +489,6 @@ hipError_t launch_cov_wide(hipStream_t s, const float2* X, const float* R, void*
     if (kc == 2) return launch_dominant(wide_cov64_kernel<2>, grid, dim3(kBlock), 0, s, X, (const double*)wt, Vpart, T, F, M, K, K, g.tc);
     return hipErrorInvalidValue;
 }
-
-int wide_pow_sources_per_pass(int K) { return K >= 3 ? 4 : K; }
 
 hipError_t launch_power_wide(hipStream_t s, const float2* X, const float2* What, float* Ppart, int T, int F, int M, int K, const PowGeom& g) {
     if (!wide_channels(M)) return hipErrorInvalidValue;

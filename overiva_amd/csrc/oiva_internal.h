@@ -5,28 +5,15 @@
 
 #include <string>
 
+#include "kernel_choice.h"
 #include "overiva_hip.h"
 
 namespace oiva {
-
-// channel counts of the kernels tuned per shape (1..kNarrowMax: register arrays sized by it) and of the generic wide path
-// (kNarrowMax + 1 .. kWideMax = OIVA_MAX_CHANNELS, kernels_wide.hip), chosen by the channel count alone
-constexpr int kNarrowMax = 16;
-constexpr int kWideMax = OIVA_MAX_CHANNELS;
 
 // records the thread-local message oiva_last_error() returns and hands back `code` (host_util.hip)
 int fail_with(int code, const std::string& msg);
 // exchange.hip: rank / world / slot size and every rank's gather buffer as mapped in this process; -1 unless connected
 int xchg_peers(oiva_xchg* x, char** peers, int* rank, int* world, size_t* slot_bytes);
-
-// ---- lane geometry shared by the streaming kernels -------------------------------------------
-// A wave is 16 bins x 4 frame phases: lane l -> bin (l & 15), phase (l >> 4).  The 16 bins of one
-// frame are 16*M*8 contiguous bytes of the native (T, F, M) complex64 tensor, so one wave touches
-// four contiguous runs per step and every byte of every cache line it opens is consumed.
-constexpr int kBinsPerWave = 16;
-constexpr int kPhasesPerWave = 4;
-constexpr int kBlock = 256;  // 4 waves
-constexpr int kWaves = kBlock / 64;
 
 // packed Hermitian layout of one M x M covariance: M real diagonals, then for every c < d
 // (row-major) the pair (re, im) of V[c][d] = sum w * x_c * conj(x_d).  M*M floats in total.
@@ -67,45 +54,7 @@ hipError_t launch_dominant(Kern kernel, dim3 grid, dim3 block, size_t shmem, hip
     return hipGetLastError();
 }
 
-struct CovGeom {
-    int nsplit;   // frame splits (grid.y)
-    int tc;       // frames per split (multiple of 16)
-    int kc;       // sources per pass (template KC)
-    int nbg;      // bin groups of 16 (grid.x)
-    int hmfma = 0;  // with half16, 9..16 sources: the sources on the fp32 matrix cores (kernels_cov_hmfma.hip)
-    int half16 = 0; // 10/12/14/16 channels (9..15 odd: padded copy): kernels_cov_half16.hip (2 bins per workgroup; float32: 5..16 sources, all per pass; float64: 3..16 sources, 4 or 8 per pass)
-    int pair32 = 0; // 8 channels, >= 3 sources, float32: kernels_cov_pair32.hip (32 bins per workgroup, four sources per pass)
-    int pad = 0;  // odd channel count on the vector-ALU kernels: they read the copy of X padded to M + 1 channels
-    int quad = 0; // 10/12/14/16 channels, few sources, float32: the vector-ALU kernel of kernels_cov_quad.hip (float64 partials)
-    int part32 = 0; // hmfma, float32 arithmetic: the partial blocks leave as float32 (each the float64 sum of its chains, rounded once)
-};
-// Which frame chunk the y-th dispatched row of power_kernel's grid takes when the pass runs against the covariance pass
-// (DESIGN §3).  The covariance pass walks `cs` splits of `ctc` frames ascending and side by side, so the X it read last -- what
-// the Infinity Cache still holds -- is the TAIL of every split.  The n chunks of tcp frames are therefore handed out tail
-// first: chunk c belongs to the split that holds its last frame (split s owns chunks [first[s], first[s + 1]), first[s] = the
-// chunk that holds frame s * ctc), row 0 of the order is the last chunk of every split, row 1 the one before it, and so on
-// down to the heads, which the next covariance pass reads first.  A bijection of [0, n) for any n, tcp, cs, ctc >= 1 (a split
-// may own no chunk at all).  The table is made on the host and travels by value in the kernel's arguments (the divisions of the
-// closed form cost every workgroup 1-2 us in front of its first load: measured); uniform scalar work in the kernel.
-constexpr int kPowOrderMaxSplits = 64;
-struct PowOrder {
-    int cs = 0;                              // covariance splits (0: no order, chunk = row)
-    int q = 0;                               // chunks EVERY split owns: the rows of the order that hold all cs splits
-    int first[kPowOrderMaxSplits + 1] = {};  // first chunk of split s; first[cs] = n
-};
-inline PowOrder make_pow_order(int n, int tcp, int cs, int ctc) {
-    PowOrder o;
-    if (cs < 1 || cs > kPowOrderMaxSplits || ctc < 1 || tcp < 1 || n < 1) return o;      // (more splits than the table holds: chunk = row)
-    o.cs = cs;
-    for (int s = 0; s < cs; ++s) {
-        const long long c = (long long)s * ctc / tcp;
-        o.first[s] = c < n ? (int)c : n;
-    }
-    o.first[cs] = n;
-    o.q = n;
-    for (int s = 0; s < cs; ++s) o.q = o.first[s + 1] - o.first[s] < o.q ? o.first[s + 1] - o.first[s] : o.q;
-    return o;
-}
+// the chunk that row y of power_kernel's grid takes (PowOrder and make_pow_order: kernel_choice.h)
 __host__ __device__ inline int power_chunk_tail_first(int y, int n, const PowOrder& o) {
     if (y < o.q * o.cs) return o.first[y % o.cs + 1] - 1 - y / o.cs;
     y -= o.q * o.cs;
@@ -114,19 +63,6 @@ __host__ __device__ inline int power_chunk_tail_first(int y, int n, const PowOrd
             if (o.first[s + 1] - o.first[s] > r && y-- == 0) return o.first[s + 1] - 1 - r;
     return n - 1;      // (not reached: the rows hold n chunks in all)
 }
-struct PowGeom {
-    int nb;       // bin batches of 64 (grid.x)
-    int nsplit;   // frame splits (grid.y)
-    int tcp;      // frames per split (multiple of 4, <= kPowMaxFrames)
-    int kp;       // sources per pass
-    // the frame order of power_kernel: rev = every chunk from its last step to its first, ord = which chunk a row of the grid
-    // takes (both: against the covariance pass, kernels_demix.hip).  Filled in at launch time (stage_power).
-    int rev = 0;
-    PowOrder ord{};
-    int rounds = 1;   // rounds of resident workgroups the grid of power_kernel takes (choose_pow_geom)
-};
-constexpr int kPowMaxFrames = 512;
-
 
 // ---- launchers (one per kernel family; each .hip file owns its template instantiations) -------
 // Weighted covariance pass, overiva.py:179 (and :87 with unit weights).
@@ -147,8 +83,6 @@ hipError_t launch_cov_mfma(hipStream_t s, const float2* X, const float* R, float
 // vector-ALU kernel for 10, 12, 14, 16 channels and K <= 4 sources, float32 arithmetic (kernels_cov_quad.hip): the Hermitian
 // half split over four lanes per (bin, frame); tc multiple of 8; Vpart float64; R == nullptr: unit weights (K = 1);
 // Wt (T,16): scratch for the final weights, as for launch_cov_mfma
-bool cov_quad_supported(int M, int K);
-int cov_quad_sources_per_pass(int K);
 hipError_t launch_cov_quad(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                            double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g);
 // pre-pass of the 9..16-channel kernels: Wt (T, Kp) = 1 / max(r / gamma, eps), columns >= K zero; writes wscale (K)
@@ -156,39 +90,28 @@ hipError_t launch_cov_weights(hipStream_t s, const float* R, float* Wt, float* w
 // float64 vector-ALU kernel for 8 channels (kernels_cov_pair64.hip): the Hermitian half split over two lanes per (bin, frame),
 // 32 bins per workgroup (grid.x = ceil(F / 32)), tc multiple of 8, Vpart float64; Wt: the (T, 16) float scratch, used as
 // (T, 8) doubles; R == nullptr: unit weights (K = 1)
-bool cov_pair64_supported(int M);
-int cov_pair64_sources_per_pass(int K);
-int cov_pair64_bins_per_block();
 hipError_t launch_cov_pair64(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                              double* Vpart, int T, int F, int M, int K, const CovGeom& g);
 // float32 kernel for 8 channels and three or more sources, FOUR per pass over X (kernels_cov_pair32.hip): the Hermitian half
 // over two lanes per (bin, frame), 32 bins per workgroup, tc multiple of 8, Vpart float64; Wt: (T, 16) scratch as for
 // launch_cov_mfma; R == nullptr: unit weights (K = 1) on the same geometry
-bool cov_pair32_supported(int M, int K);
-int cov_pair32_sources_per_pass();
-int cov_pair32_bins_per_block();
 hipError_t launch_cov_pair32(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                              double* Vpart, int T, int F, int M, int K, const CovGeom& g);
 // float32 vector-ALU kernel for 10, 12, 14, 16 channels and up to 16 sources in ONE pass (kernels_cov_half16.hip): the
 // Hermitian half over 32 lanes per (bin, frame), 2 bins per workgroup (grid.x = ceil(F / 2)), tc multiple of 16, Vpart
 // float64; Wt: (T + 1, 16) scratch (row T is zeroed by the launcher); R == nullptr: unit weights (K = 1)
-bool cov_half16_supported(int M, int K);
-int cov_half16_sources_per_pass(int K);
 hipError_t launch_cov_half16(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                              double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g);
+// its weights pre-pass and that of the float64 form, shared with the matrix-core kinds (Hmfma, Hmfma64)
+hipError_t launch_cov_half16_weights(hipStream_t s, const float* R, float* Wt, float* wscale, int model, int raw, int T, int K);
+hipError_t launch_cov_half16_weights_f64(hipStream_t s, const float* R, float* Wt, float* wscale, int model, int raw, int T, int K);
 // the same decomposition with float64 sums (the `precise` arithmetic), 3..16 sources, 4 or 8 per pass; Wt: (T + 1, 16) DOUBLES
 // 9..16 sources: the sources as rows of the fp32 matrix-core instruction, Hermitian products on the vector ALU (kernels_cov_hmfma.hip)
-bool cov_hmfma_supported(int M, int K);
 hipError_t launch_cov_hmfma(hipStream_t s, const float2* X, const float* Wt, double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g);
-bool cov_hmfma64_supported(int M, int K);
 hipError_t launch_cov_hmfma64(hipStream_t s, const float2* X, const double* Wt, double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g);
-bool cov_half16_f64_supported(int M, int K);
-int cov_half16_f64_sources_per_pass(int K);
 hipError_t launch_cov_half16_f64(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                                  double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g);
-int cov_sources_per_pass(int M, int K, bool f64, bool short_axis = false);
 hipError_t cov_blocks_per_cu(int M, int kc, bool f64, int* n);
-bool cov_supported(int M);
 
 // Demix + source power, overiva.py:140 + the norms at :153/:155.
 //   What (F,M,M) c64 row-major;  Ppart [nb][T][K]
@@ -197,7 +120,7 @@ hipError_t launch_power(hipStream_t s, const float2* X, const float2* Xpad, cons
                         int K, const PowGeom& g);
 // matrix-core variant for 9..16 channels (same Ppart layout, one pass over X for all sources)
 hipError_t launch_power_mfma(hipStream_t s, const float2* X, const float2* What, float* Ppart, int T, int F, int M, int Mp, int K);
-int pow_sources_per_pass(int M, int K);
+hipError_t launch_power_lds(hipStream_t s, const float2* X, const float2* What, float* Ppart, int T, int F, int M, int K);
 hipError_t pow_blocks_per_cu(int M, int kp, int tcp, int* n);
 
 // Source activation, overiva.py:152-155: parts [nparts][T][K] -> R (T,K) = 2 sqrt(p) | p / F_total.
@@ -369,9 +292,6 @@ hipError_t launch_pca_subspace(hipStream_t s, const double* Cx, float2* What, do
 
 // The wide path, 17..32 channels (kernels_wide.hip): the launchers above hand over to these for M > kNarrowMax.  Same buffer
 // layouts as the narrow kernels (Vpart always float64).
-bool wide_channels(int M);
-int wide_cov_sources_per_pass(int K);
-int wide_pow_sources_per_pass(int K);
 //   covariance: float64 sums of exact float64 products whatever the arithmetic mode; Wt: (T, K) doubles of scratch
 hipError_t launch_cov_wide(hipStream_t s, const float2* X, const float* R, void* Wt, float* wscale, int model, int raw, double* Vpart,
                            int T, int F, int M, int K, const CovGeom& g);

@@ -66,11 +66,9 @@ struct oiva_plan {
     int prec = 0;                 // OIVA_PREC_* bits (oiva_plan_set_precision)
     bool upd_f64() const { return prec & OIVA_PREC_UPDATE_F64; }
     bool cov_f64() const { return prec & OIVA_PREC_COV_F64; }
-    // element type of the covariance partials: the vector-ALU kernels (<= 8 channels) always sum their float32 lane
-    // chains across lanes in float64 and store float64 partials; the 9..16-channel matrix-core kernel stores its
-    // accumulator type
-    bool vpart_f64() const { return vpart_f64_of(cov); }
-    bool vpart_f64_of(const CovGeom& g) const { return cov_f64() || M <= 8 || M > kNarrowMax || g.quad || (g.half16 && !g.part32); }
+    // element type of the covariance partials: the vector-ALU kernels always sum their float32 lane chains across lanes in
+    // float64 and store float64 partials; the 9..16-channel matrix-core kernel stores its accumulator type (CovTraits::partials)
+    bool vpart_f64() const { return partials_f64(cov, cov_f64()); }
     int use_graph = 0;
     // OGIVE (ive.py): per-bin state, allocated by oiva_plan_ogive_begin
     OgiveState og{};
@@ -129,163 +127,39 @@ struct oiva_plan {
 
 namespace {
 
-// Frame splits are chosen so that the grid is a whole number of "rounds" of what the chip holds at
-// once (CUs x resident workgroups per CU): a grid of 1.5 rounds runs as long as one of 2.
-int pick_splits(int capacity, int blocks_per_split, int T, int min_frames) {
-    int ns = std::max(1, capacity / std::max(1, blocks_per_split));
-    ns = std::min(ns, std::max(1, T / std::max(1, min_frames)));   // every split keeps >= min_frames frames
-    return ns;
+// what the choice of the two streaming passes depends on (kernel_choice.h).  $OIVA_HMFMA_PART32 is read at every choice,
+// $OIVA_COV_KC_WIDE and $OIVA_POWER_LDS once per process.
+ChoiceIn choice_in(const oiva_plan* p) {
+    static const bool kc_wide = [] { const char* v = std::getenv("OIVA_COV_KC_WIDE"); return !(v && v[0] == '0'); }();
+    static const bool power_lds = [] { const char* v = std::getenv("OIVA_POWER_LDS"); return !(v && v[0] == '0'); }();
+    const char* pv = std::getenv("OIVA_HMFMA_PART32");
+    ChoiceIn c{};
+    c.T = p->T, c.F = p->F, c.F_total = p->F_total, c.M = p->M, c.K = p->K, c.n_cu = p->n_cu;
+    c.cov_f64 = p->cov_f64(), c.upd_f64 = p->upd_f64();
+    c.cov_quad_on = p->cov_quad_on, c.cov_hmfma_on = p->cov_hmfma_on;
+    c.part32 = pv && pv[0] == '1';
+    c.kc_wide = kc_wide, c.power_lds = power_lds;
+    return c;
 }
-
-// Kernels with four frame phases per workgroup, float64 per-bin algebra behind them (`mixed`): 8 frame splits on a long
-// frame axis, 4 on a short one (their float32 chains are then T / 32 resp. T / 16 frames); on a short axis never more than
-// one round of workgroups (a workgroup's fixed costs dominate there) or splits of fewer than 16 frames.
-int mixed_min_splits(int capacity, int blocks_per_split, int T) {
-    if (T >= 1024) return 8;       // (a second round of workgroups costs little there: +18 us of 270 at 2048 x 4000 x 16 / 2)
-    const int one_round = std::max(1, capacity / std::max(1, blocks_per_split));
-    return std::max(1, std::min(std::min(4, one_round), T / 16));
+// the device's answers (< 1: the query failed); asked[0] / asked[1] (may be nullptr) receive what each query returned
+Occupancy device_occupancy(int* asked = nullptr) {
+    Occupancy o;
+    o.cov_blocks_per_cu = [asked](int M, int kc, bool f64) {
+        int n = 0;
+        if (cov_blocks_per_cu(M, kc, f64, &n) != hipSuccess) n = 0;
+        if (asked) asked[0] = n;
+        return n;
+    };
+    o.pow_blocks_per_cu = [asked](int M, int kp, int tcp) {
+        int n = 0;
+        if (pow_blocks_per_cu(M, kp, tcp, &n) != hipSuccess) n = 0;
+        if (asked) asked[1] = n;
+        return n;
+    };
+    return o;
 }
-
-void choose_cov_geom(oiva_plan* p, int nsplit_req) {
-    CovGeom g;
-    if (p->M > kNarrowMax) {
-        // 17..32 channels (kernels_wide.hip): one workgroup per (bin, split, pass of sources), float64 sums in every mode;
-        // splits only to fill the chip with two workgroups per CU
-        g.kc = wide_cov_sources_per_pass(p->K);
-        g.nbg = p->F;
-        int nsplit = nsplit_req;
-        if (nsplit <= 0) {
-            // (counted on F_total, not on this plan's bins: every rank of a bin-sharded run then groups the frames of a bin
-            //  into the same splits as one plan over all bins does, and its float64 partials add up to the same bits)
-            const int groups = p->F_total * ceil_div(p->K, g.kc);
-            nsplit = 1;
-            while (groups * nsplit < 2 * p->n_cu && ceil_div(p->T, nsplit + 1) >= 128) ++nsplit;
-        }
-        g.tc = round_up(ceil_div(p->T, nsplit), 4);
-        g.nsplit = ceil_div(p->T, g.tc);
-        p->cov = g;
-        return;
-    }
-    // float64, 8 channels: two lanes per (bin, frame), 32 bins per workgroup (kernels_cov_pair64.hip); else 16 bins
-    // (same geometry, float32: 8 channels with three or more sources, four per pass -- kernels_cov_pair32.hip)
-    g.pair32 = !p->cov_f64() && cov_pair32_supported(p->M, p->K);
-    const bool pair = g.pair32 || (p->cov_f64() && cov_pair64_supported(p->M));
-    g.nbg = ceil_div(p->F, pair ? cov_pair64_bins_per_block() : kBinsPerWave);
-    g.kc = cov_sources_per_pass(p->M, p->K, p->cov_f64(), p->T < 1024);
-    const int nz = ceil_div(p->K, g.kc);
-    int nsplit = nsplit_req;
-    // few sources: the Hermitian half on the vector ALU, four lanes per (bin, frame).  One or two sources are one pass
-    // over X and faster than the matrix-core kernel in any mode; three or four are two passes, slower than its float32
-    // form (measured 486-517 against 459 us at 2048 x 4000 x 16) but with float64 partial sums of short float32 chains,
-    // which is what the float64 per-bin algebra of the `mixed` mode needs -- and 1.8 times faster than the float64
-    // matrix-core pass that mode would otherwise have to be replaced by
-    // (9, 11, 13, 15 channels: the same kernels on the copy of X padded by one zero channel, plan_covariance)
-    const int Mc = p->M + (p->M > 8 && p->M % 2 && p->X_pad != nullptr ? 1 : 0);
-    g.pad = Mc != p->M;
-    if (p->M > 8 && !p->cov_f64() && p->cov_quad_on && cov_quad_supported(Mc, p->K) && (p->K <= 2 || p->upd_f64())) {
-        // one round of two workgroups per CU
-        g.quad = 1;
-        g.kc = cov_quad_sources_per_pass(p->K);
-        if (nsplit <= 0) {
-            const int blocks = g.nbg * ceil_div(p->K, g.kc);
-            nsplit = std::min(32, pick_splits(p->n_cu * 2, blocks, p->T, p->T >= 1024 ? 128 : 64));
-            // only 4 frame phases per workgroup: a lane's float32 chain is T / (4 nsplit) frames, four times that of the
-            // 8-channel kernel at equal splits, and the error of the result grows linearly with it (measured against
-            // the reference's own complex64 floor, 16 channels / 2 sources x 20 iterations: T = 4000: 4 splits 0.8-1.0
-            // floors, 8 splits 0.5-0.6, 16 splits 0.3; T = 163: 1 split 1.4, 4 splits 0.8, 8 splits 0.6).  With the
-            // float64 per-bin algebra (`mixed`, the default arithmetic of these shapes) the chains are what is left of
-            // the error, so that mode takes 8 splits (+18 us on the pass, +8 us in the update at 2048 x 4000 x 16 / 2).
-            // ... as long as that is still one round of workgroups (few frames: 4 splits = chains of T / 16, 0.8 floors)
-            if (p->upd_f64()) nsplit = std::max(nsplit, mixed_min_splits(p->n_cu * 2, blocks, p->T));
-        }
-        g.tc = round_up(ceil_div(p->T, nsplit), 8);
-        g.nsplit = ceil_div(p->T, g.tc);
-        p->cov = g;
-        return;
-    }
-    // many sources (5..16): the Hermitian half over 32 lanes per (bin, frame), every source in one pass; a wave's float32
-    // chain is T / (4 nsplit) frames: <= 256 in `fast`, <= 128 with the float64 per-bin algebra behind it
-    // (float64 sums, `precise`, 3..16 sources: the same lanes with four or eight sources per pass; splits only to fill the chip)
-    if (p->M > 8 && p->cov_quad_on &&
-        (p->cov_f64() ? cov_half16_f64_supported(Mc, p->K) : p->K > 4 && cov_half16_supported(Mc, p->K))) {
-        g.half16 = 1;
-        g.hmfma = (p->cov_hmfma_on && (p->cov_f64() ? cov_hmfma64_supported(Mc, p->K) : cov_hmfma_supported(Mc, p->K))) ? 1 : 0;
-        g.nbg = ceil_div(p->F, 2);
-        g.kc = p->cov_f64() ? cov_half16_f64_sources_per_pass(p->K) : cov_half16_sources_per_pass(p->K);
-        if (nsplit <= 0) {
-            // (float64: no chain to bound; the four-source form runs a little faster in two rounds of workgroups -- 2048 x 4000
-            //  x 16 / 4: 1 split 744 us, 2 splits 691, 4 splits 693; the eight-source form does not care)
-            // (the matrix-core kernel: one bin per workgroup and eight float32 chains -- half the splits for the same chain)
-            const int chains = g.hmfma ? 8 : 4;
-            nsplit = p->cov_f64() ? (!g.hmfma && g.kc == 4 && p->T >= 1024 ? 2 : 1) : ceil_div(p->T, chains * (p->upd_f64() ? 128 : 256));
-            const int per_cu = g.hmfma ? (p->cov_f64() ? 2 : 3) : p->cov_f64() && g.kc == 4 ? 4 : 2;      // workgroups a CU holds (registers / launch bounds)
-            const int groups = g.hmfma ? p->F : g.nbg * ceil_div(p->K, g.kc);
-            while (groups * nsplit < per_cu * p->n_cu && ceil_div(p->T, nsplit + 1) >= 64) ++nsplit;
-        }
-        g.tc = round_up(ceil_div(p->T, nsplit), g.hmfma ? 32 : 16);
-        g.nsplit = ceil_div(p->T, g.tc);
-        // (round 6, opt-in: $OIVA_HMFMA_PART32=1, read whenever the geometry is chosen) the float32 matrix-core kernel hands its
-        // partial blocks over as float32 -- half the bytes the per-bin update is bound by at 16 x 16 (update 66 -> 50 us, iteration
-        // 931 -> 903 us) for one more rounding per block: W moves by 1e-8 on i.i.d. input and by 3e-6 .. 1e-5 (0.3-0.5 reference
-        // floors) on a 16-source mixture at full size, and the fixtures of <= 1024 frames land up to twice as far from the
-        // complex128 result (tools/r6/part32_ab.py, tools/r6/NOTES.md).  Not the default: parity first.
-        if (g.hmfma && !p->cov_f64()) {
-            const char* pv = std::getenv("OIVA_HMFMA_PART32");
-            g.part32 = pv && pv[0] == '1';
-        }
-        p->cov = g;
-        return;
-    }
-    if (p->M > 8) {
-        // planar matrix-core path: one wave per (bin, split); splits bound the length of the fp32
-        // accumulation chain (<= 512 frames) and keep >= 2 waves per SIMD when there are few bins
-        if (nsplit <= 0) {
-            nsplit = ceil_div(p->T, 512);
-            const int waves = p->F * ceil_div(p->K, 4);
-            while (waves * nsplit < 2 * 4 * p->n_cu && ceil_div(p->T, nsplit + 1) >= 64) ++nsplit;
-        }
-        g.tc = round_up(ceil_div(p->T, nsplit), 4);
-        g.nsplit = ceil_div(p->T, g.tc);
-        p->cov = g;
-        return;
-    }
-    const int quantum = pair ? 8 : 16;      // frames per step of a workgroup
-    if (nsplit <= 0) {
-        int bpc = 2;
-        if (cov_blocks_per_cu(p->M, g.kc, p->cov_f64(), &bpc) != hipSuccess || bpc < 1) bpc = 2;
-        // one round: the grid is what the chip holds at once (CUs x resident workgroups); every workgroup pays a
-        // fixed cost (gamma prologue, ring fill, epilogue), so fewer, longer workgroups win as long as the chip
-        // is full, and 1.5 rounds run as long as 2
-        // (on a short frame axis at least 64 frames per split instead of 128: at the reference's 160-235 frames the floor of
-        //  128 left the chip to one split -- 2049 x 235 x 8 / 2: 1 split 18.9 / 29.2 us (float32 / float64), 3 splits 14.7 /
-        //  16.8.  On a long axis the floor of 128 stays: a 256-bin shard of 4000 frames takes 28 splits in 20.4 us, 32 splits
-        //  -- exactly the chip's 512 workgroup slots, which the dispatcher does not fill evenly -- 26.3)
-        nsplit = pick_splits(p->n_cu * bpc, g.nbg * nz, p->T, p->T >= 1024 ? 128 : 64);
-        // a grid that fills the chip's workgroup slots EXACTLY runs slower than one an eighth short of it (the dispatcher does
-        // not fill the CUs evenly): 512 bins x 4000 frames, 16 splits = 512 workgroups 31.4 us, 14 splits 29.5 us; 256 bins: 32
-        // splits 26.3 us, 28 splits 20.4 us
-        if (nsplit >= 12 && g.nbg * nz * nsplit >= p->n_cu * bpc) nsplit = nsplit * 7 / 8;
-        // the update kernel adds the nsplit partials of every matrix element in one round of loads per 16 splits
-        // (sum_vpart); more than 32 splits cost more there than the fuller grid saves here (measured on a
-        // 256-bin shard: 16 splits 25.2 + 8.0 us, 28 splits 21.4 + 9.2 us, 42 splits 25.5 + 10.3 us)
-        // ... unless 32 splits would leave most of the chip idle (few bins, very long frame axis): then the
-        // streaming pass dominates and up to 64 splits are allowed
-        const int cap = (g.nbg * nz * 32 >= p->n_cu) ? 32 : 64;
-        nsplit = std::min(nsplit, cap);
-        // four frame phases per workgroup instead of 16: float32 chains four times as long at equal splits; with the
-        // float64 per-bin algebra behind it the pass takes at least 8 splits (see the 10..16-channel kernel above)
-        // (round 5: on a short frame axis the bound is the chain itself -- T / (4 nsplit) <= 64 frames, what 4 splits give just below
-        //  1024 frames -- not 4 splits whatever T: at the reference's 2049 bins x 235 frames the forced fourth split cost 8 / 4
-        //  sources 26.8 against 21.2 us on the pass (iteration 74.4 -> 69.2 us), 8 / 3 23.0 against 19.2 (63.5 -> 59.4))
-        if (g.pair32 && p->upd_f64()) {
-            const int by_chain = p->T >= 1024 ? 8 : std::min(4, ceil_div(p->T, 256));
-            nsplit = std::max(nsplit, std::min(by_chain, mixed_min_splits(p->n_cu * bpc, g.nbg * nz, p->T)));
-        }
-    }
-    g.tc = round_up(ceil_div(p->T, nsplit), quantum);
-    g.nsplit = ceil_div(p->T, g.tc);
-    p->cov = g;
-}
+void choose_cov_geom(oiva_plan* p, int nsplit_req) { p->cov = choose_cov(choice_in(p), device_occupancy(), nsplit_req); }
+void choose_pow_geom(oiva_plan* p, int nsplit_req) { p->pw = choose_pow(choice_in(p), device_occupancy(), nsplit_req); }
 
 void choose_stats_geom(oiva_plan* p) {
     CovGeom g;
@@ -300,51 +174,6 @@ void choose_stats_geom(oiva_plan* p) {
         return;
     }
     p->stg = stats_geom(p->T, p->F, p->K, p->n_cu);
-}
-
-void choose_pow_geom(oiva_plan* p, int nsplit_req) {
-    PowGeom g;
-    g.nb = ceil_div(p->F, kBinsPerWave * kWaves);
-    if (p->M > kNarrowMax) {
-        // 17..32 channels (kernels_wide.hip): one lane per bin of a 64-bin batch; about four workgroups per CU
-        g.kp = wide_pow_sources_per_pass(p->K);
-        const int groups = g.nb * ceil_div(p->K, g.kp);
-        const int nsplit = nsplit_req > 0 ? nsplit_req : pick_splits(p->n_cu * 4, groups, p->T, 16);
-        g.tcp = round_up(ceil_div(p->T, nsplit), 4);
-        g.nsplit = ceil_div(p->T, g.tcp);
-        p->pw = g;
-        return;
-    }
-    g.kp = pow_sources_per_pass(p->M, p->K);
-    int nsplit = nsplit_req;
-    if (nsplit <= 0) {
-        // Workgroups so that about 48 KB of X are in flight per CU: a wave keeps two steps (2 x 4 frames x 16 bins x 8M
-        // bytes) in flight, i.e. 12 / M workgroups per CU -- 1.5 at 8 channels, 3 at 4, 0.75 at 16.  Measured at 2048 bins
-        // x 4000 frames on the kernel itself and on the pure-read form of its geometry (tools/membench.hip, pattern P):
-        // 8 channels 12 splits (384 workgroups) 88-90 us, 16: 91, 24: 92, 8: 106 (four steps in flight and 24 splits, as in
-        // round 1: 94-96 us); 4 channels 24 splits 40.7 us, 12: 46; 2 channels 24 splits 21.8, 12: 35; 16 channels / 2
-        // sources 6 splits 172 us, 12: 234.  More resident waves thrash the 32 KB L1, fewer expose HBM latency.  Each
-        // workgroup loads its W first (256-bin shard: 62 splits 13.5 us, 167 splits 15.9 us).
-        // (counted per source pass: with 8 sources in two passes, 12 splits 112 us, 6 splits 127-137 us)
-        // ONE source per pass halves the arithmetic per byte and a wave runs through its two steps in flight before the next
-        // ones arrive: twice the workgroups (8 channels / 1 source: 12 splits 111 us, 24 splits 92.5; with 2-4 sources 24
-        // splits measure the same as 12)
-        // (not beyond 8 channels: 16 channels / 1 source 6 splits 226 us, 12 splits -- 1.5 rounds of workgroups -- 276)
-        const int per_cu_x12 = (g.kp == 1 && p->M <= 8) ? 24 : 12;
-        // (at least 32 frames per workgroup: with 64, 2049 x 235 x 8 / 2 ran 3 splits in 16.0 us where 6-8 take 11.9-12.1,
-        //  2049 x 160 x 4 / 2 2 splits in 12.0 us where 5-8 take 8.2-8.4)
-        nsplit = pick_splits(std::max(p->n_cu / 2, p->n_cu * per_cu_x12 / std::max(p->M, 1)), g.nb, p->T, 32);
-    }
-    int tcp = round_up(ceil_div(p->T, nsplit), 4);
-    tcp = std::min(std::max(tcp, 4), kPowMaxFrames);
-    g.tcp = tcp;
-    g.nsplit = ceil_div(p->T, tcp);
-    // rounds of workgroups the grid runs in (a long frame axis: tcp is capped, so the chunks outnumber the chip's slots)
-    int bpc = 0;
-    if (p->M <= 8 || p->K <= 4)
-        if (pow_blocks_per_cu(p->M, g.kp, g.tcp, &bpc) == hipSuccess && bpc > 0)
-            g.rounds = (int)ceil_div((long long)g.nb * g.nsplit * ceil_div(p->K, g.kp), (long long)bpc * p->n_cu);
-    p->pw = g;
 }
 
 int drop_graph(oiva_plan* p) {
@@ -426,7 +255,7 @@ int stage_update(oiva_plan* p, bool init_only) {
 // covariance and per-bin update as one launch (kernels_cov_update.hip) where the plan's geometry is the kernel's: the headline
 // shape and its neighbours (8 channels, 2 sources, four frame splits)
 bool cov_update_applies(const oiva_plan* p) {
-    return p->M <= kNarrowMax && p->fuse_cov_update && !p->cov_f64() && !p->cov.pair32 && !p->raw_weights && !(p->prec & OIVA_PREC_UPDATE_ROWS) && p->K < p->M &&
+    return traits(p->cov.kind).fusable && p->fuse_cov_update && !p->cov_f64() && !p->raw_weights && !(p->prec & OIVA_PREC_UPDATE_ROWS) && p->K < p->M &&
            cov_update_supported(p->M, p->K, p->T, p->F, p->cov.nsplit, p->cov.tc);
 }
 int stage_cov_update(oiva_plan* p) {
@@ -697,7 +526,6 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
     OIVA_NEED(K >= 1 && K <= M, OIVA_ERR_ARG, "n_src must be in 1..n_chan");
     OIVA_NEED(model == OIVA_MODEL_LAPLACE || model == OIVA_MODEL_GAUSS, OIVA_ERR_ARG, "unknown model");
     OIVA_NEED(F_total >= F, OIVA_ERR_ARG, "F_total must be >= F");
-    OIVA_NEED(cov_supported(M), OIVA_ERR_ARG, "unsupported number of channels");
     int ndev = 0;
     OIVA_TRY_HIP(hipGetDeviceCount(&ndev));
     OIVA_NEED(device >= 0 && device < ndev, OIVA_ERR_ARG, "no such device");
@@ -830,12 +658,14 @@ int oiva_plan_covariance(oiva_plan* p) {
     p->pad_valid = false;
     int rcp = ensure_pad(p);
     if (rcp) return rcp;
+    // unit weights, one "source", on the plan's splits by the kind its traits name for that (never a matrix-core kind of many
+    // sources): partials land in Vpart laid out as [nsplit][F][1][M*M]
     CovGeom g = p->cov;
+    g.kind = traits(p->cov.kind).unit;
     g.kc = 1;
-    g.part32 = 0;          // (one "source": never the matrix-core kernel)
-    // unit weights, one "source": partials land in Vpart laid out as [nsplit][F][1][M*M]
+    g.part32 = 0;
     OIVA_TRY_HIP(launch_cov(p->stream, p->X, p->X_pad, nullptr, nullptr, nullptr, p->model, 0, p->Vpart, p->cov_f64(), p->T, p->F, p->M, 1, g));
-    OIVA_TRY_HIP(launch_sum_parts(p->stream, p->Vpart, p->vpart_f64_of(g), g.nsplit, p->Cx, (long long)p->F * p->M * p->M, 1. / (double)p->T));
+    OIVA_TRY_HIP(launch_sum_parts(p->stream, p->Vpart, partials_f64(g, p->cov_f64()), g.nsplit, p->Cx, (long long)p->F * p->M * p->M, 1. / (double)p->T));
     p->have_cx = true;
     return OIVA_OK;
 }
@@ -1323,7 +1153,7 @@ int oiva_plan_iterate_timed(oiva_plan* p, int n, float* total_ms, float* per_ker
             // (where the stage is two launches -- a weights pre-pass in front of the kernel: 9..16 channels, the float64 kernel
             //  of 8 channels, 8 channels with three or more sources -- it keeps its bracketed time, so that the stages still add
             //  up to the total)
-            const bool one_launch = p->M <= 8 && !p->cov.pair32 && !(p->cov_f64() && cov_pair64_supported(p->M));
+            const bool one_launch = traits(p->cov.kind).launches == 1;
             if (s == 2 && one_launch && kev[2 * it] && kev[2 * it + 1] && hipEventElapsedTime(&kms, kev[2 * it], kev[2 * it + 1]) == hipSuccess &&
                 kms > 0.f && kms <= ms)
                 ms = kms;
@@ -1355,7 +1185,7 @@ int oiva_plan_set_cov_quad(oiva_plan* p, int enable, int* active) {
     return change_geometry(p, [&] {
         p->cov_quad_on = enable != 0;
         choose_cov_geom(p, 0);
-        if (active) *active = p->cov.quad || p->cov.half16;
+        if (active) *active = traits(p->cov.kind).quad_switch;
         return OIVA_OK;
     });
 }
@@ -1407,7 +1237,7 @@ int oiva_plan_set_precision(oiva_plan* p, int flags) {
         }
         // (more than 8 channels: which float32 kernel takes the pass also depends on the arithmetic of the per-bin algebra;
         // 8 channels with three or more sources: the number of frame splits does)
-        const bool cov_changed = ((flags ^ p->prec) & (OIVA_PREC_COV_F64 | ((p->M > 8 || p->cov.pair32) ? OIVA_PREC_UPDATE_F64 : 0))) != 0;
+        const bool cov_changed = ((flags ^ p->prec) & (OIVA_PREC_COV_F64 | (traits(p->cov.kind).update_arith ? OIVA_PREC_UPDATE_F64 : 0))) != 0;
         p->prec = flags;
         if (cov_changed) choose_cov_geom(p, 0);            // sources per pass and residency depend on the accumulator type
         return (int)OIVA_OK;
@@ -1812,6 +1642,26 @@ int oiva_test_power_order(int nsplit, int tcp, int cov_splits, int cov_tc, int* 
     OIVA_NEED(cov_splits <= kPowOrderMaxSplits, OIVA_ERR_ARG, "more covariance splits than the order table holds");
     const PowOrder o = make_pow_order(nsplit, tcp, cov_splits, cov_tc);
     for (int y = 0; y < nsplit; ++y) order[y] = power_chunk_tail_first(y, nsplit, o);
+    return OIVA_OK;
+}
+
+int oiva_test_kernel_choice(int device, int T, int F, int F_total, int M, int K, int prec_flags, int quad_on, int hmfma_on,
+                            int cov_splits_req, int pow_splits_req, int* out) {
+    OIVA_NEED(out && T >= 1 && F >= 1 && F_total >= F && M >= 1 && M <= OIVA_MAX_CHANNELS && K >= 1 && K <= M, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(cov_splits_req >= 0 && pow_splits_req >= 0, OIVA_ERR_ARG, "bad split count");
+    DeviceGuard guard(device);
+    oiva_plan p;      // (a plan's fields, nothing allocated: what choice_in reads)
+    p.device = device, p.T = T, p.F = F, p.F_total = F_total, p.M = M, p.K = K, p.prec = prec_flags;
+    p.cov_quad_on = quad_on != 0, p.cov_hmfma_on = hmfma_on != 0;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) p.n_cu = prop.multiProcessorCount;
+    int asked[2] = {-1, -1};
+    const ChoiceIn c = choice_in(&p);
+    const CovGeom g = choose_cov(c, device_occupancy(asked), cov_splits_req);
+    const PowGeom w = choose_pow(c, device_occupancy(asked), pow_splits_req);
+    const int o[18] = {(int)g.kind, g.nsplit, g.tc, g.kc, g.nbg, g.pad, g.part32, partials_f64(g, c.cov_f64) ? 1 : 0, (int)traits(g.kind).unit,
+                       (int)w.kind, w.nb, w.nsplit, w.tcp, w.kp, w.rounds, asked[0], asked[1], p.n_cu};
+    std::copy(o, o + 18, out);
     return OIVA_OK;
 }
 

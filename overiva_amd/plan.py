@@ -359,3 +359,21 @@ class Plan(_lib.Handle):
         p = np.empty((self.T, self.K), np.float32)
         _lib.check(self.lib.oiva_test_run_power(self.h, _lib.ptr(p)))
         return p
+
+
+COV_KINDS = ("Lane", "Pair32", "Pair64", "Quad", "Half16", "Hmfma", "Half16F64", "Hmfma64", "Mfma", "Wide")
+POW_KINDS = ("Lane", "Mfma", "Lds", "Wide")
+KERNEL_CHOICE = ("cov_kind", "nsplit", "tc", "kc", "nbg", "pad", "part32", "vpart_f64", "unit_kind", "pow_kind", "nb", "pow_nsplit",
+                 "tcp", "kp", "rounds", "occ_cov", "occ_pow", "n_cu")
+
+
+def kernel_choice(T, F, M, K, mode="fast", F_total=None, cov_quad=True, cov_hmfma=True, cov_splits=0, pow_splits=0, device=0):
+    """the kernels and geometry a plan of this shape and these settings runs (csrc/kernel_choice.h; test hook, allocates
+    nothing): a dict of ``KERNEL_CHOICE`` with the three kinds by name.  ``mode`` as ``Plan.set_precision``."""
+    flags = _lib.PREC_BY_NAME[mode] if isinstance(mode, str) else int(mode)
+    out = (C.c_int * len(KERNEL_CHOICE))()
+    _lib.check(_lib.load().oiva_test_kernel_choice(int(device), int(T), int(F), int(F if F_total is None else F_total), int(M), int(K),
+                                                   flags, int(bool(cov_quad)), int(bool(cov_hmfma)), int(cov_splits), int(pow_splits), out))
+    d = dict(zip(KERNEL_CHOICE, out))
+    d["cov_kind"], d["unit_kind"], d["pow_kind"] = COV_KINDS[d["cov_kind"]], COV_KINDS[d["unit_kind"]], POW_KINDS[d["pow_kind"]]
+    return d

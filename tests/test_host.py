@@ -4,6 +4,7 @@ without the built library.  No compute calls (no GPU here)."""
 import ctypes
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -173,6 +174,28 @@ def test_device_arena_ownership_logic(tmp_path):
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
     assert run.stdout.strip() == "arena ok"
+
+
+def test_kernel_choice_replays_the_recorded_table(tmp_path):
+    """choose_cov / choose_pow (csrc/kernel_choice.h, host only) against every row of tests/golden/kernel_choice_256cu.json -- the
+    choices of the commit before the table existed, recorded on a 256-CU device with the occupancy figures each row was made with
+    -- in a stand-alone program: the same kinds, splits and geometry on every row, and the traits' invariants (the chosen kind's
+    predicate holds, tc is a multiple of its quantum and of the unit-weights kind's, the splits cover T)"""
+    import subprocess
+
+    from overiva_amd import build
+
+    exe = tmp_path / "kernel_choice_main"
+    host_flags = [f for f in build.FLAGS if not f.startswith("--offload-arch")]
+    r = subprocess.run([build._hipcc(), *host_flags, os.path.join(REPO, "tests", "helpers", "kernel_choice_main.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    run = subprocess.run([str(exe), os.path.join(REPO, "tests", "golden", "kernel_choice_256cu.json")], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout[-4000:] + run.stderr
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import kernel_choice_table
+
+    assert run.stdout.strip() == f"kernel choice ok: {len(kernel_choice_table.sweep())} rows"      # every row of the sweep
 
 
 def test_resident_kernels_use_no_scratch_memory(lib):
