@@ -10,8 +10,11 @@ namespace {
 // Source activation, reference overiva.py:152-155:
 //   R[t,k] = 2 sqrt(p) (laplace) | p / F_total (gauss), p = sum over parts in part order (bin batch, or rank then
 //   batch), associated in the canonical blocks described in the kernel: a sharded run with equal shards on 64-bin
-//   batches gets the same bits as the single-GPU run -- of r; of W too where the plans also split the frame axis of the covariance
-//   pass alike.  (16 channels with more than 4 sources: the 64-bin parts themselves come from power_lds_kernel where
+//   batches gets the same bits as the single-GPU run -- of r, for every power kernel family: each leaves for a 64-bin batch the
+//   same part wherever that batch sits in its launch (tests/test_power_parts_gpu.py; iterated over every covariance family:
+//   tests/test_sharded_gpu.py::test_every_kernel_family_gives_the_single_plans_bits_on_equal_shards); of W too where the plans
+//   also split the frame axis of the covariance pass alike, which the plans do not see to themselves.
+//   (16 channels with more than 4 sources: the 64-bin parts themselves come from power_lds_kernel where
 //   a plan has at least 64 bins and 16 frames -- ragged bin counts included: its last batch is masked -- and from power_mfma_kernel
 //   below that (PowKind::Lds / Mfma, kernel_choice.h), which add a part's 64 bins in different orders: a shard that falls on the
 //   other side of that line than the single-GPU plan agrees with one GPU to rounding only)

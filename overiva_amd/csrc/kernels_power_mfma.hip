@@ -194,10 +194,21 @@ __global__ __launch_bounds__(kBlock, 2) void power_lds_kernel(const float2* __re
     // pace; with the same order everywhere, the chip asks memory for 2 KB of every 8 KB at any one time and the stream stops at
     // 5.3 TB/s -- rotated, the workgroups in flight cover all four quarters: 6.3 TB/s for the stream alone
     // (tools/r6/dmabench.hip, rows F and M).
+    // The rotation follows the workgroup's FRAME row alone.  The sub-batches enter one float32 chain (P below) in the order
+    // they are taken, so that order is part of a part's bits -- and a part must not depend on where its batch sits in the
+    // launch: the same 64 bins are batch 2 of a plan over all bins and batch 0 of a bin shard, and both must leave the same bits
+    // (tests/test_power_parts_gpu.py, tests/test_sharded_gpu.py).  Every plan of a sharded run holds the same frames,
+    // so blockIdx.y is the same for a batch wherever it runs; blockIdx.x, which the rotation used to add, is not.  The
+    // workgroups in flight at any one time are whole rows of the grid (x runs fastest: 512 slots are 16 rows at 2048 bins), so
+    // the rows alone cover the four quarters as evenly; an XCD, which takes every eighth workgroup of a row, saw one rotation
+    // per row before as well (x + 8 i is x modulo 4).  Measured at 2048 x 4000 x 16 / 16, five calls of 20 launches, the two
+    // builds alternating on one device: rotation by x + y 217.0 / 216.7 us (median; the five calls 209-245), by y 216.7 / 215.9.
+    // (Tried first: one accumulator set per sub-batch, added in ascending order at the end -- free of the order altogether, but
+    // 64 more registers on a kernel that holds 236 of the 256 that two waves per SIMD allow: 116 bytes of scratch per lane.)
     // (a ragged last batch has fewer sub-batches: those that start past the last bin are left out, one that is cut is shifted below)
     const int nsb = min(4, (F - f0 + 15) >> 4);
     const int nsteps = nsb * kPlTiles;
-    const int rot = (int)((blockIdx.x + blockIdx.y) % (unsigned)nsb);
+    const int rot = (int)(blockIdx.y % (unsigned)nsb);
     auto sub_batch = [&](int sbi) {
         const int sb = sbi + rot;
         return sb < nsb ? sb : sb - nsb;

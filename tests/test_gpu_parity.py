@@ -606,6 +606,69 @@ def test_odd_shapes_against_oracle(oa, shape, model):
     assert eW < bound and eY < 2 * bound
 
 
+# (T, F, M, K), the covariance and the power kernel `mixed` runs on it (csrc/kernel_choice.h)
+MANY_SOURCES_64_BINS = [((256, 64, 16, 16), "Hmfma", "Lds"),      # one whole batch
+                        ((200, 130, 16, 16), "Hmfma", "Lds"),     # two batches + a ragged one of 2 bins
+                        ((160, 65, 16, 9), "Hmfma", "Lds"),       # background channels, one-bin ragged batch
+                        ((192, 128, 16, 5), "Half16", "Lds"),
+                        ((160, 79, 15, 15), "Hmfma", "Mfma"),     # padded copy of X, ragged batch
+                        ((144, 70, 12, 12), "Hmfma", "Mfma"),
+                        ((150, 66, 10, 6), "Half16", "Mfma")]
+
+
+@pytest.mark.parametrize("model", ["laplace", "gauss"])
+@pytest.mark.parametrize("shape,cov_kind,pow_kind", MANY_SOURCES_64_BINS, ids=["x".join(str(v) for v in c[0]) for c in MANY_SOURCES_64_BINS])
+def test_many_sources_from_64_bins_against_oracle(oa, shape, cov_kind, pow_kind, model):
+    """more than 8 channels and more than 4 sources at 64 bins and more, ITERATED: the chain matrix-core power pass (power_lds_kernel /
+    power_mfma_kernel over several 64-bin batches with a ragged last one) -> activation -> cov_hmfma / cov_half16 -> per-bin
+    update (update_det16r_kernel where determined) of BASELINE.json configs[4], five iterations against the oracle's
+    complex128 result (overiva.py:138-190).  Every part of that chain is held against the oracle alone elsewhere, at these
+    sizes; the hand-over between the parts at several batches only here.  Bounds from the reference's own arithmetic (oracle,
+    reference-faithful complex64 form against the complex128 one, 5 iterations): i.i.d. input floors 1.2e-7 .. 4.5e-7 -> the north
+    star's 1e-5 on W and Y; complex128 input (runs `precise`) 1e-6 on W as test_rows_kernel_against_the_oracle; mixture-like
+    input floors 1.8e-5 .. 4.9e-4 -> max(1e-5, 1.5 floors) on W with the floor computed here.  (192 x 128 x 16 / 5 gauss on the
+    mixture: the reference's complex64 floor is 1.3 -- chaotic, nothing to pin -- and that one leg is left out.)"""
+    from overiva_amd import plan
+
+    T, F, M, K = shape
+    kw = dict(n_src=K, n_iter=5, proj_back=False, model=model, return_filters=True)
+    fixture = f"T{T}F{F}M{M}K{K}"
+    X = orc.synth_iid(T, F, M, seed=sum(shape))
+    Yr, Wr = orc.overiva_staged(X, **kw)
+    # complex64 input: `mixed`, the kernels the row is named for
+    Y, W = oa.overiva(X, **kw)
+    info = oa.last_solver_info()
+    assert info["precision"] == "mixed" and not info["sharded"] and info["resident_launches"] == 0
+    choice = plan.kernel_choice(T, F, M, K, info["precision"])
+    assert (choice["cov_kind"], choice["pow_kind"]) == (cov_kind, pow_kind)
+    eW, eY = orc.rel_err(W, Wr), orc.rel_err(Y, Yr)
+    _log(test="many_sources_64", fixture=fixture + " iid", model=model, n_iter=5, input="c64", mode="mixed", W_vs_c128=eW, Y_vs_c128=eY)
+    print(f"\n[parity] {fixture} iid {model} 5 its (mixed, {cov_kind} + {pow_kind}): W err {eW:.2e} Y err {eY:.2e} (bound {TOL:.0e})")
+    assert eW < TOL and eY < TOL
+    # complex128 input: `precise` -- the same power pass, float64 covariances
+    _, W128 = oa.overiva(X.astype(np.complex128), **kw)
+    info = oa.last_solver_info()
+    assert info["precision"] == "precise" and plan.kernel_choice(T, F, M, K, "precise")["pow_kind"] == pow_kind
+    e128 = orc.rel_err(W128, Wr)
+    _log(test="many_sources_64", fixture=fixture + " iid", model=model, n_iter=5, input="c128", mode="precise", W_vs_c128=e128)
+    print(f"\n[parity] {fixture} iid {model} 5 its (precise): W err {e128:.2e} (bound 1e-06)")
+    assert e128 < 1e-6
+    # mixture-like input, complex64: within 1.5 of the reference's own complex64 floors
+    if shape == (192, 128, 16, 5) and model == "gauss":
+        return
+    Xm = orc.synth_mixture(T, F, M, K, seed=sum(shape))
+    _, Wmr = orc.overiva_staged(Xm, **kw)
+    floor = _c64_floor(lambda: orc.overiva_faithful(Xm, **kw)[1], Wmr)
+    _, Wm = oa.overiva(Xm, **kw)
+    assert oa.last_solver_info()["precision"] == "mixed"
+    em = orc.rel_err(Wm, Wmr)
+    bound = max(TOL, 1.5 * floor)
+    _log(test="many_sources_64", fixture=fixture + " mixture", model=model, n_iter=5, input="c64", mode="mixed", W_vs_c128=em,
+         ref_c64_floor=floor, bound_c128=bound)
+    print(f"\n[parity] {fixture} mixture {model} 5 its (mixed): W err {em:.2e} (reference c64 floor {floor:.2e}, bound {bound:.1e})")
+    assert em < bound
+
+
 _RANDOM_SKIPPED = []
 
 

@@ -78,6 +78,27 @@ def test_rows_kernel_against_the_one_matrix_per_wave_kernel(both_forms, case):
     assert e[1] < 1e-11 and e[3] < 1e-5
 
 
+@pytest.mark.parametrize("case", [c for c in CASES if c[1] >= 64], ids=lambda c: "x".join(str(v) for v in c))
+def test_rows_kernel_at_64_bins_and_more_against_the_oracle(both_forms, case):
+    """the cases with whole 64-bin batches of the power pass (one batch, one + a ragged bin, two + two bins at 9 channels) against
+    the oracle itself, not only against the kernel's predecessor: W after three iterations of the row kernel's run within the
+    north star's 1e-5 of the oracle's complex128 result on the i.i.d. cases (even bin counts), within max(1e-5, 1.5 floors) on
+    the mixture-like one (odd), floor = the reference's own complex64 arithmetic against its complex128 one"""
+    T, F, M, splits = case
+    mixture = F % 2 == 1
+    X = orc.synth_mixture(T, F, M, M, seed=T + F + M) if mixture else orc.synth_iid(T, F, M, seed=T + F + M)      # as the child
+    kw = dict(n_src=M, n_iter=3, proj_back=False, model="laplace", return_filters=True)
+    _, Wr = orc.overiva_staged(X, **kw)
+    bound = 1e-5
+    if mixture:
+        with np.errstate(all="ignore"):
+            floor = orc.rel_err(orc.overiva_faithful(X, **kw)[1], Wr)
+        bound = max(bound, 1.5 * floor)
+    e = orc.rel_err(both_forms["1"][f"{T}_{F}_{M}_{splits}_3"], Wr)
+    print(f"\n[det16r] {case}: rows vs oracle after 3 iterations {e:.2e} (bound {bound:.1e})")
+    assert e < bound
+
+
 @pytest.mark.parametrize("shape", [(200, 10, 16), (160, 7, 12), (320, 5, 9)], ids=lambda s: "x".join(str(v) for v in s))
 def test_rows_kernel_against_the_oracle(oa, shape):
     """end to end through overiva() (the default kernel of these shapes) against the oracle's complex128 arithmetic"""
