@@ -248,6 +248,17 @@ int oiva_plan_set_fuse_cov_update(oiva_plan *p, int enable, int *active);
  * (a long frame axis), so only then are the chunks re-ordered; 2 (a test hook, $OIVA_POWER_REVERSE=2) re-orders them in a grid
  * of one round too.  Same bits in every setting (frames are independent in this pass).  Drops captured graphs. */
 int oiva_plan_set_power_reverse(oiva_plan *p, int enable);
+/* Load policy of X in the two streaming passes at 8 channels, float32 sums (cov_dma_kernel, power_kernel; csrc/kernel_choice.h, DESIGN
+ * §3): up to `mb` MB (1e6 bytes) of X -- a fixed set of frame groups, the same in both passes and in every iteration -- are read
+ * with plain loads and may stay in the last-level cache; the rest streams with non-temporal loads.  The share is as many
+ * sixteenths of X as mb holds; frame by frame it can exceed them, and so mb, by up to 64 frames per covariance split (a split
+ * that ends inside a period of 16 groups).  mb <= 0: off, every load plain.  X that fits the budget whole is read plain throughout.  Default: $OIVA_X_RESIDENT_MB at plan creation, else the
+ * library's figure.  Same bits in every setting (only the load instructions differ).  Drops captured graphs. */
+int oiva_plan_set_x_resident_mb(oiva_plan *p, double mb);
+/* What that policy is for the plan's present geometry: *n16 of every 16 frame groups are resident; *nt: the others stream
+ * non-temporally (0: every load is plain); *reason: 0 off, 1 X fits the budget whole, 2 the passes run other kernels, 3 the
+ * geometry does not keep every load step inside one frame group, 4 a share was chosen. */
+int oiva_plan_get_x_resident(oiva_plan *p, int *n16, int *nt, int *reason);
 /* Replay the iteration from a captured hipGraph instead of eager launches (default off). */
 int oiva_plan_use_graph(oiva_plan *p, int enable);
 /* Arithmetic: an OR of OIVA_PREC_* (default OIVA_PREC_FAST).  Call it before oiva_plan_covariance so that the
@@ -355,6 +366,15 @@ int oiva_test_time_stage(oiva_plan *p, int stage, int reps, float *avg_ms);
 /* Test hook: device and pinned buffers the library has handed to its handles and temporaries and not yet taken back, and their
  * bytes, over all handles of the process.  A large buffer resting in the pool (oiva_pool_trim) counts as taken back. */
 int oiva_test_live_buffers(long long *count, long long *bytes);
+/* host only: the load policy of X (oiva_plan_set_x_resident_mb) for T frames of F bins x M channels, covariance splits of cov_tc
+ * frames, power chunks of pow_tcp frames and a budget: out (3) = n16, nt, reason; cov_walk / pow_walk (T each): every frame as
+ * the load steps of the covariance / power kernel meet it -- -1 never, 0 plain, 1 nt, 2 more than once */
+int oiva_test_x_policy(int T, int F, int M, int cov_tc, int pow_tcp, double budget_mb, int *out, signed char *cov_walk, signed char *pow_walk);
+/* host only: the policy a plan with these kernels and this geometry chooses (kinds as oiva_test_kernel_choice reports them):
+ * out (3) = n16, nt, reason.  from_env != 0: the budget a plan created now starts with ($OIVA_X_RESIDENT_MB, else the library's
+ * default) instead of budget_mb; *budget_used (may be NULL) receives the budget applied. */
+int oiva_test_x_choice(int T, int F, int M, int prec_flags, int cov_kind, int cov_tc, int pow_kind, int pow_tcp, double budget_mb, int from_env,
+                       int *out, double *budget_used);
 /* Test hook: the kernels and geometry a plan of this shape and these settings would run on `device` (csrc/kernel_choice.h), by
  * the functions a plan chooses with; nothing is allocated.  prec_flags: OIVA_PREC_*; quad_on / hmfma_on: the switches of
  * oiva_plan_set_cov_quad / _hmfma; *_splits_req: 0 or the splits asked for.  out (18): covariance kind, nsplit, tc, kc, nbg, pad,

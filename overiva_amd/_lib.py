@@ -80,6 +80,8 @@ SIGNATURES = {
     "oiva_plan_set_cov_hmfma": [_vp, _i],
     "oiva_plan_set_fuse_cov_update": [_vp, _i, C.POINTER(_i)],
     "oiva_plan_set_power_reverse": [_vp, _i],
+    "oiva_plan_set_x_resident_mb": [_vp, C.c_double],
+    "oiva_plan_get_x_resident": [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "oiva_plan_use_graph": [_vp, _i],
     "oiva_plan_set_precision": [_vp, _i],
     "oiva_plan_set_resident": [_vp, _i],
@@ -104,6 +106,8 @@ SIGNATURES = {
     "oiva_test_run_power": [_vp, _vp],
     "oiva_test_get_ppart": [_vp, _vp, C.POINTER(_i)],
     "oiva_test_power_order": [_i, _i, _i, _i, C.POINTER(_i)],
+    "oiva_test_x_choice": [_i] * 8 + [C.c_double, _i, C.POINTER(_i), C.POINTER(C.c_double)],
+    "oiva_test_x_policy": [_i, _i, _i, _i, _i, C.c_double, C.POINTER(_i), _vp, _vp],
     "oiva_test_time_stage": [_vp, _i, _i, _fp],
     "oiva_test_live_buffers": [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
     "oiva_test_kernel_choice": [_i] * 11 + [C.POINTER(_i)],

@@ -47,6 +47,7 @@ struct CovGeom {
     CovKind kind = CovKind::Lane;
     int pad = 0;  // odd channel count of 9..15: the kinds that read the padded X read the copy of X padded to M + 1 channels
     int part32 = 0; // Hmfma: the partial blocks leave as float32 (each the float64 sum of its chains, rounded once)
+    int xplain = 16; // cov_dma_kernel: the frame groups g of a split with g % 16 < xplain are loaded plain, the others nt (XPolicy)
 };
 // Which frame chunk the y-th dispatched row of power_kernel's grid takes when the pass runs against the covariance pass
 // (DESIGN §3).  The covariance pass walks `cs` splits of `ctc` frames ascending and side by side, so the X it read last -- what
@@ -87,8 +88,49 @@ struct PowGeom {
     int rev = 0;
     PowOrder ord{};
     int rounds = 1;   // rounds of resident workgroups the grid of power_kernel takes (choose_pow)
+    // the load policy of X (XPolicy below), filled in at launch time like the order: frames in groups of 16 counted from the
+    // start of their covariance split of xctc frames, groups g with g % 16 < xplain loaded plain, the others nt
+    int xplain = 16;
+    int xctc = 0;
 };
 constexpr int kPowMaxFrames = 512;
+
+// ---- one load policy per byte of X, the same in both streaming passes and in every iteration ---------------------
+// The frames of every covariance split are counted off in groups of kXGroup from the split's first frame; of every kXPeriod
+// consecutive groups the first n16 are RESIDENT: both passes read them with plain loads, so they may stay in the Infinity Cache
+// from pass to pass, and read the other groups with non-temporal loads (8 channels: cov_dma_kernel<8, KC>, power_kernel<8, KP>).
+// A covariance step (16 frames) is one group; a power load step (4 frames) lies inside one group because splits and chunks
+// start on multiples of 4 frames.
+constexpr int kXGroup = 16, kXPeriod = 16;
+constexpr bool x_group_plain(int frame_in_split, int xplain) { return ((frame_in_split / kXGroup) % kXPeriod) < xplain; }
+// frame-in-split of the frame `tl` frames behind one at `off0` in its split, for walks that cross at most one split boundary
+constexpr int x_split_offset(int off0, int tl, int ctc) { return off0 + tl >= ctc ? off0 + tl - ctc : off0 + tl; }
+enum class XReason { Off, Fits, Kernels, Geometry, Share };
+constexpr double kXResidentDefaultMB = 268.;      // MB of X that may stay resident: the 256 MiB of the Infinity Cache
+struct XPolicy {
+    int n16 = 0;                     // resident groups of every 16
+    bool nt = false;                 // the other groups stream non-temporally (false: every load of X is plain, as before)
+    XReason why = XReason::Off;
+    int xplain() const { return nt ? n16 : kXPeriod; }      // what the kernels take
+};
+// budget_mb: what may stay resident ($OIVA_X_RESIDENT_MB, oiva_plan_set_x_resident_mb; <= 0: the policy is off).  The share is
+// n16 sixteenths of X, as many as the budget holds.  Counted frame by frame the resident bytes can EXCEED the budget: a split that
+// ends inside a period has up to n16 (16 - n16) <= 64 resident frames more than its sixteenths (headline, 200 MB: 201.3 MB).  All plain, as before: X fits the budget whole (Fits); a pass is not cov_dma_kernel /
+// power_kernel (Kernels); the geometry does not keep every step inside one group (Geometry).
+inline XPolicy choose_x_policy(double budget_mb, int T, int F, int M, bool cov_f64, const CovGeom& cg, const PowGeom& pg) {
+    XPolicy x;
+    if (!(budget_mb > 0.)) return x;
+    const double frame_bytes = (double)F * M * 8., budget = budget_mb * 1e6;
+    x.why = XReason::Fits, x.n16 = kXPeriod;
+    if (frame_bytes * T <= budget) return x;
+    x.why = XReason::Kernels, x.n16 = 0;
+    if (cg.kind != CovKind::Lane || pg.kind != PowKind::Lane || cov_f64 || M != 8) return x;
+    x.why = XReason::Geometry;
+    if (cg.tc % kXGroup != 0 || pg.tcp % 4 != 0 || pg.tcp > cg.tc) return x;
+    x.why = XReason::Share, x.nt = true;
+    x.n16 = std::min(kXPeriod - 1, (int)(budget * kXPeriod / (frame_bytes * T)));
+    return x;
+}
 
 // ---- the traits ----------------------------------------------------------------------------------------------------------------
 enum class Partials { F64, Acc, F32IfPart32 };      // float64 always | the accumulator's type | float32 when CovGeom::part32

@@ -65,7 +65,7 @@ __device__ __forceinline__ void reduce_and_store(const ACC (&acc)[KC][M * M], AC
 template <int M, int KC, bool UNIT, typename ACC>
 __global__ __launch_bounds__(kBlock) void cov_kernel(const float2* __restrict__ X, const float* __restrict__ R,
                                                      float* __restrict__ wscale, int model, int raw,
-                                                     double* __restrict__ Vpart, int T, int F, int K, int tc) {
+                                                     double* __restrict__ Vpart, int T, int F, int K, int tc, int /*xplain*/) {
     constexpr int NA = M * M;
     __shared__ ACC lds[kChunk * kLdsStride];
 
@@ -165,11 +165,11 @@ __global__ __launch_bounds__(kBlock) void cov_kernel(const float2* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 constexpr int kDmaStages = 4;
 
-typedef __attribute__((address_space(1))) const void gvoid_t;
-typedef __attribute__((address_space(3))) void lvoid_t;
-
 template <int PIECES>
 __device__ __forceinline__ void ring_read(unsigned addr, float4 (&v)[PIECES]);
+// the same for a stage that landed row by row (an nt step, XRows in oiva_device.h): the lane's pieces lie side by side
+template <int PIECES>
+__device__ __forceinline__ void ring_read_rows(unsigned addr, float4 (&v)[PIECES]);
 
 template <>
 __device__ __forceinline__ void ring_read<4>(unsigned addr, float4 (&v)[4]) {
@@ -196,6 +196,31 @@ __device__ __forceinline__ void ring_read<2>(unsigned addr, float4 (&v)[2]) {
         : "memory");
 }
 
+template <>
+__device__ __forceinline__ void ring_read_rows<4>(unsigned addr, float4 (&v)[4]) {
+    asm volatile(
+        "s_waitcnt vmcnt(12)\n\t"
+        "ds_read_b128 %0, %4\n\t"
+        "ds_read_b128 %1, %4 offset:16\n\t"
+        "ds_read_b128 %2, %4 offset:32\n\t"
+        "ds_read_b128 %3, %4 offset:48\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
+        : "v"(addr)
+        : "memory");
+}
+template <>
+__device__ __forceinline__ void ring_read_rows<2>(unsigned addr, float4 (&v)[2]) {
+    asm volatile(
+        "s_waitcnt vmcnt(6)\n\t"
+        "ds_read_b128 %0, %2\n\t"
+        "ds_read_b128 %1, %2 offset:16\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(v[0]), "=&v"(v[1])
+        : "v"(addr)
+        : "memory");
+}
+
 // (tools/build_variant.py ... -DOIVA_COVDMA_TRACE: 100 MHz wall-clock stamps of every workgroup, read by tools/r6/covdma_trace.py)
 #ifdef OIVA_COVDMA_TRACE
 __device__ long long g_cd_trace[8 * 2048];
@@ -212,7 +237,7 @@ __device__ long long g_cd_trace[8 * 2048];
 template <int M, int KC>
 __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __restrict__ X, const float* __restrict__ R,
                                                             float* __restrict__ wscale, int model, int raw,
-                                                            double* __restrict__ Vpart, int T, int F, int K, int tc) {
+                                                            double* __restrict__ Vpart, int T, int F, int K, int tc, int xplain) {
     constexpr int NA = M * M;
     constexpr int PIECES = M / 2;                       // 16-byte pieces of one M-vector
     constexpr int STAGE = PIECES * 64;                  // float4 per stage per wave
@@ -251,10 +276,20 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
     const unsigned rd_base = (unsigned)(uintptr_t)(wring) + lane * 16;      // LDS byte address of this lane's slot
     const size_t frame_stride = (size_t)F * M;
     const float2* pbase = X + (size_t)fc * M;
+    // the load policy of X (kernel_choice.h; 8 channels: at 4 the registers of the second form would cost <4, 2> a wave per SIMD):
+    // step i is frame group i of this split, plain or nt; wave-uniform
+    using Rows = XRows<M>;
+    const int row_off = Rows::offset(lane, blockIdx.x * kBinsPerWave, F);
+    const unsigned rd_rows = (unsigned)(uintptr_t)(wring) + Rows::slot(b, ql) * 16;
+    auto plain = [&](int i) { return M != 8 || x_group_plain(kXGroup * i, xplain); };
 
     // issue the M/2 DMA requests of step i into stage s; steps past the end re-request the last frame
     // (legal address, never consumed) so that every step adds the same count to vmcnt
     auto issue = [&](int i, int s) {
+        if (!plain(i)) {
+            Rows::issue_nt(X, frame_stride, row_off, lane, t_begin + wave * kPhasesPerWave + 16 * i, i < nsteps ? t_end : 0, T, wring + s * STAGE);
+            return;
+        }
         const int t = t_begin + q + 16 * i;
         const int tcl = (i < nsteps && t < t_end) ? t : T - 1;
         const float2* src = pbase + (size_t)tcl * frame_stride;
@@ -280,7 +315,10 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
             w[kk] = activation_weight(r, ginv[kk]) * live;
         }
         float4 v[PIECES];
-        ring_read<PIECES>(rd_base + s * STAGE * 16, v);
+        if (plain(i))
+            ring_read<PIECES>(rd_base + s * STAGE * 16, v);
+        else
+            ring_read_rows<PIECES>(rd_rows + s * STAGE * 16, v);
 #if defined(OIVA_COVDMA_ABLATE) && (OIVA_COVDMA_ABLATE & 1)      // variant build (tools/build_variant.py): no arithmetic
         if constexpr (kPacked) {
             if (v[0].x == 12345.f) pacc.add(reinterpret_cast<const v2f(&)[M]>(v), v2f{w[0], w[1]});
@@ -360,7 +398,7 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
 }
 
 template <typename ACC>
-using CovKernel = void (*)(const float2*, const float*, float*, int, int, double*, int, int, int, int);   // ACC = accumulator type
+using CovKernel = void (*)(const float2*, const float*, float*, int, int, double*, int, int, int, int, int);   // ACC = accumulator type
 
 // (M, KC, unit weights) -> kernel instantiation, handed to fn together with its KC.  Register budget:
 // KC * M^2 accumulators of ACC must stay below ~144 registers.
@@ -465,12 +503,12 @@ hipError_t launch_cov(hipStream_t s, const float2* X, const float2* Xpad, const 
     if (f64)
         return dispatch_cov<double>(M, kc, R == nullptr, [&](CovKernel<double> kern, int KC) {
             kern<<<dim3(g.nbg, g.nsplit, (K + KC - 1) / KC), dim3(kBlock), 0, s>>>(X, R, wscale, model, raw,
-                                                                                 static_cast<double*>(Vpart), T, F, K, g.tc);
+                                                                                 static_cast<double*>(Vpart), T, F, K, g.tc, g.xplain);
             return hipGetLastError();
         });
     return dispatch_cov<float>(M, kc, R == nullptr, [&](CovKernel<float> kern, int KC) {
         return launch_dominant(kern, dim3(g.nbg, g.nsplit, (K + KC - 1) / KC), dim3(kBlock), 0, s, X, R, wscale, model, raw,
-                               static_cast<double*>(Vpart), T, F, K, g.tc);
+                               static_cast<double*>(Vpart), T, F, K, g.tc, g.xplain);
     });
 }
 

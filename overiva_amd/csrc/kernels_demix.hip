@@ -16,16 +16,20 @@ namespace {
 // tail first (power_chunk_tail_first) and every chunk is walked from its last step to its first, so that the launch starts on
 // the X the covariance pass read last and ends on the X it reads first.  Frames are independent of each other (the sums run
 // over bins), so every word of Ppart keeps its place and its bits.  rev == 0: chunk = row, ascending.
+// NT: the instantiation that follows the load policy of X (kernel_choice.h; 8 channels, launched only where some group
+// streams): a load step of a streamed group goes HBM -> LDS row by row with nt loads (XRows, oiva_device.h) and the lane picks
+// its own M-vector up from there -- the registers the arithmetic sees are the same values either way.
 // ---------------------------------------------------------------------------------------------
 constexpr int kPowUnroll = 2;
 
-template <int M, int KP>
+template <int M, int KP, bool NT = false>
 __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict__ X, const float2* __restrict__ What,
-                                                       float* __restrict__ Ppart, int T, int F, int K, int tcp, int rev, PowOrder ord) {
+                                                       float* __restrict__ Ppart, int T, int F, int K, int tcp, int rev, PowOrder ord,
+                                                       int xplain, int xctc) {
     extern __shared__ __attribute__((aligned(16))) float sp[];  // [kWaves][tcp][KP]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const int wave = NT ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int b = lane & 15;
     const int q = lane >> 4;
     const int f = (blockIdx.x * kWaves + wave) * kBinsPerWave + b;
@@ -47,19 +51,48 @@ __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict_
     // because a lane's M*8 bytes arrive through M/2 separate dwordx4 requests to the same lines).
     const size_t frame_stride = (size_t)F * M;
     const float2* pbase = X + (size_t)fc * M;
+    // NT: where this chunk starts in its covariance split (a chunk is no longer than a split: choose_x_policy), this lane's
+    // place in a row-contiguous step and in the landed one
+    int off0 = 0, row_off = 0;
+    float4* wrows = nullptr;
+    if constexpr (NT) {
+        __shared__ float4 rows[kWaves * kPowUnroll * 32 * M];      // one landed step (64 lanes x M/2 pieces) per step in flight, per wave
+        off0 = t_begin % xctc;
+        row_off = XRows<M>::offset(lane, (blockIdx.x * kWaves + wave) * kBinsPerWave, F);
+        wrows = rows + wave * kPowUnroll * 32 * M;
+    }
     for (int g = 0; g < ngroups; ++g) {
         const int i = (rev ? ngroups - 1 - g : g) * kPowUnroll;
         float xr[kPowUnroll][M], xi[kPowUnroll][M];
+        bool plain[kPowUnroll];
 #pragma unroll
         for (int u = 0; u < kPowUnroll; ++u) {
             const int tl = 4 * (i + u) + q;
             const int t = tl < len ? t_begin + tl : T - 1;      // clamped: legal address, result unused
+            plain[u] = !NT || x_group_plain(x_split_offset(off0, 4 * (i + u), xctc), xplain);      // wave-uniform
+            if constexpr (NT) {
+                if (!plain[u]) {
+                    XRows<M>::issue_nt(X, frame_stride, row_off, lane, t_begin + 4 * (i + u), t_end, T, wrows + u * 32 * M);
+                    continue;
+                }
+            }
             load_x<M>(pbase + (size_t)t * frame_stride, xr[u], xi[u]);
         }
 #pragma unroll
         for (int u = 0; u < kPowUnroll; ++u) {
             const int tl = 4 * (i + u) + q;
             const bool live = tl < len;
+            if constexpr (NT) {
+                if (!plain[u]) {
+                    // (the compiler waits for the step to land in front of these reads: it counts LDS-DMA like any load)
+                    const float4* v = wrows + u * 32 * M + XRows<M>::slot(b, q);
+#pragma unroll
+                    for (int j = 0; j < M / 2; ++j) {
+                        const float4 p = v[j];
+                        xr[u][2 * j] = p.x, xi[u][2 * j] = p.y, xr[u][2 * j + 1] = p.z, xi[u][2 * j + 1] = p.w;
+                    }
+                }
+            }
 #pragma unroll
             for (int kk = 0; kk < KP; ++kk) {
                 float yr, yi;
@@ -208,7 +241,14 @@ hipError_t launch_power_one(hipStream_t s, const float2* X, const float2* What, 
                             const PowGeom& g) {
     dim3 grid(g.nb, g.nsplit, (K + KP - 1) / KP);
     const size_t shmem = (size_t)kWaves * g.tcp * KP * sizeof(float);
-    hipLaunchKernelGGL((power_kernel<M, KP>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, g.tcp, g.rev, g.ord);
+    if constexpr (M == 8) {
+        if (g.xplain < kXPeriod) {
+            if (g.xctc < g.tcp || g.xctc % kXGroup != 0) return hipErrorInvalidValue;      // (choose_x_policy never asks for it)
+            hipLaunchKernelGGL((power_kernel<M, KP, true>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, g.tcp, g.rev, g.ord, g.xplain, g.xctc);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((power_kernel<M, KP, false>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, g.tcp, g.rev, g.ord, kXPeriod, 0);
     return hipGetLastError();
 }
 

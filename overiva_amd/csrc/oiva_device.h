@@ -65,6 +65,40 @@ __device__ __forceinline__ void load_x(const float2* __restrict__ p, float (&xr)
     }
 }
 
+// ---- the non-temporal form of a wave's load step (4 frames x 16 bins of M = 4 or 8 channels), HBM -> LDS ----
+// nt loads bypass the L1, which is what merges the M/2 requests a lane makes for its own M-vector: a lane-strided nt step moves
+// every line M/2 times across the L2 (3.6 TB/s against 6.0 plain, profiles/mallbench.log).  So the nt step is ROW-CONTIGUOUS: the
+// 16 bins of one frame are one run of 128 M bytes, instruction j of the step takes 1 KB of the step's runs, lane l its bytes
+// [16 l, 16 l + 16), and the step lands in LDS frame by frame, bin by bin -- float4 index (frame * 16 + bin) * M/2 + piece.
+// Lane (bin b, frame phase q) then reads the same M-vector it loads itself in the plain form.
+typedef __attribute__((address_space(1))) const void gvoid_t;
+typedef __attribute__((address_space(3))) void lvoid_t;
+template <int M>
+struct XRows {
+    static_assert(M == 4 || M == 8, "whole 1-KB instructions of 16-byte pieces");
+    static constexpr int kPieces = M / 2;               // 16-byte pieces of one M-vector
+    static constexpr int kLanesPerRow = 16 * kPieces;   // lanes that take one frame's run
+    static constexpr int kFramesPerInstr = 64 / kLanesPerRow;
+    // what this lane requests: frame (of the step's four) in instruction j, and its float2 offset inside a frame of F bins
+    static __device__ __forceinline__ int frame(int lane, int j) { return j * kFramesPerInstr + lane / kLanesPerRow; }
+    static __device__ __forceinline__ int offset(int lane, int f0, int F) {
+        const int r = lane % kLanesPerRow, f = f0 + r / kPieces;
+        return (f < F ? f : F - 1) * M + (r % kPieces) * 2;      // bins past the end: the last bin (legal, never stored)
+    }
+    // float4 index of lane (b, q)'s first piece in the landed step
+    static __device__ __forceinline__ int slot(int b, int q) { return (q * 16 + b) * kPieces; }
+    // request the step whose frames are t0 .. t0 + 3 into `stage` (wave-uniform); frames >= t_lim re-request frame T - 1
+    static __device__ __forceinline__ void issue_nt(const float2* __restrict__ X, size_t frame_stride, int off, int lane, int t0, int t_lim,
+                                                    int T, float4* stage) {
+#pragma unroll
+        for (int j = 0; j < kPieces; ++j) {
+            const int t = t0 + frame(lane, j);
+            const float2* src = X + (size_t)(t < t_lim ? t : T - 1) * frame_stride + off;
+            __builtin_amdgcn_global_load_lds((gvoid_t*)src, (lvoid_t*)(stage + j * 64), 16, 0, /*aux: nt*/ 2);
+        }
+    }
+};
+
 // ---- fp32 / fp64 matrix-core tile of shape 16x16x4 (A, B: one value per lane; C/D: 4 values per lane) ----
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f64x4 = __attribute__((ext_vector_type(4))) double;

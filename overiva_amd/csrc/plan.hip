@@ -54,6 +54,7 @@ struct oiva_plan {
     bool cov_hmfma_on = true;     // oiva_plan_set_cov_hmfma ($OIVA_COV_HMFMA=0: off)
     bool fuse_cov_update = false; // oiva_plan_set_fuse_cov_update ($OIVA_COV_UPDATE=1: on wherever the shape qualifies)
     int power_reverse = 1;        // oiva_plan_set_power_reverse ($OIVA_POWER_REVERSE=0: off): the power pass walks X against the covariance pass; 2: and takes its chunks tail first even in a grid of one round
+    double x_resident_mb = kXResidentDefaultMB;   // oiva_plan_set_x_resident_mb ($OIVA_X_RESIDENT_MB; <= 0: off): how much of X the two streaming passes keep in the Infinity Cache (XPolicy, kernel_choice.h)
     CovGeom stg{};              // geometry of the projection-back statistics pass (16-bin groups, independent of cov)
     PowGeom pw{};
     int n_cu = 256;
@@ -197,11 +198,21 @@ int ensure_vpart(oiva_plan* p) {
     return OIVA_OK;
 }
 
+// the load policy of X for the geometry of THIS launch (the setters of splits and precision change it after plan creation)
+XPolicy x_policy(const oiva_plan* p) { return choose_x_policy(p->x_resident_mb, p->T, p->F, p->M, p->cov_f64(), p->cov, p->pw); }
+CovGeom cov_geom_now(const oiva_plan* p) {
+    CovGeom g = p->cov;
+    g.xplain = x_policy(p).xplain();
+    return g;
+}
+
 // ---- the five stages of one iteration -----------------------------------------------------------
 int stage_power(oiva_plan* p) {
-    // the order follows the covariance geometry of THIS launch (oiva_plan_set_cov_splits and the precision change it after the
-    // power geometry was chosen)
+    // the order and the load policy follow the covariance geometry of THIS launch (oiva_plan_set_cov_splits and the precision
+    // change it after the power geometry was chosen)
     PowGeom g = p->pw;
+    g.xplain = x_policy(p).xplain();
+    g.xctc = p->cov.tc;
     if (p->power_reverse) {
         g.rev = 1;
         // which chunk a row takes only matters when the rows do not all run at once; in one round the order table measured
@@ -226,7 +237,7 @@ int stage_activation(oiva_plan* p, const float* parts, int nparts) {
 }
 int stage_cov(oiva_plan* p) {
     OIVA_TRY_HIP(launch_cov(p->stream, p->X, p->X_pad, p->R, p->Wwide ? static_cast<float*>(p->Wwide) : p->Plocal /* weights scratch, (T,16) */, p->wscale, p->model,
-                       p->raw_weights, p->Vpart, p->cov_f64(), p->T, p->F, p->M, p->K, p->cov));
+                       p->raw_weights, p->Vpart, p->cov_f64(), p->T, p->F, p->M, p->K, cov_geom_now(p)));
     p->wscale_pending = !p->raw_weights;
     return OIVA_OK;
 }
@@ -565,6 +576,8 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
         p->fuse_cov_update = u && u[0] == '1';
         const char* r = std::getenv("OIVA_POWER_REVERSE");      // read here, once: the plan keeps what it was created with
         p->power_reverse = (r && r[0] == '0') ? 0 : (r && r[0] == '2') ? 2 : 1;
+        const char* x = std::getenv("OIVA_X_RESIDENT_MB");
+        if (x && x[0]) p->x_resident_mb = std::atof(x);
     }
     choose_cov_geom(p, 0);
     choose_pow_geom(p, 0);
@@ -1216,6 +1229,19 @@ int oiva_plan_set_power_reverse(oiva_plan* p, int enable) {
     return change_geometry(p, [&] { p->power_reverse = enable < 0 ? 0 : enable > 2 ? 2 : enable; return OIVA_OK; });
 }
 
+int oiva_plan_set_x_resident_mb(oiva_plan* p, double mb) {
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    OIVA_NEED(mb == mb, OIVA_ERR_ARG, "the budget is not a number");
+    return change_geometry(p, [&] { p->x_resident_mb = mb; return OIVA_OK; });
+}
+
+int oiva_plan_get_x_resident(oiva_plan* p, int* n16, int* nt, int* reason) {
+    OIVA_NEED(p && n16 && nt && reason, OIVA_ERR_ARG, "null argument");
+    const XPolicy x = x_policy(p);
+    *n16 = x.n16, *nt = x.nt ? 1 : 0, *reason = (int)x.why;
+    return OIVA_OK;
+}
+
 int oiva_plan_use_graph(oiva_plan* p, int enable) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
@@ -1446,7 +1472,7 @@ int oiva_plan_ogive_iterate(oiva_plan* p, int first_epoch, int n, double step_si
             if (r) return r;
             OIVA_TRY_HIP(launch_activation(p->stream, p->Ppart, p->pw.nb, p->R, p->T, 1, amodel, p->F));   // ive.py:209-217 (floor + 1/r in the consumer)
             OIVA_TRY_HIP(launch_cov(p->stream, p->X, p->X_pad, p->R, p->Plocal, p->wscale, p->model, /*raw: weights 1 / max(r, eps)*/ 1, p->Vpart,
-                               p->cov_f64(), p->T, p->F, p->M, 1, p->cov));                    // ive.py:221-227
+                               p->cov_f64(), p->T, p->F, p->M, 1, cov_geom_now(p)));           // ive.py:221-227
             OIVA_TRY_HIP(launch_ogive_step(p->stream, p->og, p->Vpart, p->vpart_f64(), p->cov.nsplit, p->T, p->F, p->M, step_size,
                                       tol));                                                     // ive.py:228-246
         }
@@ -1642,6 +1668,50 @@ int oiva_test_power_order(int nsplit, int tcp, int cov_splits, int cov_tc, int* 
     OIVA_NEED(cov_splits <= kPowOrderMaxSplits, OIVA_ERR_ARG, "more covariance splits than the order table holds");
     const PowOrder o = make_pow_order(nsplit, tcp, cov_splits, cov_tc);
     for (int y = 0; y < nsplit; ++y) order[y] = power_chunk_tail_first(y, nsplit, o);
+    return OIVA_OK;
+}
+
+int oiva_test_x_policy(int T, int F, int M, int cov_tc, int pow_tcp, double budget_mb, int* out, signed char* cov_walk, signed char* pow_walk) {
+    OIVA_NEED(out && cov_walk && pow_walk && T >= 1 && F >= 1 && M >= 1 && cov_tc >= 1 && pow_tcp >= 1, OIVA_ERR_ARG, "bad arguments");
+    CovGeom cg{};
+    cg.tc = cov_tc, cg.nsplit = ceil_div(T, cov_tc);
+    PowGeom pg{};
+    pg.tcp = pow_tcp, pg.nsplit = ceil_div(T, pow_tcp);
+    const XPolicy x = choose_x_policy(budget_mb, T, F, M, false, cg, pg);
+    out[0] = x.n16, out[1] = x.nt ? 1 : 0, out[2] = (int)x.why;
+    // every frame as the steps of the two kernels meet it: -1 never, 0 plain, 1 nt, 2 more than once or by two policies
+    std::fill(cov_walk, cov_walk + T, (signed char)-1);
+    std::fill(pow_walk, pow_walk + T, (signed char)-1);
+    auto mark = [T](signed char* walk, int t, int frames, bool plain) {
+        for (int u = t; u < std::min(T, t + frames); ++u) walk[u] = walk[u] == -1 ? (plain ? 0 : 1) : 2;
+    };
+    const int xplain = x.xplain();
+    for (int t_begin = 0; t_begin < T; t_begin += cov_tc)            // cov_dma_kernel: step i of a split is its frame group i
+        for (int i = 0; t_begin + 16 * i < std::min(T, t_begin + cov_tc); ++i)
+            mark(cov_walk, t_begin + 16 * i, std::min(16, cov_tc - 16 * i), x_group_plain(kXGroup * i, xplain));
+    for (int t_begin = 0; t_begin < T; t_begin += pow_tcp) {         // power_kernel: steps of 4 frames, offsets as the kernel forms them
+        const int off0 = t_begin % cov_tc;
+        for (int tl = 0; t_begin + tl < std::min(T, t_begin + pow_tcp); tl += 4)
+            mark(pow_walk, t_begin + tl, std::min(4, pow_tcp - tl), !x.nt || x_group_plain(x_split_offset(off0, tl, cov_tc), xplain));
+    }
+    return OIVA_OK;
+}
+
+int oiva_test_x_choice(int T, int F, int M, int prec_flags, int cov_kind, int cov_tc, int pow_kind, int pow_tcp, double budget_mb, int from_env, int* out,
+                       double* budget_used) {
+    OIVA_NEED(out && T >= 1 && F >= 1 && M >= 1 && cov_tc >= 1 && pow_tcp >= 1, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(cov_kind >= 0 && cov_kind < kCovKinds && pow_kind >= 0 && pow_kind < kPowKinds, OIVA_ERR_ARG, "unknown kernel kind");
+    if (from_env) {      // what a plan created now would start with
+        const char* x = std::getenv("OIVA_X_RESIDENT_MB");
+        budget_mb = x && x[0] ? std::atof(x) : kXResidentDefaultMB;
+    }
+    CovGeom cg{};
+    cg.kind = (CovKind)cov_kind, cg.tc = cov_tc, cg.nsplit = ceil_div(T, cov_tc);
+    PowGeom pg{};
+    pg.kind = (PowKind)pow_kind, pg.tcp = pow_tcp, pg.nsplit = ceil_div(T, pow_tcp);
+    const XPolicy x = choose_x_policy(budget_mb, T, F, M, (prec_flags & OIVA_PREC_COV_F64) != 0, cg, pg);
+    out[0] = x.n16, out[1] = x.nt ? 1 : 0, out[2] = (int)x.why;
+    if (budget_used) *budget_used = budget_mb;
     return OIVA_OK;
 }
 

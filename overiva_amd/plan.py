@@ -231,6 +231,21 @@ class Plan(_lib.Handle):
         ascending; ``2``: the chunks tail first even in a grid of one round (test hook); same bits, drops captured graphs"""
         _lib.check(self.lib.oiva_plan_set_power_reverse(self.h, int(enable)))
 
+    X_RESIDENT_REASONS = ("off", "fits", "kernels", "geometry", "share")
+
+    def set_x_resident_mb(self, mb):
+        """streaming passes at 8 channels: up to ``mb`` MB of X (a fixed set of frame groups) are read with plain loads and
+        may stay in the last-level cache, the rest streams non-temporally; ``0``: off, every load plain (``$OIVA_X_RESIDENT_MB`` at
+        plan creation); same bits, drops captured graphs"""
+        _lib.check(self.lib.oiva_plan_set_x_resident_mb(self.h, float(mb)))
+
+    def x_resident(self):
+        """``(n16, nt, reason)`` of the load policy of X for the present geometry: ``n16`` of every 16 frame groups resident,
+        whether the others stream non-temporally, and why (one of ``X_RESIDENT_REASONS``)"""
+        n16, nt, why = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self.lib.oiva_plan_get_x_resident(self.h, C.byref(n16), C.byref(nt), C.byref(why)))
+        return n16.value, bool(nt.value), self.X_RESIDENT_REASONS[why.value]
+
     def use_graph(self, enable=True):
         _lib.check(self.lib.oiva_plan_use_graph(self.h, 1 if enable else 0))
 
@@ -367,13 +382,20 @@ KERNEL_CHOICE = ("cov_kind", "nsplit", "tc", "kc", "nbg", "pad", "part32", "vpar
                  "tcp", "kp", "rounds", "occ_cov", "occ_pow", "n_cu")
 
 
-def kernel_choice(T, F, M, K, mode="fast", F_total=None, cov_quad=True, cov_hmfma=True, cov_splits=0, pow_splits=0, device=0):
+def kernel_choice(T, F, M, K, mode="fast", F_total=None, cov_quad=True, cov_hmfma=True, cov_splits=0, pow_splits=0, device=0,
+                  x_resident_mb=None):
     """the kernels and geometry a plan of this shape and these settings runs (csrc/kernel_choice.h; test hook, allocates
-    nothing): a dict of ``KERNEL_CHOICE`` with the three kinds by name.  ``mode`` as ``Plan.set_precision``."""
+    nothing): a dict of ``KERNEL_CHOICE`` with the three kinds by name, and the load policy of X on that geometry as
+    ``x_n16``, ``x_nt``, ``x_why`` (``Plan.x_resident``) for the budget ``x_budget_mb`` = ``x_resident_mb``, or what a plan created
+    now starts with.  ``mode`` as ``Plan.set_precision``."""
     flags = _lib.PREC_BY_NAME[mode] if isinstance(mode, str) else int(mode)
     out = (C.c_int * len(KERNEL_CHOICE))()
     _lib.check(_lib.load().oiva_test_kernel_choice(int(device), int(T), int(F), int(F if F_total is None else F_total), int(M), int(K),
                                                    flags, int(bool(cov_quad)), int(bool(cov_hmfma)), int(cov_splits), int(pow_splits), out))
     d = dict(zip(KERNEL_CHOICE, out))
+    x, mb = (C.c_int * 3)(), C.c_double()
+    _lib.check(_lib.load().oiva_test_x_choice(int(T), int(F), int(M), flags, d["cov_kind"], d["tc"], d["pow_kind"], d["tcp"],
+                                              0. if x_resident_mb is None else float(x_resident_mb), int(x_resident_mb is None), x, C.byref(mb)))
+    d["x_n16"], d["x_nt"], d["x_why"], d["x_budget_mb"] = x[0], bool(x[1]), Plan.X_RESIDENT_REASONS[x[2]], mb.value
     d["cov_kind"], d["unit_kind"], d["pow_kind"] = COV_KINDS[d["cov_kind"]], COV_KINDS[d["unit_kind"]], POW_KINDS[d["pow_kind"]]
     return d
