@@ -9,8 +9,8 @@
 //   qL, qS    quadratic forms per 64-row block of G / G_jj, added in block order by the criteria kernel
 //
 // The room comes from the grid and a workgroup never holds two rooms.  Every sum runs in an order that is a function of the
-// room's own (n, N, Lf) and of the element's index: the lag sums run sample by sample inside segments whose bounds follow from n
-// alone and the segments are added in order; the factorisation, the substitutions and the quadratic forms walk 64-wide blocks in
+// room's own (n, N, Lf) and of the element's index: the lag sums run sample by sample inside 128-sample steps, the steps are added in order
+// inside segments whose bounds follow from n alone and the segments are added in order; the factorisation, the substitutions and the quadratic forms walk 64-wide blocks in
 // ascending order with one fixed order inside a block.  Nothing depends on B, on the room's place in the batch, on the lengths of
 // the other rooms or on how the rooms are grouped for memory.  A room therefore gets the same bits alone, in a larger batch, in a
 // permuted one and in a ragged one.
@@ -32,7 +32,9 @@ __device__ __forceinline__ bool room_flagged(const int* flag, int room) { return
 
 // ---------------------------------------------------------------------------------------------
 // lag sums: one workgroup = (room, segment, signal b_x, 256 lags); lane = lag tau; N accumulators, one per reference s_i.
-// A step stages kTile samples of the N references and kTile + 256 of b_x; the sum runs over u in ascending order.
+// A step stages kTile samples of the N references and kTile + 256 of b_x; its products are added in ascending u from zero and
+// the step's sum is then added to the segment's: chains of kTile and of kBssSeg / kTile additions, not one of kBssSeg (the SAR
+// subtracts numbers a thousand times its denominator and answers to the last bits of G, D and E: DESIGN.md 3.10).
 // ---------------------------------------------------------------------------------------------
 template <int N>
 __global__ __launch_bounds__(kLagLanes) void bss_lag_kernel(const double* __restrict__ ref, const double* __restrict__ est,
@@ -68,13 +70,20 @@ __global__ __launch_bounds__(kLagLanes) void bss_lag_kernel(const double* __rest
             sb[idx] = g < n ? b[g] : 0.;
         }
         __syncthreads();
+        double tile[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) tile[i] = 0.;
+        double tileE = 0.;
 #pragma unroll 4
         for (int u = 0; u < len; ++u) {
             const double bv = sb[u + tid];
 #pragma unroll
-            for (int i = 0; i < N; ++i) acc[i] = fma(sa[u][i], bv, acc[i]);
-            accE = fma(bv, bv, accE);
+            for (int i = 0; i < N; ++i) tile[i] = fma(sa[u][i], bv, tile[i]);
+            tileE = fma(bv, bv, tileE);
         }
+#pragma unroll
+        for (int i = 0; i < N; ++i) acc[i] += tile[i];
+        accE += tileE;
         __syncthreads();
     }
     const int tau = tau0 + tid;

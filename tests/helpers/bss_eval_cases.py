@@ -13,7 +13,12 @@ import bss_eval_oracle as bso
 
 SEED = 23
 # (kind, B, N, n, Lf)
-CASES = [("white", 3, 1, 300, 8), ("white", 2, 2, 700, 33), ("ar", 2, 3, 1500, 70), ("ar", 1, 5, 1200, 20), ("ar", 1, 2, 4000, 512)]
+CASES = [("white", 3, 1, 300, 8), ("white", 2, 2, 700, 33), ("ar", 2, 3, 1500, 70), ("ar", 1, 5, 1200, 20), ("ar", 1, 2, 4000, 512),
+         # N = 4, 6, 7, 8 (8: 72 vectors in the quadratic forms, 8 right-hand sides per substitution); n of exactly one segment of
+         # 2048, of one sample more and of whole 128-sample tiles; Lf = 64 (a small system is one block), 257 (a single lag in the
+         # second 256), N Lf = 512 and 192 (whole blocks)
+         ("ar", 1, 4, 2048, 16), ("white", 2, 6, 2049, 11), ("ar", 1, 7, 1000, 10), ("ar", 1, 8, 900, 9), ("white", 1, 8, 1100, 64),
+         ("white", 1, 2, 1500, 257), ("ar", 1, 3, 700, 64), ("ar", 1, 4, 640, 128), ("white", 1, 1, 128, 64)]
 ADMIT_DB = 1e-6          # a case is admitted only if 10 x yardstick <= this
 FACTOR = 10.0
 

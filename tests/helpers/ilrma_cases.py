@@ -9,9 +9,14 @@ SEED = 11
 # (T, F, M, L) of the iterated comparisons: no case has fewer than 70 frames (a mixture at 33 frames, M = L = 3, overfits)
 SHORT_SHAPES = [(70, 17, 2, 2), (100, 65, 3, 3), (70, 17, 4, 2), (257, 20, 8, 2)]
 LONG_SHAPES = [(70, 17, 2, 2), (100, 65, 3, 3), (257, 20, 8, 2)]
+# the component counts and channel counts the shapes above leave out: LP = 8 and 16 with L below and at LP, LP = 4 exact, M = 6, 7
+WIDE_SHAPES = [(70, 17, 6, 5), (100, 33, 7, 8), (130, 17, 3, 9), (64, 16, 2, 16), (128, 64, 2, 16), (70, 17, 4, 4)]
+ONE_CHANNEL = (70, 5, 1, 4)          # i.i.d. only: a one-source mixture is the same thing
 # (kind, shape, n_iter): 1 and 5 epochs on i.i.d. and mixture input, 20 epochs on i.i.d. input only
 ITERATED = ([(kind, shape, n) for kind in ("iid", "mix") for shape in SHORT_SHAPES for n in (1, 5)]
-            + [("iid", shape, 20) for shape in LONG_SHAPES])
+            + [("iid", shape, 20) for shape in LONG_SHAPES]
+            + [(kind, shape, n) for kind in ("iid", "mix") for shape in WIDE_SHAPES for n in (1, 5)]
+            + [("iid", ONE_CHANNEL, n) for n in (1, 5)])
 
 
 def case_id(case):

@@ -110,8 +110,26 @@ def test_batch_matches_single_calls(oa, M, K, model, proj_back, w0, dtype):
         assert orc.rel_err(W[0], Wr) < 1e-5
 
 
+# 9 to 16 parts of 64 bins: the activation sums them 16 at a time in blocks of two.  520 bins are 9 parts with a short fifth
+# block, 1024 bins are 16 parts in 8 full blocks.  A wrong canonical order of that float32 sum moves r by about 1e-8 relative.
+@pytest.mark.parametrize("model", ["laplace", "gauss"])
+@pytest.mark.parametrize("F", [520, 1024])
+def test_batch_matches_single_calls_at_9_to_16_parts(oa, F, model):
+    B, T, M, K = 2, 64, 2, 2
+    X = np.stack([orc.synth_iid(T, F, M, seed=1000 + F + b) for b in range(B)]).astype(np.complex128)
+    kw = dict(n_src=K, n_iter=12, proj_back=False, model=model, return_filters=True)
+    Y, W = oa.overiva_batch(X, **kw)
+    assert Y.dtype == np.complex128 and Y.shape == (B, T, F, K) and W.shape == (B, F, M, K)
+    assert oa.last_solver_info()["batched"] == B and oa.last_solver_info()["precision"] == "precise"
+    for b in range(B):
+        Ys, Ws = _single(oa, X[b], **kw)
+        eW, eY = orc.rel_err(W[b], Ws), orc.rel_err(Y[b], Ys)
+        print(f"batch F={F} {model} problem {b}: W {eW:.2e}, Y {eY:.2e} of the single call's")
+        assert eW < SAME and eY < SAME, (b, eW, eY)
+
+
 # ---- 3. bitwise batch invariance --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("T, F, M, K", [(64, 2049, 4, 2), (100, 40, 6, 3), (48, 7, 8, 8)])
+@pytest.mark.parametrize("T, F, M, K", [(64, 2049, 4, 2), (100, 40, 6, 3), (48, 7, 8, 8), (64, 520, 2, 2)])
 def test_batch_bits_do_not_depend_on_the_batch(oa, T, F, M, K):
     B = 8
     X = np.stack([orc.synth_iid(T, F, M, seed=7 * b + M) if b % 2 else orc.synth_mixture(T, F, M, K, seed=7 * b + M)

@@ -11,9 +11,28 @@ Measured on the CPU for the restatement (delta / distance between forms, dB; con
     ar    N=3 n=1500 Lf=70  : <= 4.0e-12 / <= 6.6e-11 ; 1e3
     ar    N=5 n=1200 Lf=20  : 5.7e-12 / 3.7e-12       ; 5e2
     ar    N=2 n=4000 Lf=512 : 1.4e-12 / 5.1e-11       ; 3e3
+    ar    N=4 n=2048 Lf=16  : 2.3e-12 / 3.9e-11       ; 3e2
+    white N=6 n=2049 Lf=11  : <= 1.8e-12 / <= 4.8e-12 ; 2
+    ar    N=7 n=1000 Lf=10  : 1.3e-12 / 2.1e-12       ; 3e2
+    ar    N=8 n=900  Lf=9   : 1.1e-12 / 4.9e-12       ; 3e2
+    white N=8 n=1100 Lf=64  : 1.8e-12 / 8.3e-12       ; 2e1
+    white N=2 n=1500 Lf=257 : 1.3e-12 / 1.8e-12       ; 1e1
+    ar    N=3 n=700  Lf=64  : 3.5e-12 / 9.8e-12       ; 1e3
+    ar    N=4 n=640  Lf=128 : 4.6e-12 / 7.6e-12       ; 2e4
+    white N=1 n=128  Lf=64  : 6.7e-13 / 2.9e-12       ; 3e1
 Measured on an MI355X: see DESIGN.md 3.10.
 
-The lag pass works in segments of 2048 samples: the 4000-sample case runs two segments with a partial last one.
+The lag pass works in segments of 2048 samples: the 4000-sample case runs two segments with a partial last one, the 2048-sample
+case exactly one, the 2049-sample case a second one of a single sample.
+
+``test_stages_against_numpy[white-B1-N2-n1500-Lf257]`` is the case that made the lag pass add each 128-sample step from zero
+and then the steps, not up to 2048 products in one chain.  The SAR of this room is 30-32 dB with ``E_k / art`` = 1e3 .. 1.7e3 in
+``art = E_k - 2 D_k^T C_k + tot``, and the Gram form reacts to the last bits of G, D and E there: on the restatement's own G, D, E a
+relative perturbation of 3e-16 per entry moves its SAR by up to 1.1e-11 dB, 1e-15 by 1.9e-11 dB.  With one chain per segment the
+device's G and D were 4.5e-16 and 1.2e-15 from NumPy's and the SAR 2.04e-11 dB from the time-domain form against 10 x yardstick =
+1.84e-11 dB (the NumPy Gram form on the DEVICE's G, D, E landed on the same 2.04e-11); with the steps added separately they are
+1.5e-16 and 1.7e-16, and the distance is 2.27e-12 dB.  Over all cases G, D, E went from <= 2.9e-15 to <= 5.4e-16 and the worst
+ratio of distance to bound from 1.11 to 0.59 (ar N=4 n=640 Lf=128: 4.45e-11 against 7.56e-11).
 """
 import os
 import subprocess
@@ -73,9 +92,14 @@ def test_stages_against_numpy(case):
 
 
 def test_ragged_rooms_have_the_bits_of_their_own_call():
+    """the second trio: a room of exactly one 2048-sample segment, one of a segment and one sample, and a shorter one"""
+    _ragged_rooms(2, 33, [700, 655, 1001])
+    _ragged_rooms(4, 16, [2048, 2049, 1000])
+
+
+def _ragged_rooms(N, Lf, lens):
     from overiva_amd import bss_eval_batch, last_batch_info
 
-    N, Lf, lens = 2, 33, [700, 655, 1001]
     rooms = [cases.make_room("white", N, n, 300 + b) for b, n in enumerate(lens)]
     out = bss_eval_batch([r for r, _ in rooms], [e for _, e in rooms], filter_length=Lf, return_matrices=True)
     info = last_batch_info()
@@ -87,14 +111,18 @@ def test_ragged_rooms_have_the_bits_of_their_own_call():
 
 
 def test_bits_do_not_depend_on_the_batch():
+    """five rooms of three sources, then three rooms of eight: 72 vectors in the quadratic forms, 8 right-hand sides"""
+    _batch_bits(5, 3, 20, 900, [3, 0, 4, 2, 1])
+    _batch_bits(3, 8, 9, 900, [2, 0, 1])
+
+
+def _batch_bits(B, N, Lf, n, order):
     from overiva_amd import bss_eval_batch
     from overiva_amd.metrics import BssEval
 
-    B, N, Lf, n = 5, 3, 20, 900
     rooms = [cases.make_room("ar", N, n, 400 + b) for b in range(B)]
     ref, est = np.stack([r for r, _ in rooms]), np.stack([e for _, e in rooms])
     together = bss_eval_batch(ref, est, filter_length=Lf, return_matrices=True)
-    order = [3, 0, 4, 2, 1]
     permuted = bss_eval_batch(ref[order], est[order], filter_length=Lf, return_matrices=True)
     for b in range(B):
         alone = bss_eval_batch(ref[b:b + 1], est[b:b + 1], filter_length=Lf, return_matrices=True)

@@ -139,6 +139,23 @@ def test_ogive_batch_matches_single_calls(oa, M, update, model, w0, dtype):
             assert orc.rel_err(got[e][b], sgot[e]) < tol
 
 
+# 9 to 16 parts of 64 bins (520 bins: a short fifth block of two; 1024 bins: 8 full blocks), as test_batch_gpu.py
+@pytest.mark.parametrize("model", ["laplace", "gauss"])
+@pytest.mark.parametrize("F", [520, 1024])
+def test_ogive_batch_matches_single_calls_at_9_to_16_parts(oa, F, model):
+    B, T, M, n = 2, 64, 2, 120
+    X = np.stack([orc.synth_iid(T, F, M, seed=1200 + F + b) for b in range(B)]).astype(np.complex128)
+    kw = dict(n_iter=n, tol=0.0, model=model, return_filters=True)
+    Y, w = oa.ogive_batch(X, **kw)
+    info = oa.last_batch_info()
+    assert info["batched"] == B and info["precision"] == "precise" and info["epochs"] == [n] * B
+    for b in range(B):
+        Ys, ws = _single(oa, X[b], **kw)
+        ew, eY = orc.rel_err(w[b], ws), orc.rel_err(Y[b], Ys)
+        print(f"ogive batch F={F} {model} problem {b}: w {ew:.2e}, Y {eY:.2e} of the single call's")
+        assert ew < SAME and eY < SAME, (b, ew, eY)
+
+
 # ---- 3. a stopping rule per problem ------------------------------------------------------------------------------------------
 def test_ogive_batch_stops_each_problem_at_its_own_epoch(oa):
     T, F, M, n = 96, 45, 4, 300
@@ -184,7 +201,7 @@ def test_ogive_batch_stops_each_problem_at_its_own_epoch(oa):
 
 
 # ---- 4. bitwise batch invariance --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("T, F, M", [(64, 2049, 4), (90, 37, 6)])
+@pytest.mark.parametrize("T, F, M", [(64, 2049, 4), (90, 37, 6), (64, 520, 2)])
 def test_ogive_batch_bits_do_not_depend_on_the_batch(oa, T, F, M):
     B = 8
     X = np.stack([orc.synth_iid(T, F, M, seed=7 * b + M) if b % 2 else _mix(T, F, M, 7 * b + M) for b in range(B)])

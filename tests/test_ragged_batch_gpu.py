@@ -48,6 +48,7 @@ BIT_CASES = [
     (67, 6, 3, "gauss", np.complex64, (63, 65, 256, 300), True, True),
     (7, 8, 4, "laplace", np.complex128, (16, 65, 160, 520), False, False),
     (67, 8, 8, "gauss", np.complex128, (16, 147, 257), True, False),
+    (520, 2, 2, "gauss", np.complex128, (64, 65, 100), False, False),          # 9 parts of 64 bins: summed 16 at a time
 ]
 
 
@@ -130,6 +131,22 @@ def test_ragged_matches_single_calls(oa, M, K, model, proj_back, w0, dtype):
         assert orc.rel_err(Ys[b], Y1) < tol, (b, orc.rel_err(Ys[b], Y1))
         for e in range(2):
             assert orc.rel_err(got[e][b], sgot[e]) < tol
+
+
+# 9 to 16 parts of 64 bins (520 bins: a short fifth block of two; 1024 bins: 8 full blocks), as test_batch_gpu.py
+@pytest.mark.parametrize("model", ["laplace", "gauss"])
+@pytest.mark.parametrize("F", [520, 1024])
+def test_ragged_matches_single_calls_at_9_to_16_parts(oa, F, model):
+    frames, M, K = (64, 65), 2, 2
+    Xs = [orc.synth_iid(T, F, M, seed=1100 + F + b).astype(np.complex128) for b, T in enumerate(frames)]
+    kw = dict(n_src=K, n_iter=12, proj_back=False, model=model, return_filters=True)
+    Ys, W = oa.overiva_batch_ragged(Xs, **kw)
+    assert oa.last_solver_info()["batched"] == len(frames) and oa.last_solver_info()["precision"] == "precise"
+    for b, X in enumerate(Xs):
+        Y1, W1 = _single(oa, X, **kw)
+        eW, eY = orc.rel_err(W[b], W1), orc.rel_err(Ys[b], Y1)
+        print(f"ragged F={F} {model} problem {b}: W {eW:.2e}, Y {eY:.2e} of the single call's")
+        assert eW < SAME and eY < SAME, (b, eW, eY)
 
 
 # ---- 4. reference parity --------------------------------------------------------------------------------------------------------

@@ -42,7 +42,8 @@ def _sir(sig, src):
 
 
 # ---- 1. analysis -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("frame,hop,C", [(64, 32, 3), (512, 256, 8), (4096, 2048, 4), (128, 128, 1), (256, 64, 2), (96, 32, 5), (30, 10, 4)])
+@pytest.mark.parametrize("frame,hop,C", [(64, 32, 3), (512, 256, 8), (4096, 2048, 4), (128, 128, 1), (256, 64, 2), (96, 32, 5), (30, 10, 4),
+                                         (96, 32, 6), (64, 32, 7)])
 @pytest.mark.parametrize("B", [1, 5])
 def test_analysis_dense_matches_the_oracle(frame, hop, C, B):
     from overiva_amd import BatchSTFT
@@ -61,7 +62,7 @@ def test_analysis_dense_matches_the_oracle(frame, hop, C, B):
         assert err < TOL
 
 
-@pytest.mark.parametrize("frame,hop,C", [(64, 32, 3), (512, 256, 8), (4096, 2048, 4), (128, 128, 1)])
+@pytest.mark.parametrize("frame,hop,C", [(64, 32, 3), (512, 256, 8), (4096, 2048, 4), (128, 128, 1), (96, 32, 6), (64, 32, 7)])
 def test_analysis_ragged_matches_the_oracle(frame, hop, C):
     """lengths that are and are not multiples of hop, a room of exactly one hop, a loud room in front of a silent-start room"""
     from overiva_amd import BatchSTFT
