@@ -615,6 +615,47 @@ oiva_status oiva_bsseval_get_criteria(oiva_bsseval *p, double *sdr, double *sir,
 oiva_status oiva_bsseval_status(oiva_bsseval *p, int *status);
 oiva_status oiva_bsseval_time_stages(oiva_bsseval *p, int n, float *per_stage_ms);
 
+/*
+ * Shoebox rooms by the image-source method on the device (room.hip, kernels_room.hip): impulse responses, premix
+ * (every source convolved with its response at every microphone) and mix-down of B rooms of S sources (1..16) and M microphones
+ * (1..32), all arithmetic in float64.  One handle = one set of geometries; fs, c and max_order (0..32) are the batch's.
+ *   room_dim (B, 3), sources (B, S, 3), mics (B, M, 3), absorption6 (B, 6): energy absorption in [0, 1) of the walls x=0, x=Lx,
+ *   y=0, y=Ly, z=0, z=Lz.  rir_length: 0 = room b gets k_max,b + 81 samples, else that many for every room (<= 65536).
+ *   oiva_room_compute_rir : k_max of every room, then every impulse response (once per handle)
+ *   oiva_room_rir_lengths : lengths[B] (may be NULL) and the number of images (may be NULL)
+ *   oiva_room_get_rir     : packed (sum_b S M Lr_b): room b's (S, M, Lr_b), row-major, room after room
+ *   oiva_room_set_signals : n_samples[B] and the packed signals (sum_b S n_b): room b's (S, n_b); max_group: 0, or the most rooms
+ *                           whose premix may be held at once (the handle halves the group by itself when the allocation fails)
+ *   oiva_room_groups      : rooms per group; a group is named by its first room g0 = 0, group, 2 group, ...
+ *   oiva_room_convolve    : the premix of group g0: room b's (S, M, n_b + Lr_b - 1), the full linear convolution.  One premix
+ *                           buffer: convolving a group gives up the premix and the mix of the group before
+ *   oiva_room_get_premix  : packed premix of group g0, room after room
+ *   oiva_room_mix         : group g0 (convolved): every source divided by its population standard deviation at ref_mic, targets
+ *                           s < K scaled by sqrt(sources_var[s]) (NULL: ones), the others by sigma_i, background = their sum +
+ *                           sigma_n * noise (packed (n_out_b, M) of the group's rooms, NULL: none); K == S needs sinr = +inf
+ *   oiva_room_get_mix     : packed mix (n_out_b, M) and ref (K + 1, n_out_b, M) of group g0, room after room
+ *   oiva_room_time_stages : n full runs (unit sources_var, no noise) with events around every stage: per_stage_ms[4] = k_max,
+ *                           impulse responses, convolution, mix-down; ms per run
+ * A room's bits do not depend on B, on its place in the batch, on the other rooms or on the grouping.  Every entry checks its
+ * arguments before any device call and is synchronous.
+ */
+typedef struct oiva_room oiva_room;
+oiva_status oiva_room_create(oiva_room **out, int device, int B, int S, int M, double fs, double c, int max_order,
+                             const double *room_dim, const double *sources, const double *mics, const double *absorption6,
+                             int rir_length, void *stream);
+oiva_status oiva_room_destroy(oiva_room *p);
+oiva_status oiva_room_compute_rir(oiva_room *p);
+oiva_status oiva_room_rir_lengths(oiva_room *p, int *lengths, int *images);
+oiva_status oiva_room_get_rir(oiva_room *p, double *rir_host_packed);
+oiva_status oiva_room_set_signals(oiva_room *p, const int *n_samples, const double *signals_host_packed, int max_group);
+oiva_status oiva_room_groups(oiva_room *p, int *rooms_per_group);
+oiva_status oiva_room_convolve(oiva_room *p, int g0);
+oiva_status oiva_room_get_premix(oiva_room *p, int g0, double *premix_host_packed);
+oiva_status oiva_room_mix(oiva_room *p, int g0, int K, double sinr, double snr, int ref_mic, const double *sources_var,
+                          const double *noise_host_packed);
+oiva_status oiva_room_get_mix(oiva_room *p, int g0, double *mix_host_packed, double *ref_host_packed);
+oiva_status oiva_room_time_stages(oiva_room *p, int n, int K, double sinr, double snr, int ref_mic, float *per_stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,18 @@ SIGNATURES = {
     "oiva_bsseval_get_criteria": [_vp, _vp, _vp, _vp],
     "oiva_bsseval_status": [_vp, C.POINTER(_i)],
     "oiva_bsseval_time_stages": [_vp, _i, _fp],
+    "oiva_room_create": [C.POINTER(_vp), _i, _i, _i, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _i, _vp],
+    "oiva_room_destroy": [_vp],
+    "oiva_room_compute_rir": [_vp],
+    "oiva_room_rir_lengths": [_vp, C.POINTER(_i), C.POINTER(_i)],
+    "oiva_room_get_rir": [_vp, _vp],
+    "oiva_room_set_signals": [_vp, C.POINTER(_i), _vp, _i],
+    "oiva_room_groups": [_vp, C.POINTER(_i)],
+    "oiva_room_convolve": [_vp, _i],
+    "oiva_room_get_premix": [_vp, _i, _vp],
+    "oiva_room_mix": [_vp, _i, _i, C.c_double, C.c_double, _i, _vp, _vp],
+    "oiva_room_get_mix": [_vp, _i, _vp, _vp],
+    "oiva_room_time_stages": [_vp, _i, _i, C.c_double, C.c_double, _i, _fp],
 }
 
 

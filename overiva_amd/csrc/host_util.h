@@ -1,4 +1,4 @@
-// The host layer shared by plan.hip, batch.hip, bsseval.hip, stft.hip, bstft.hip and exchange.hip: error plumbing, the
+// The host layer shared by plan.hip, batch.hip, bsseval.hip, room.hip, stft.hip, bstft.hip and exchange.hip: error plumbing, the
 // current-device guard, the owner of a handle's device and pinned memory (DeviceArena) and of its stream and events (HandleStream),
 // graph capture and its cache, W_hat packing, the statistics geometry and the OGIVE per-bin state.  Host code only, no kernels.
 // What is state -- the last error, the allocators and their process-wide pool of large buffers, the count of live buffers --

@@ -427,6 +427,42 @@ hipError_t launch_bss_criteria(hipStream_t s, const double* lag, const double* E
                                double* qL, double* qS, double* sdr, double* sir, double* sar, int g0, int rooms, int N, int Lf,
                                int diag_only, const int* flag);
 
+// Shoebox image-source rooms (kernels_room.hip, room.hip): impulse responses, premix and mix-down of B rooms of S
+// sources and M microphones, float64.  One record per room; every field is the room's own.
+constexpr int kRoomFdl = 81;          // taps of one image's windowed sinc
+constexpr int kRoomHalf = 40;         // its fixed lag
+constexpr int kRoomMaxOrder = 32;
+constexpr int kRoomMaxSrc = 16;
+constexpr int kRoomMaxMic = 32;
+constexpr int kRoomMaxRir = 65536;
+struct RoomRec {
+    double dim[3];       // Lx, Ly, Lz
+    double beta[6];      // sqrt(1 - alpha) of the walls x=0, x=Lx, y=0, y=Ly, z=0, z=Lz
+    long long rir_off;   // first element of the room's (S, M, Lr) impulse responses in the packed buffer
+    int Lr;              // length of its impulse responses
+    int pad;
+};
+//   images (n_img) of (nx, ny, nz, 0) in enumeration order; src (B, S, 3), mic (B, M, 3); tau = d * fs_over_c
+//   kmax[b] = max(kmax[b], largest k of room b): an integer max, the caller zeroes it
+hipError_t launch_room_kmax(hipStream_t s, const RoomRec* rooms, const double* src, const double* mic, const char4* images, int n_img,
+                            int B, int S, int M, double fs_over_c, int* kmax);
+//   rir packed by rooms[b].rir_off: every sample of every pair is written, its terms added in the order of the images
+hipError_t launch_room_rir(hipStream_t s, const RoomRec* rooms, const double* src, const double* mic, const char4* images, int n_img,
+                           int B, int S, int M, int max_Lr, double fs_over_c, double* rir);
+//   dst (rows, nfft) = src (rows, len), zero-padded; the rows of src lie src_stride apart
+hipError_t launch_room_pad(hipStream_t s, const double* src, long long src_stride, int len, double* dst, int nfft, int rows);
+//   H (S, M, nf) *= X (S, nf)
+hipError_t launch_room_product(hipStream_t s, double2* H, const double2* X, int nf, int S, int M);
+//   premix (rows, n_out) = y (rows, nfft)[:n_out] / nfft
+hipError_t launch_room_unpack(hipStream_t s, const double* y, int nfft, double* premix, int n_out, int rows);
+//   std[s_] = population standard deviation of premix[s_, ref_mic, :] of one room (S, M, n_out): mean first, then the squares, a
+//   fixed tree
+hipError_t launch_room_std(hipStream_t s, const double* premix, int S, int M, int n_out, int ref_mic, double* std);
+//   mix (n_out, M) and ref (K + 1, n_out, M) of one room: premix[s_] / std[s_] * scale[s_], targets s_ < K, the rest and
+//   sigma_n * noise (n_out, M; may be null) to the background
+hipError_t launch_room_mix(hipStream_t s, const double* premix, const double* std, const double* scale, const double* noise,
+                           double sigma_n, int S, int M, int K, int n_out, double* mix, double* ref);
+
 // dense complex128 <-> complex64 conversion on the device
 hipError_t launch_cast_c128_to_c64(hipStream_t s, const double2* in, float2* out, long long n);
 hipError_t launch_cast_c64_to_c128(hipStream_t s, const float2* in, double2* out, long long n);
