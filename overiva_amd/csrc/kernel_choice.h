@@ -216,6 +216,7 @@ struct ChoiceIn {
     bool part32 = false;       // $OIVA_HMFMA_PART32=1: float32 partials where the kind can leave them
     bool kc_wide = true;       // $OIVA_COV_KC_WIDE
     bool power_lds = true;     // $OIVA_POWER_LDS
+    double x_resident_mb = 0.; // the budget of the load policy of X (XPolicy): where X streams, the power pass takes other chunks
 };
 // the only device queries the choice makes: workgroups of an instantiation one CU holds at once (< 1: the query failed)
 struct Occupancy {
@@ -413,6 +414,16 @@ inline PowKind choose_pow_kind(const ChoiceIn& c) {
     return PowKind::Mfma;
 }
 
+// Does the load policy of X stream some group of this shape, as far as budget, size and kernels decide it?  (The geometry has
+// the last word: choose_x_policy on the splits and chunks that were chosen.)
+inline bool x_streams_by_kernels(const ChoiceIn& c, PowKind pk) {
+    CovGeom cg{};
+    cg.kind = choose_cov_kind(c), cg.tc = kXGroup;
+    PowGeom pg{};
+    pg.kind = pk, pg.tcp = 4;
+    return choose_x_policy(c.x_resident_mb, c.T, c.F, c.M, c.cov_f64, cg, pg).nt;
+}
+
 inline PowGeom choose_pow(const ChoiceIn& c, const Occupancy& occ, int nsplit_req) {
     PowGeom g{};
     g.kind = choose_pow_kind(c);
@@ -446,6 +457,20 @@ inline PowGeom choose_pow(const ChoiceIn& c, const Occupancy& occ, int nsplit_re
         // (at least 32 frames per workgroup: with 64, 2049 x 235 x 8 / 2 ran 3 splits in 16.0 us where 6-8 take 11.9-12.1,
         //  2049 x 160 x 4 / 2 2 splits in 12.0 us where 5-8 take 8.2-8.4)
         nsplit = pick_splits(std::max(n_cu / 2, n_cu * per_cu_x12 / std::max(c.M, 1)), g.nb, T, 32);
+        // The instantiation that STREAMS X (8 channels, two sources per pass): ONE workgroup per CU where the grid can be that.
+        // Its steps are whole 1-KB rows past the L1, so the reasoning above does not carry over, and more requests in flight make
+        // it slower, not faster: 2048 x 4000 x 8 / 2, 268 MB resident, chunks through oiva_plan_set_pow_splits, power stage /
+        // iteration in us: 8 chunks (256 workgroups of 500 frames) 77.6 / 177.9, 10 (1.25 workgroups per CU: the last quarter
+        // runs alone) 89.5 / 191.1, 12: 84.8 / 186.4, 16: 85.0 / 186.7, 20: 85.0 / 187.0, 24: 82.5 / 184.9, 32: 95.4 / 198.0
+        // (profiles/pow_splits_nt.log; the pure-read form says the same of deeper request queues: tools/mallbench.hip rows "e",
+        // DESIGN §7).  Where the cap of tcp or the number of bin batches leaves no grid of 7/8 .. 1 workgroups per CU (2049 bins:
+        // 33 x 8 = 264) the chunks above stay; one source per pass was not measured and keeps them too.
+        if (g.kind == PowKind::Lane && g.kp == 2 && x_streams_by_kernels(c, g.kind)) {
+            const int one = pick_splits(n_cu, g.nb, T, 32);
+            const int tcp1 = std::min(std::max(round_up(ceil_div(T, one), t.quantum), 4), kPowMaxFrames);
+            const long long grid = (long long)g.nb * ceil_div(T, tcp1);
+            if (grid <= n_cu && grid * 8 >= (long long)n_cu * 7) nsplit = one;
+        }
     }
     int tcp = round_up(ceil_div(T, nsplit), t.quantum);
     tcp = std::min(std::max(tcp, 4), kPowMaxFrames);

@@ -159,67 +159,11 @@ __global__ __launch_bounds__(kBlock) void cov_kernel(const float2* __restrict__ 
 // kernel limited to two waves per SIMD by its 128 accumulators needs to cover HBM latency.  Each lane
 // reads back exactly the bytes it requested (piece j of its own M-vector lands at
 // stage_base + j*1024 + lane*16), so the ring needs no swizzle and no workgroup barrier; the only
-// ordering is the wave's own vmcnt.  The LDS reads and both counted waits sit in one asm block:
-// hipcc otherwise drains the whole DMA queue (vmcnt(0)) in front of any LDS read it can see.
+// ordering is the wave's own vmcnt.  The LDS reads and both counted waits sit in one asm block (ring_read,
+// oiva_device.h): hipcc otherwise drains the whole DMA queue (vmcnt(0)) in front of any LDS read it can see.
 // The weights r[t,k] of the wave's four frame phases are wave-uniform and come through the scalar cache.
 // ---------------------------------------------------------------------------------------------
 constexpr int kDmaStages = 4;
-
-template <int PIECES>
-__device__ __forceinline__ void ring_read(unsigned addr, float4 (&v)[PIECES]);
-// the same for a stage that landed row by row (an nt step, XRows in oiva_device.h): the lane's pieces lie side by side
-template <int PIECES>
-__device__ __forceinline__ void ring_read_rows(unsigned addr, float4 (&v)[PIECES]);
-
-template <>
-__device__ __forceinline__ void ring_read<4>(unsigned addr, float4 (&v)[4]) {
-    asm volatile(
-        "s_waitcnt vmcnt(12)\n\t"
-        "ds_read_b128 %0, %4\n\t"
-        "ds_read_b128 %1, %4 offset:1024\n\t"
-        "ds_read_b128 %2, %4 offset:2048\n\t"
-        "ds_read_b128 %3, %4 offset:3072\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
-        : "v"(addr)
-        : "memory");
-}
-template <>
-__device__ __forceinline__ void ring_read<2>(unsigned addr, float4 (&v)[2]) {
-    asm volatile(
-        "s_waitcnt vmcnt(6)\n\t"
-        "ds_read_b128 %0, %2\n\t"
-        "ds_read_b128 %1, %2 offset:1024\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(v[0]), "=&v"(v[1])
-        : "v"(addr)
-        : "memory");
-}
-
-template <>
-__device__ __forceinline__ void ring_read_rows<4>(unsigned addr, float4 (&v)[4]) {
-    asm volatile(
-        "s_waitcnt vmcnt(12)\n\t"
-        "ds_read_b128 %0, %4\n\t"
-        "ds_read_b128 %1, %4 offset:16\n\t"
-        "ds_read_b128 %2, %4 offset:32\n\t"
-        "ds_read_b128 %3, %4 offset:48\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
-        : "v"(addr)
-        : "memory");
-}
-template <>
-__device__ __forceinline__ void ring_read_rows<2>(unsigned addr, float4 (&v)[2]) {
-    asm volatile(
-        "s_waitcnt vmcnt(6)\n\t"
-        "ds_read_b128 %0, %2\n\t"
-        "ds_read_b128 %1, %2 offset:16\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(v[0]), "=&v"(v[1])
-        : "v"(addr)
-        : "memory");
-}
 
 // (tools/build_variant.py ... -DOIVA_COVDMA_TRACE: 100 MHz wall-clock stamps of every workgroup, read by tools/r6/covdma_trace.py)
 #ifdef OIVA_COVDMA_TRACE
@@ -316,9 +260,9 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
         }
         float4 v[PIECES];
         if (plain(i))
-            ring_read<PIECES>(rd_base + s * STAGE * 16, v);
+            ring_read<PIECES, (kDmaStages - 1) * PIECES>(rd_base + s * STAGE * 16, v);
         else
-            ring_read_rows<PIECES>(rd_rows + s * STAGE * 16, v);
+            ring_read_rows<PIECES, (kDmaStages - 1) * PIECES>(rd_rows + s * STAGE * 16, v);
 #if defined(OIVA_COVDMA_ABLATE) && (OIVA_COVDMA_ABLATE & 1)      // variant build (tools/build_variant.py): no arithmetic
         if constexpr (kPacked) {
             if (v[0].x == 12345.f) pacc.add(reinterpret_cast<const v2f(&)[M]>(v), v2f{w[0], w[1]});

@@ -17,10 +17,24 @@ namespace {
 // the X the covariance pass read last and ends on the X it reads first.  Frames are independent of each other (the sums run
 // over bins), so every word of Ppart keeps its place and its bits.  rev == 0: chunk = row, ascending.
 // NT: the instantiation that follows the load policy of X (kernel_choice.h; 8 channels, launched only where some group
-// streams): a load step of a streamed group goes HBM -> LDS row by row with nt loads (XRows, oiva_device.h) and the lane picks
-// its own M-vector up from there -- the registers the arithmetic sees are the same values either way.
+// streams).  Every load step goes HBM -> LDS row by row (XRows, oiva_device.h), a step of a resident group with plain requests, one
+// of a streamed group with nt requests, into a private ring of kPowStages stages per wave: the wave requests step n + 1, waits
+// with a counted vmcnt for step n alone and picks its own M-vector up from there -- the registers the arithmetic sees are the
+// same values as in the plain instantiation.  A wave reads only what it requested itself: no barrier inside the loop.  Steps
+// past the end of the chunk re-request a legal address that is never consumed, so that every step adds the same count to vmcnt.
+// hipcc counts LDS-DMA like any load and drains the queue (vmcnt(0)) in front of every LDS access it can see: the reads of
+// the ring (ring_read_rows) and the store of a step's sums (lds_store) are inline assembly for that reason.
+// Two stages, measured on the pure-read form (tools/mallbench.hip, rows q = "e"): three and four run slower.
 // ---------------------------------------------------------------------------------------------
 constexpr int kPowUnroll = 2;
+constexpr int kPowStages = 2;
+
+// sp[idx] = v out of the compiler's sight (see above); LDS stores of a wave complete in order, the wave waits for them with
+// lds_stores_done() before anyone reads them
+__device__ __forceinline__ void lds_store(float* base, int idx, float v) {
+    asm volatile("ds_write_b32 %0, %1" : : "v"((unsigned)(uintptr_t)base + 4u * (unsigned)idx), "v"(v) : "memory");
+}
+__device__ __forceinline__ void lds_stores_done() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 
 template <int M, int KP, bool NT = false>
 __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict__ X, const float2* __restrict__ What,
@@ -41,66 +55,89 @@ __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict_
     const int t_end = min(T, t_begin + tcp);
     const int len = t_end - t_begin;
     const int nsteps = (len + 3) >> 2;
-    const int ngroups = (nsteps + kPowUnroll - 1) / kPowUnroll;
+    [[maybe_unused]] const int ngroups = (nsteps + kPowUnroll - 1) / kPowUnroll;      // (the plain instantiation's walk)
 
     float wr[KP][M], wi[KP][M];
     load_wconj<M, KP>(What, fc, k0, K, wr, wi);
 
-    // kPowUnroll steps are loaded before any of them is consumed: a wave keeps kPowUnroll * 64 * M * 8
-    // bytes in flight, which is what hides HBM latency here (more resident waves only thrash the L1,
-    // because a lane's M*8 bytes arrive through M/2 separate dwordx4 requests to the same lines).
     const size_t frame_stride = (size_t)F * M;
-    const float2* pbase = X + (size_t)fc * M;
-    // NT: where this chunk starts in its covariance split (a chunk is no longer than a split: choose_x_policy), this lane's
-    // place in a row-contiguous step and in the landed one
-    int off0 = 0, row_off = 0;
-    float4* wrows = nullptr;
+    [[maybe_unused]] const float2* pbase = X + (size_t)fc * M;
     if constexpr (NT) {
-        __shared__ float4 rows[kWaves * kPowUnroll * 32 * M];      // one landed step (64 lanes x M/2 pieces) per step in flight, per wave
-        off0 = t_begin % xctc;
-        row_off = XRows<M>::offset(lane, (blockIdx.x * kWaves + wave) * kBinsPerWave, F);
-        wrows = rows + wave * kPowUnroll * 32 * M;
-    }
-    for (int g = 0; g < ngroups; ++g) {
-        const int i = (rev ? ngroups - 1 - g : g) * kPowUnroll;
-        float xr[kPowUnroll][M], xi[kPowUnroll][M];
-        bool plain[kPowUnroll];
+        constexpr int PIECES = XRows<M>::kPieces, STAGE = PIECES * 64;      // float4 per stage per wave
+        __shared__ float4 ring[kWaves * kPowStages * STAGE];
+        float4* wring = ring + wave * kPowStages * STAGE;                   // wave-uniform
+        // where this chunk starts in its covariance split (a chunk is no longer than a split: choose_x_policy), this lane's
+        // place in a row-contiguous step and in the landed one
+        const int off0 = t_begin % xctc;
+        const int row_off = XRows<M>::offset(lane, (blockIdx.x * kWaves + wave) * kBinsPerWave, F);
+        const unsigned rd_rows = (unsigned)(uintptr_t)wring + XRows<M>::slot(b, q) * 16;
+        auto step_of = [&](int n) { return rev ? nsteps - 1 - n : n; };     // the n-th step of the walk
+        auto issue = [&](int n, int s) {
+            const int i = n < nsteps ? step_of(n) : 0;
+            const int t_lim = n < nsteps ? t_end : 0;                       // past the end: frame T - 1 four times
+            if (x_group_plain(x_split_offset(off0, 4 * i, xctc), xplain))   // wave-uniform
+                XRows<M>::template issue<0>(X, frame_stride, row_off, lane, t_begin + 4 * i, t_lim, T, wring + s * STAGE);
+            else
+                XRows<M>::template issue<2>(X, frame_stride, row_off, lane, t_begin + 4 * i, t_lim, T, wring + s * STAGE);
+        };
+        auto consume = [&](int n, int s) {
+            float4 v[PIECES];
+            ring_read_rows<PIECES, (kPowStages - 1) * PIECES>(rd_rows + s * STAGE * 16, v);
+            float xr[M], xi[M];
 #pragma unroll
-        for (int u = 0; u < kPowUnroll; ++u) {
-            const int tl = 4 * (i + u) + q;
-            const int t = tl < len ? t_begin + tl : T - 1;      // clamped: legal address, result unused
-            plain[u] = !NT || x_group_plain(x_split_offset(off0, 4 * (i + u), xctc), xplain);      // wave-uniform
-            if constexpr (NT) {
-                if (!plain[u]) {
-                    XRows<M>::issue_nt(X, frame_stride, row_off, lane, t_begin + 4 * (i + u), t_end, T, wrows + u * 32 * M);
-                    continue;
-                }
-            }
-            load_x<M>(pbase + (size_t)t * frame_stride, xr[u], xi[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < kPowUnroll; ++u) {
-            const int tl = 4 * (i + u) + q;
-            const bool live = tl < len;
-            if constexpr (NT) {
-                if (!plain[u]) {
-                    // (the compiler waits for the step to land in front of these reads: it counts LDS-DMA like any load)
-                    const float4* v = wrows + u * 32 * M + XRows<M>::slot(b, q);
-#pragma unroll
-                    for (int j = 0; j < M / 2; ++j) {
-                        const float4 p = v[j];
-                        xr[u][2 * j] = p.x, xi[u][2 * j] = p.y, xr[u][2 * j + 1] = p.z, xi[u][2 * j + 1] = p.w;
-                    }
-                }
-            }
+            for (int j = 0; j < PIECES; ++j) xr[2 * j] = v[j].x, xi[2 * j] = v[j].y, xr[2 * j + 1] = v[j].z, xi[2 * j + 1] = v[j].w;
+            const int tl = 4 * step_of(n) + q;
 #pragma unroll
             for (int kk = 0; kk < KP; ++kk) {
                 float yr, yi;
-                demix_one<M>(wr[kk], wi[kk], xr[u], xi[u], yr, yi);
+                demix_one<M>(wr[kk], wi[kk], xr, xi, yr, yi);
                 float pw = fmaf(yr, yr, yi * yi);
                 pw = fvalid ? pw : 0.f;
                 pw = row16_sum(pw);
-                if (b == 0 && live) sp[(wave * tcp + tl) * KP + kk] = pw;
+                if (b == 0 && tl < len) lds_store(sp, (wave * tcp + tl) * KP + kk, pw);
+            }
+        };
+        static_assert(kPowStages == 2, "the loop is unrolled over the stages by hand");
+        // (W has arrived before the first request leaves: with loads of registers still counted at the head of the loop hipcc
+        //  drains the queue there, first step included)
+#pragma unroll
+        for (int kk = 0; kk < KP; ++kk)
+#pragma unroll
+            for (int m = 0; m < M; ++m) asm volatile("" : "+v"(wr[kk][m]), "+v"(wi[kk][m]));
+        issue(0, 0);
+        int n = 0;
+        for (; n + 2 <= nsteps; n += 2) {       // stage indices are compile-time constants in the unrolled body
+            issue(n + 1, 1); consume(n, 0);
+            issue(n + 2, 0); consume(n + 1, 1);
+        }
+        if (n < nsteps) { issue(n + 1, 1); consume(n, 0); }
+        lds_stores_done();
+    } else {
+        // kPowUnroll steps are loaded before any of them is consumed: a wave keeps kPowUnroll * 64 * M * 8
+        // bytes in flight, which is what hides HBM latency here (more resident waves only thrash the L1,
+        // because a lane's M*8 bytes arrive through M/2 separate dwordx4 requests to the same lines).
+        for (int g = 0; g < ngroups; ++g) {
+            const int i = (rev ? ngroups - 1 - g : g) * kPowUnroll;
+            float xr[kPowUnroll][M], xi[kPowUnroll][M];
+#pragma unroll
+            for (int u = 0; u < kPowUnroll; ++u) {
+                const int tl = 4 * (i + u) + q;
+                const int t = tl < len ? t_begin + tl : T - 1;      // clamped: legal address, result unused
+                load_x<M>(pbase + (size_t)t * frame_stride, xr[u], xi[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < kPowUnroll; ++u) {
+                const int tl = 4 * (i + u) + q;
+                const bool live = tl < len;
+#pragma unroll
+                for (int kk = 0; kk < KP; ++kk) {
+                    float yr, yi;
+                    demix_one<M>(wr[kk], wi[kk], xr[u], xi[u], yr, yi);
+                    float pw = fmaf(yr, yr, yi * yi);
+                    pw = fvalid ? pw : 0.f;
+                    pw = row16_sum(pw);
+                    if (b == 0 && live) sp[(wave * tcp + tl) * KP + kk] = pw;
+                }
             }
         }
     }

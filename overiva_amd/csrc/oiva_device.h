@@ -87,17 +87,78 @@ struct XRows {
     }
     // float4 index of lane (b, q)'s first piece in the landed step
     static __device__ __forceinline__ int slot(int b, int q) { return (q * 16 + b) * kPieces; }
-    // request the step whose frames are t0 .. t0 + 3 into `stage` (wave-uniform); frames >= t_lim re-request frame T - 1
-    static __device__ __forceinline__ void issue_nt(const float2* __restrict__ X, size_t frame_stride, int off, int lane, int t0, int t_lim,
-                                                    int T, float4* stage) {
+    // request the step whose frames are t0 .. t0 + 3 into `stage` (wave-uniform); frames >= t_lim re-request frame T - 1.
+    // AUX: the cache policy bits of the instruction (0 plain, 2 nt)
+    template <int AUX>
+    static __device__ __forceinline__ void issue(const float2* __restrict__ X, size_t frame_stride, int off, int lane, int t0, int t_lim, int T,
+                                                 float4* stage) {
 #pragma unroll
         for (int j = 0; j < kPieces; ++j) {
             const int t = t0 + frame(lane, j);
             const float2* src = X + (size_t)(t < t_lim ? t : T - 1) * frame_stride + off;
-            __builtin_amdgcn_global_load_lds((gvoid_t*)src, (lvoid_t*)(stage + j * 64), 16, 0, /*aux: nt*/ 2);
+            __builtin_amdgcn_global_load_lds((gvoid_t*)src, (lvoid_t*)(stage + j * 64), 16, 0, AUX);
         }
     }
+    static __device__ __forceinline__ void issue_nt(const float2* __restrict__ X, size_t frame_stride, int off, int lane, int t0, int t_lim,
+                                                    int T, float4* stage) {
+        issue<2>(X, frame_stride, off, lane, t0, t_lim, T, stage);
+    }
 };
+
+// ---- a lane's read of its own M-vector from a stage of a per-wave LDS-DMA ring (cov_dma_kernel, the streamed power_kernel) ----
+// The counted wait and the LDS reads sit in one asm block: hipcc counts LDS-DMA like any load and drains the whole queue
+// (vmcnt(0)) in front of any LDS access it can see.  INFLIGHT = the requests that may stay outstanding: those of the steps issued
+// behind the one that is read (every step issues PIECES of them).
+// ring_read: a stage that landed lane by lane (piece j of the lane's vector at stage + j * 1024 + lane * 16);
+// ring_read_rows: one that landed row by row (XRows): the lane's pieces lie side by side.
+template <int PIECES, int INFLIGHT>
+__device__ __forceinline__ void ring_read(unsigned addr, float4 (&v)[PIECES]) {
+    static_assert(PIECES == 2 || PIECES == 4, "M in {4, 8}");
+    if constexpr (PIECES == 4)
+        asm volatile(
+            "s_waitcnt vmcnt(%5)\n\t"
+            "ds_read_b128 %0, %4\n\t"
+            "ds_read_b128 %1, %4 offset:1024\n\t"
+            "ds_read_b128 %2, %4 offset:2048\n\t"
+            "ds_read_b128 %3, %4 offset:3072\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
+            : "v"(addr), "n"(INFLIGHT)
+            : "memory");
+    else
+        asm volatile(
+            "s_waitcnt vmcnt(%3)\n\t"
+            "ds_read_b128 %0, %2\n\t"
+            "ds_read_b128 %1, %2 offset:1024\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(v[0]), "=&v"(v[1])
+            : "v"(addr), "n"(INFLIGHT)
+            : "memory");
+}
+template <int PIECES, int INFLIGHT>
+__device__ __forceinline__ void ring_read_rows(unsigned addr, float4 (&v)[PIECES]) {
+    static_assert(PIECES == 2 || PIECES == 4, "M in {4, 8}");
+    if constexpr (PIECES == 4)
+        asm volatile(
+            "s_waitcnt vmcnt(%5)\n\t"
+            "ds_read_b128 %0, %4\n\t"
+            "ds_read_b128 %1, %4 offset:16\n\t"
+            "ds_read_b128 %2, %4 offset:32\n\t"
+            "ds_read_b128 %3, %4 offset:48\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
+            : "v"(addr), "n"(INFLIGHT)
+            : "memory");
+    else
+        asm volatile(
+            "s_waitcnt vmcnt(%3)\n\t"
+            "ds_read_b128 %0, %2\n\t"
+            "ds_read_b128 %1, %2 offset:16\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(v[0]), "=&v"(v[1])
+            : "v"(addr), "n"(INFLIGHT)
+            : "memory");
+}
 
 // ---- fp32 / fp64 matrix-core tile of shape 16x16x4 (A, B: one value per lane; C/D: 4 values per lane) ----
 using f32x4 = __attribute__((ext_vector_type(4))) float;

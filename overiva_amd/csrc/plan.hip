@@ -54,6 +54,7 @@ struct oiva_plan {
     bool cov_hmfma_on = true;     // oiva_plan_set_cov_hmfma ($OIVA_COV_HMFMA=0: off)
     bool fuse_cov_update = false; // oiva_plan_set_fuse_cov_update ($OIVA_COV_UPDATE=1: on wherever the shape qualifies)
     int power_reverse = 1;        // oiva_plan_set_power_reverse ($OIVA_POWER_REVERSE=0: off): the power pass walks X against the covariance pass; 2: and takes its chunks tail first even in a grid of one round
+    int pow_splits_req = 0;                       // oiva_plan_set_pow_splits (0: the rule's own count), kept for the choices that follow it
     double x_resident_mb = kXResidentDefaultMB;   // oiva_plan_set_x_resident_mb ($OIVA_X_RESIDENT_MB; <= 0: off): how much of X the two streaming passes keep in the Infinity Cache (XPolicy, kernel_choice.h)
     CovGeom stg{};              // geometry of the projection-back statistics pass (16-bin groups, independent of cov)
     PowGeom pw{};
@@ -140,6 +141,7 @@ ChoiceIn choice_in(const oiva_plan* p) {
     c.cov_quad_on = p->cov_quad_on, c.cov_hmfma_on = p->cov_hmfma_on;
     c.part32 = pv && pv[0] == '1';
     c.kc_wide = kc_wide, c.power_lds = power_lds;
+    c.x_resident_mb = p->x_resident_mb;
     return c;
 }
 // the device's answers (< 1: the query failed); asked[0] / asked[1] (may be nullptr) receive what each query returned
@@ -160,7 +162,10 @@ Occupancy device_occupancy(int* asked = nullptr) {
     return o;
 }
 void choose_cov_geom(oiva_plan* p, int nsplit_req) { p->cov = choose_cov(choice_in(p), device_occupancy(), nsplit_req); }
-void choose_pow_geom(oiva_plan* p, int nsplit_req) { p->pw = choose_pow(choice_in(p), device_occupancy(), nsplit_req); }
+void choose_pow_geom(oiva_plan* p, int nsplit_req) {
+    p->pow_splits_req = nsplit_req;
+    p->pw = choose_pow(choice_in(p), device_occupancy(), nsplit_req);
+}
 
 void choose_stats_geom(oiva_plan* p) {
     CovGeom g;
@@ -1232,7 +1237,8 @@ int oiva_plan_set_power_reverse(oiva_plan* p, int enable) {
 int oiva_plan_set_x_resident_mb(oiva_plan* p, double mb) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     OIVA_NEED(mb == mb, OIVA_ERR_ARG, "the budget is not a number");
-    return change_geometry(p, [&] { p->x_resident_mb = mb; return OIVA_OK; });
+    // (where X streams the power pass takes other chunks: choose_pow)
+    return change_geometry(p, [&] { p->x_resident_mb = mb; choose_pow_geom(p, p->pow_splits_req); return OIVA_OK; });
 }
 
 int oiva_plan_get_x_resident(oiva_plan* p, int* n16, int* nt, int* reason) {
@@ -1266,6 +1272,7 @@ int oiva_plan_set_precision(oiva_plan* p, int flags) {
         const bool cov_changed = ((flags ^ p->prec) & (OIVA_PREC_COV_F64 | (traits(p->cov.kind).update_arith ? OIVA_PREC_UPDATE_F64 : 0))) != 0;
         p->prec = flags;
         if (cov_changed) choose_cov_geom(p, 0);            // sources per pass and residency depend on the accumulator type
+        if (cov_changed) choose_pow_geom(p, p->pow_splits_req);      // ... and whether X streams, which the power chunks follow
         return (int)OIVA_OK;
     });
 }

@@ -20,9 +20,18 @@
 //   q = "c": nt against plain for the whole buffer, no share; nt lane-strided and row-contiguous
 //   q = "a": is the share still there in the later passes?  share swept, layout first, rest nt against rest plain, both kernels
 //   q = "b": interleaved against share-first, and the two kernels alternating as in an iteration (kern = "pair")
+//   q = "e": the power pass through a per-wave RING of S stages of 4 KB (S = 2, 3, 4; "addr": "ring", "stages": S) with counted
+//            vmcnt, as the covariance kernel streams: every wave keeps S - 1 steps in flight all the time, where the landing-area
+//            form above loads two steps, waits for both and consumes both.  Chunks walked from their last step to their first, as
+//            the kernel does when the pass runs against the covariance pass.  Streamed groups row-contiguous nt; resident groups
+//            "plain_addr": "lane" (lane-addressed plain global_load_lds, the covariance kernel's plain step) or "row"
+//            (row-contiguous plain).  Shares 0 and 268 MB interleaved, the pass alone and the two passes alternating; the
+//            `pow ... addr row` rows of the same shares are repeated beside them as the yardstick of the same run.  Then the same
+//            in 8 chunks of 500 frames (one workgroup per CU), and X of one shard of two and of four (262 and 131 MB, all plain,
+//            384 workgroups): register loads against the ring.
 //   q = "d": (the program's first question, docs/HISTORY_rounds_1-3.md §3.1) buffers of 128 .. 500 MiB streamed by 2048 concurrent
 //            workgroups, every pass in the same direction against passes of alternating direction
-// No step waits on anything but its own kernels; the whole sweep is about 110 rows of 7 launches of < 0.2 ms (1-2 s of GPU time
+// No step waits on anything but its own kernels; the whole sweep is about 170 rows of 7 launches of < 0.2 ms (1-2 s of GPU time
 // behind 1.1 GB of allocations).  Run it under a time limit:
 //
 //   hipcc -O3 --offload-arch=gfx950 tools/mallbench.hip -o mallbench && timeout -k 10 120 ./mallbench > profiles/mallbench.log
@@ -56,6 +65,8 @@ struct Policy {
     int nfirst;   // layout first (>= 0): groups g < nfirst of every split are resident; -1: layout il
     int rest_nt;  // streamed groups: 1 nt loads, 0 plain loads
     int contig;   // 1: nt steps row-contiguous through LDS
+    int ring;     // pow: 0 the landing-area form, S = 2..4 a ring of S stages per wave
+    int rowplain; // ring: 1 plain steps row-contiguous too, 0 lane-addressed
 };
 struct Shape {
     int T, F;
@@ -199,6 +210,85 @@ __global__ __launch_bounds__(256) void pow_stream(const char* __restrict__ X, fl
     if (acc.x + acc.y + acc.z + acc.w == 12345.678f) out[0] = acc.x;
 }
 
+// ---- the power pass's stream through a ring: S stages of 4 KB per wave, S - 1 steps in flight, counted vmcnt ----
+template <int S>
+__global__ __launch_bounds__(256) void pow_ring(const char* __restrict__ X, float* out, Shape sh, Policy p) {
+    extern __shared__ __attribute__((aligned(16))) float4 pring[];      // [4 waves][S][256]
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int f0 = (blockIdx.x * 4 + wave) * 16;
+    const int t_begin = blockIdx.y * sh.tc;
+    const int t_end = min(sh.T, t_begin + sh.tc);
+    const int nsteps = (t_end - t_begin + 3) >> 2;
+    float4* wring = pring + wave * S * 256;
+    const unsigned rd_base = (unsigned)(uintptr_t)wring + lane * 16;
+    const unsigned rd_rows = (unsigned)(uintptr_t)wring + ((lane >> 4) * 16 + (lane & 15)) * 64;
+    // walk position n -> step nsteps - 1 - n (descending); positions past the end re-request frame T - 1, never consumed
+    auto t0_of = [&](int n) { return t_begin + 4 * (nsteps - 1 - n); };
+    auto plain = [&](int n) { return resident(p, min(t0_of(n), sh.T - 1)) || !p.rest_nt; };
+    auto issue = [&](int n, int s) {
+        const bool past = n >= nsteps;
+        const int t0 = past ? sh.T : t0_of(n);
+        if (past || !plain(n)) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                __builtin_amdgcn_global_load_lds((gvoid_t*)piece(X, sh, true, t0, t_end, f0, lane, j), (lvoid_t*)(wring + s * 256 + j * 64), 16, 0, 2);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                __builtin_amdgcn_global_load_lds((gvoid_t*)piece(X, sh, p.rowplain, t0, t_end, f0, lane, j), (lvoid_t*)(wring + s * 256 + j * 64), 16, 0, 0);
+        }
+    };
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto consume = [&](int n, int s) {
+        float4 v0, v1, v2, v3;
+        if (!plain(n) || p.rowplain)
+            asm volatile(
+                "s_waitcnt vmcnt(%5)\n\t"
+                "ds_read_b128 %0, %4\n\t"
+                "ds_read_b128 %1, %4 offset:16\n\t"
+                "ds_read_b128 %2, %4 offset:32\n\t"
+                "ds_read_b128 %3, %4 offset:48\n\t"
+                "s_waitcnt lgkmcnt(0)"
+                : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
+                : "v"(rd_rows + s * 4096), "n"((S - 1) * 4)
+                : "memory");
+        else
+            asm volatile(
+                "s_waitcnt vmcnt(%5)\n\t"
+                "ds_read_b128 %0, %4\n\t"
+                "ds_read_b128 %1, %4 offset:1024\n\t"
+                "ds_read_b128 %2, %4 offset:2048\n\t"
+                "ds_read_b128 %3, %4 offset:3072\n\t"
+                "s_waitcnt lgkmcnt(0)"
+                : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
+                : "v"(rd_base + s * 4096), "n"((S - 1) * 4)
+                : "memory");
+        acc.x += v0.x + v1.x + v2.x + v3.x;
+        acc.y += v0.y + v1.y + v2.y + v3.y;
+        acc.z += v0.z + v1.z + v2.z + v3.z;
+        acc.w += v0.w + v1.w + v2.w + v3.w;
+    };
+#pragma unroll
+    for (int u = 0; u < S - 1; ++u) issue(u, u);
+    int n = 0;
+    for (; n + S <= nsteps; n += S) {
+#pragma unroll
+        for (int u = 0; u < S; ++u) {      // stage indices are compile-time constants in the unrolled body
+            issue(n + u + S - 1, (u + S - 1) % S);
+            consume(n + u, u);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < S - 1; ++u)
+        if (n + u < nsteps) {
+            issue(n + u + S - 1, (u + S - 1) % S);
+            consume(n + u, u);
+        }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (acc.x + acc.y + acc.z + acc.w == 12345.678f) out[0] = acc.x;
+}
+
 // the resident share alone, once, with plain loads: one wave per 1-KB row
 __global__ __launch_bounds__(256) void prime(const char* __restrict__ X, float* out, Shape sh, Policy p) {
     const int lane = threadIdx.x & 63;
@@ -233,7 +323,7 @@ struct Bench {
     Shape cov, pow;
     char *X = nullptr, *other = nullptr;
     float* out = nullptr;
-    size_t bytes = 0;
+    size_t bytes = 0, flush_bytes = 0;      // of X as the rows read it; of the buffer whose memset flushes the cache
     hipEvent_t ev[kPasses + 1];
 
     double share_mb(const Policy& p) const {
@@ -248,11 +338,17 @@ struct Bench {
         const bool c = !strcmp(kern, "cov") || (!strcmp(kern, "pair") && (n & 1));      // pair: power, covariance, power, ...
         if (c)
             cov_stream<<<dim3(cov.F / 16, (cov.T + cov.tc - 1) / cov.tc), 256>>>(X, out, cov, p);
-        else
+        else if (p.ring == 0)
             pow_stream<<<dim3(pow.F / 64, (pow.T + pow.tc - 1) / pow.tc), 256>>>(X, out, pow, p);
+        else {
+            const dim3 grid(pow.F / 64, (pow.T + pow.tc - 1) / pow.tc);
+            if (p.ring == 2) pow_ring<2><<<grid, 256, 2 * 16384>>>(X, out, pow, p);
+            if (p.ring == 3) pow_ring<3><<<grid, 256, 3 * 16384>>>(X, out, pow, p);
+            if (p.ring == 4) pow_ring<4><<<grid, 256, 4 * 16384>>>(X, out, pow, p);
+        }
     }
     void row(const char* q, const char* kern, Policy p) {
-        CHECK(hipMemsetAsync(other, 0x3c, bytes));
+        CHECK(hipMemsetAsync(other, 0x3c, flush_bytes));
         if (share_mb(p) > 0.) prime<<<1024, 256>>>(X, out, cov, p);
         for (int n = 0; n < kPasses; ++n) {
             CHECK(hipEventRecord(ev[n]));
@@ -270,8 +366,11 @@ struct Bench {
         std::copy(us + 2, us + kPasses, tail);
         std::sort(tail, tail + kPasses - 2);
         const double steady = 0.5 * (tail[(kPasses - 2) / 2 - 1] + tail[(kPasses - 2) / 2]);
-        printf("{\"q\": \"%s\", \"kern\": \"%s\", \"layout\": \"%s\", \"rest\": \"%s\", \"addr\": \"%s\", \"share_mb\": %.1f, \"pass_us\": [", q, kern,
-               p.nfirst >= 0 ? "first" : "il", p.rest_nt ? "nt" : "plain", p.contig ? "row" : "lane", share_mb(p));
+        printf("{\"q\": \"%s\", \"kern\": \"%s\", \"layout\": \"%s\", \"rest\": \"%s\", \"addr\": \"%s\", ", q, kern, p.nfirst >= 0 ? "first" : "il",
+               p.rest_nt ? "nt" : "plain", p.ring ? "ring" : (p.contig ? "row" : "lane"));
+        if (p.ring) printf("\"stages\": %d, \"plain_addr\": \"%s\", ", p.ring, p.rowplain ? "row" : "lane");
+        if (!strcmp(q, "e")) printf("\"x_mb\": %.0f, \"tcp\": %d, ", (double)bytes / 1e6, pow.tc);
+        printf("\"share_mb\": %.1f, \"pass_us\": [", share_mb(p));
         for (int n = 0; n < kPasses; ++n) printf("%s%.1f", n ? ", " : "", us[n]);
         printf("], \"steady_us\": %.1f, \"steady_tbps\": %.2f}\n", steady, (double)bytes / steady / 1e6);
         fflush(stdout);
@@ -283,7 +382,8 @@ int main() {
     const int T = 4000, F = 2048;
     b.cov = Shape{T, F, 1008};      // headline geometry: 4 covariance splits, 12 power chunks of 336 frames
     b.pow = Shape{T, F, 336};
-    b.bytes = (size_t)T * F * kM8;
+    b.bytes = b.flush_bytes = (size_t)T * F * kM8;
+    CHECK(hipFuncSetAttribute((const void*)pow_ring<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 16384));
     CHECK(hipMalloc(&b.X, b.bytes));
     CHECK(hipMalloc(&b.other, b.bytes));
     CHECK(hipMalloc(&b.out, 4));
@@ -313,6 +413,35 @@ int main() {
             b.row("b", kerns[k], Policy{ctc, n16, -1, 1, 1});
             if (n16 > 0) b.row("b", kerns[k], Policy{ctc, 0, (n16 * groups + 8) / 16, 1, 1});
         }
+    // (e) the power pass through a ring of S stages per wave, beside the landing-area rows of the same run
+    for (int n16 : {0, 8})
+        for (int k = 1; k < 3; ++k) {
+            b.row("e", kerns[k], Policy{ctc, n16, -1, 1, 1});
+            for (int S = 2; S <= 4; ++S)
+                for (int rowplain = 0; rowplain < (n16 ? 2 : 1); ++rowplain) b.row("e", kerns[k], Policy{ctc, n16, -1, 1, 1, S, rowplain});
+            b.row("e", kerns[k], Policy{ctc, n16, -1, 1, 1});
+        }
+    // ... and in 8 chunks of 500 frames: 256 workgroups, one per CU
+    b.pow = Shape{T, F, 500};
+    for (int k = 1; k < 3; ++k) {
+        b.row("e", kerns[k], Policy{ctc, 8, -1, 1, 1});
+        for (int S = 2; S <= 4; ++S) b.row("e", kerns[k], Policy{ctc, 8, -1, 1, 1, S, 1});
+        b.row("e", kerns[k], Policy{ctc, 8, -1, 1, 1});
+    }
+    b.pow = Shape{T, F, 336};
+    // X of one shard of two and of four, all plain, the chip's 384 workgroups: register loads against the ring
+    for (int shards : {2, 4}) {
+        b.pow = Shape{T, F / shards, 336 / shards};
+        b.cov = Shape{T, F / shards, 1008};
+        b.bytes = (size_t)T * (F / shards) * kM8;
+        b.row("e", "pow", Policy{ctc, 0, -1, 0, 0});
+        for (int S = 2; S <= 4; ++S)
+            for (int rowplain = 0; rowplain < 2; ++rowplain) b.row("e", "pow", Policy{ctc, 0, -1, 0, 0, S, rowplain});
+        b.row("e", "pow", Policy{ctc, 0, -1, 0, 0});
+    }
+    b.pow = Shape{T, F, 336};
+    b.cov = Shape{T, F, 1008};
+    b.bytes = b.flush_bytes;
     // (d) same direction against alternating direction
     for (size_t mb : {128, 256, 384, 500}) {      // MiB, up to X's size
         const size_t bytes = mb << 20, chunk4 = bytes / 16 / 2048 / 1024 * 1024;
