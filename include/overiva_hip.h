@@ -656,6 +656,50 @@ oiva_status oiva_room_mix(oiva_room *p, int g0, int K, double sinr, double snr, 
 oiva_status oiva_room_get_mix(oiva_room *p, int g0, double *mix_host_packed, double *ref_host_packed);
 oiva_status oiva_room_time_stages(oiva_room *p, int n, int K, double sinr, double snr, int ref_mic, float *per_stage_ms);
 
+/*
+ * One step of the Monte-Carlo sweep with every hand-over on the device (sweep.hip, kernels_sweep.hip; DESIGN.md 3.12;
+ * overiva_amd/sweep.py, sweep_batch): the mix of an oiva_room group goes into the batched STFT without leaving the device, and
+ * the synthesis of a solver's Y goes into an oiva_bsseval handle's ref and est without leaving it.
+ *   oiva_bstft_analysis_dev   : oiva_bstft_analysis with the packed (sum n_b, M) audio already on the device: float32 (f64 = 0, a
+ *                               device-to-device copy) or float64 (f64 = 1, cast to float32 round-to-nearest-even, what
+ *                               ndarray.astype(float32) does); the "upload" phase of oiva_bstft_phase_ms times that step
+ *   oiva_bstft_synthesis_keep : oiva_bstft_synthesis_dev without the download: *y_dev is the handle's packed (sum T_b hop, K)
+ *                               float32 audio, valid until the next call on the handle; the "download" phase reads 0
+ * One oiva_sweep handle = the rooms of one group of an oiva_room: B, their output lengths n_out[b], M microphones (1..8), K
+ * targets (1..min(M, 7)), (frame, hop) of the STFT, ref_mic and the filter_length of the evaluation.  Of room b the samples
+ * [0, m_b), m_b = T_b hop - (frame - hop), T_b = n_out[b] / hop, are evaluated; m_b < 1 is refused (OIVA_ERR_ARG naming the room).
+ *   oiva_sweep_set_filler : packed (sum m_b) float64: row K of every room's estimates, what is held against the background
+ *   oiva_sweep_take_mix   : group g0 of `room` must be mixed (OIVA_ERR_STATE otherwise) with K targets and be this handle's rooms;
+ *                           runs oiva_bstft_analysis_dev on its float64 mix where it lies and remembers where its ref lies;
+ *                           *X_dev as oiva_bstft_analysis.  No audio crosses to the host
+ *   oiva_sweep_evaluate   : Y_dev (sum T_b, F, C) complex64, K <= C <= M: oiva_bstft_synthesis_keep; the population standard
+ *                           deviation of every channel over all T_b hop samples (float64, two passes); order = the channels by
+ *                           descending standard deviation, ties to the lower index (reorder = 0: the identity); then, into the
+ *                           device buffers of `bsseval` (created with N = K + 1, lengths m_b and this filter_length):
+ *                             est[b, k, i] = y[b, i, order[b, k]] (k < K), est[b, K, i] = filler[b, i],
+ *                             ref[b, j, i] = room_ref[b, j, i, ref_mic] (j <= K)
+ *                           exact gathers; the handle is left as after oiva_bsseval_set_signals, the caller runs
+ *                           oiva_bsseval_run.  filler_dev: NULL (the handle's own) or packed (sum m_b) float64 on the device
+ *   oiva_sweep_phase_ms   : device ms of the kernels of the last evaluate behind its synthesis
+ *   oiva_sweep_get_order  : test hook: order and std of the last evaluate, (B, C) each
+ *   oiva_sweep_get_signals: test hook: the packed ref and est the last evaluate left in `bsseval`
+ * Every entry checks its arguments before any device call and is synchronous.  The room handle must stay alive and its group
+ * mixed between take_mix and the last evaluate.
+ */
+typedef struct oiva_sweep oiva_sweep;
+oiva_status oiva_bstft_analysis_dev(oiva_bstft *p, const void *x_dev, int f64, void **X_dev);
+oiva_status oiva_bstft_synthesis_keep(oiva_bstft *p, const void *Y_dev, int K, void **y_dev);
+oiva_status oiva_sweep_create(oiva_sweep **out, int device, int B, const int *n_out, int M, int K, int frame, int hop, int ref_mic,
+                              int filter_length, void *stream);
+oiva_status oiva_sweep_destroy(oiva_sweep *p);
+oiva_status oiva_sweep_set_filler(oiva_sweep *p, const double *filler_host_packed);
+oiva_status oiva_sweep_take_mix(oiva_sweep *p, oiva_room *room, int g0, oiva_bstft *bstft, void **X_dev);
+oiva_status oiva_sweep_evaluate(oiva_sweep *p, oiva_bstft *bstft, const void *Y_dev, int C, int reorder, oiva_bsseval *bsseval,
+                                const double *filler_dev);
+oiva_status oiva_sweep_phase_ms(oiva_sweep *p, float *ms);
+oiva_status oiva_sweep_get_order(oiva_sweep *p, int *order, double *std);
+oiva_status oiva_sweep_get_signals(oiva_sweep *p, oiva_bsseval *bsseval, double *ref_host_packed, double *est_host_packed);
+
 #ifdef __cplusplus
 }
 #endif

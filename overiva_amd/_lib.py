@@ -175,6 +175,16 @@ SIGNATURES = {
     "oiva_room_mix": [_vp, _i, _i, C.c_double, C.c_double, _i, _vp, _vp],
     "oiva_room_get_mix": [_vp, _i, _vp, _vp],
     "oiva_room_time_stages": [_vp, _i, _i, C.c_double, C.c_double, _i, _fp],
+    "oiva_bstft_analysis_dev": [_vp, _vp, _i, C.POINTER(_vp)],
+    "oiva_bstft_synthesis_keep": [_vp, _vp, _i, C.POINTER(_vp)],
+    "oiva_sweep_create": [C.POINTER(_vp), _i, _i, C.POINTER(_i), _i, _i, _i, _i, _i, _i, _vp],
+    "oiva_sweep_destroy": [_vp],
+    "oiva_sweep_set_filler": [_vp, _vp],
+    "oiva_sweep_take_mix": [_vp, _vp, _i, _vp, C.POINTER(_vp)],
+    "oiva_sweep_evaluate": [_vp, _vp, _vp, _i, _i, _vp, _vp],
+    "oiva_sweep_phase_ms": [_vp, _fp],
+    "oiva_sweep_get_order": [_vp, C.POINTER(_i), _vp],
+    "oiva_sweep_get_signals": [_vp, _vp, _vp, _vp],
 }
 
 

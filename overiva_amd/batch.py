@@ -36,7 +36,8 @@ def last_batch_info():
     ``ilrma_batch()`` also ``algorithm`` ("ilrma") and ``n_components``; after
     ``overiva_batch_ragged()`` also ``ragged`` (True) and ``frames`` (B ints), ``shape`` then holding the largest T; after
     ``bss_eval_batch()`` ``algorithm`` ("bss_eval"), ``batched``, ``n_sources``, ``filter_length`` and, for rooms of different
-    lengths, ``ragged`` (True) and ``lengths`` (B ints)"""
+    lengths, ``ragged`` (True) and ``lengths`` (B ints); after ``sweep_batch()`` ``algorithm`` ("sweep"), ``batched``,
+    ``rooms_per_group``, ``groups`` (the group sizes), ``algorithms`` (the entries that ran) and ``phase_ms``"""
     return dict(_info)
 
 

@@ -109,6 +109,19 @@ int read_flags(oiva_bsseval* p, std::vector<int>& st) {
 
 }  // namespace
 
+// the sweep's view of the handle (sweep.hip): it writes ref and est on the device instead of oiva_bsseval_set_signals
+void oiva::bsseval_signal_view(oiva_bsseval* p, BssSignalView* view, int* lengths, int max_rooms) {
+    view->device = p->device, view->B = p->B, view->N = p->N, view->Lf = p->Lf;
+    view->sig_total = p->sig_total;
+    view->ref = p->ref, view->est = p->est;
+    for (int b = 0; b < p->B && b < max_rooms; ++b) lengths[b] = p->rooms[b].n;
+}
+void oiva::bsseval_mark_signals(oiva_bsseval* p) {
+    p->have_sig = true;
+    p->have_result = false;
+    p->done = -1;
+}
+
 extern "C" {
 
 oiva_status oiva_bsseval_create(oiva_bsseval** out, int device, int B, const int* n_samples, int N, int filter_length, int diag_only,

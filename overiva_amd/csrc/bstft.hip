@@ -7,6 +7,8 @@
 //              upload | framing + window | R2C | (frame * M + c, F) -> (frame, F, M)
 //   synthesis: Y (sum T_b, F, K) complex64, device  ->  packed y (sum T_b * hop, K) float32, host
 //              (frame, F, K) -> (frame * K + c, F) | C2R | overlap-add per room | download
+// oiva_bstft_analysis_dev starts from audio already on the device (a copy, or a cast from float64, in place of the upload) and
+// oiva_bstft_synthesis_keep ends before the download: the handle's packed audio stays where it is (the sweep, sweep.hip).
 // Every call is synchronous; events around every phase are kept for oiva_bstft_phase_ms.
 #include <hipfft/hipfft.h>
 
@@ -44,7 +46,65 @@ struct oiva_bstft {
     float2* spec = nullptr;   // (frames_total * M, F)
     float2* X = nullptr;      // (frames_total, F, M)
     bool timed_a = false, timed_s = false;
+    bool kept_s = false;      // the last synthesis left its audio on the device: its download phase reads 0
 };
+
+namespace {
+
+// the analysis behind whatever fills the handle's packed audio x (`fill`: an upload, a device copy or a cast, on the stream)
+template <class Fill>
+int analysis_from(oiva_bstft* p, void** X_dev, Fill&& fill) {
+    const int M = p->M, L = p->L, F = p->F;
+    if (!p->have_fwd) {
+        int n[1] = {L};
+        OIVA_TRY_FFT(hipfftPlanMany(&p->fwd, 1, n, nullptr, 1, L, nullptr, 1, F, HIPFFT_R2C, (int)(p->frames_total * M)));
+        OIVA_TRY_FFT(hipfftSetStream(p->fwd, p->stream));
+        p->have_fwd = true;
+    }
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[0], p->stream));
+    OIVA_TRY_HIP(fill());
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[1], p->stream));
+    OIVA_TRY_HIP(launch_bstft_frame(p->stream, p->x, p->win_a, p->frames, p->rooms_dev, p->B, p->frames_total, M, L, p->hop));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[2], p->stream));
+    OIVA_TRY_FFT(hipfftExecR2C(p->fwd, p->frames, reinterpret_cast<hipfftComplex*>(p->spec)));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[3], p->stream));
+    OIVA_TRY_HIP(launch_bstft_to_tfc(p->stream, p->spec, p->X, p->frames_total, F, M));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[4], p->stream));
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+    p->timed_a = true;
+    *X_dev = p->X;
+    return OIVA_OK;
+}
+
+// the synthesis up to the packed (frames_total * hop, K) audio in the handle's x; events 5..8 recorded, nothing waited for
+int synthesis_to_x(oiva_bstft* p, const void* Y_dev, int K) {
+    const int L = p->L, F = p->F;
+    // one inverse plan per channel count (the solver returns fewer channels than the analysis had)
+    if (!p->have_inv || p->inv_chan != K) {
+        if (p->have_inv) OIVA_TRY_FFT(hipfftDestroy(p->inv));
+        p->have_inv = false;
+        int n[1] = {L};
+        OIVA_TRY_FFT(hipfftPlanMany(&p->inv, 1, n, nullptr, 1, F, nullptr, 1, L, HIPFFT_C2R, (int)(p->frames_total * K)));
+        OIVA_TRY_FFT(hipfftSetStream(p->inv, p->stream));
+        p->have_inv = true;
+        p->inv_chan = K;
+    }
+    const long long n_out = p->frames_total * p->hop;
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[5], p->stream));
+    OIVA_TRY_HIP(launch_bstft_from_tfc(p->stream, static_cast<const float2*>(Y_dev), p->spec, p->frames_total, F, K));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[6], p->stream));
+    OIVA_TRY_FFT(hipfftExecC2R(p->inv, reinterpret_cast<hipfftComplex*>(p->spec), p->frames));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[7], p->stream));
+    OIVA_TRY_HIP(launch_bstft_overlap_add(p->stream, p->frames, p->win_s, p->x, p->rooms_dev, p->B, n_out, K, L, p->hop));
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[8], p->stream));
+    return OIVA_OK;
+}
+
+}  // namespace
+
+void oiva::bstft_dims(oiva_bstft* p, int* device, int* B, int* M, int* frame, int* hop, long long* samples_total) {
+    *device = p->device, *B = p->B, *M = p->M, *frame = p->L, *hop = p->hop, *samples_total = p->samples_total;
+}
 
 extern "C" {
 
@@ -130,25 +190,32 @@ oiva_status oiva_bstft_shape(oiva_bstft* p, int* frames, int* n_freq) {
 oiva_status oiva_bstft_analysis(oiva_bstft* p, const float* x_host, void** X_dev) {
     OIVA_NEED(p && x_host && X_dev, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(p->device);
-    const int M = p->M, L = p->L, F = p->F;
-    if (!p->have_fwd) {
-        int n[1] = {L};
-        OIVA_TRY_FFT(hipfftPlanMany(&p->fwd, 1, n, nullptr, 1, L, nullptr, 1, F, HIPFFT_R2C, (int)(p->frames_total * M)));
-        OIVA_TRY_FFT(hipfftSetStream(p->fwd, p->stream));
-        p->have_fwd = true;
-    }
-    OIVA_TRY_HIP(hipEventRecord(p->stream.events[0], p->stream));
-    OIVA_TRY_HIP(hipMemcpyAsync(p->x, x_host, (size_t)p->samples_total * M * sizeof(float), hipMemcpyHostToDevice, p->stream));
-    OIVA_TRY_HIP(hipEventRecord(p->stream.events[1], p->stream));
-    OIVA_TRY_HIP(launch_bstft_frame(p->stream, p->x, p->win_a, p->frames, p->rooms_dev, p->B, p->frames_total, M, L, p->hop));
-    OIVA_TRY_HIP(hipEventRecord(p->stream.events[2], p->stream));
-    OIVA_TRY_FFT(hipfftExecR2C(p->fwd, p->frames, reinterpret_cast<hipfftComplex*>(p->spec)));
-    OIVA_TRY_HIP(hipEventRecord(p->stream.events[3], p->stream));
-    OIVA_TRY_HIP(launch_bstft_to_tfc(p->stream, p->spec, p->X, p->frames_total, F, M));
-    OIVA_TRY_HIP(hipEventRecord(p->stream.events[4], p->stream));
+    return analysis_from(p, X_dev, [&] {
+        return hipMemcpyAsync(p->x, x_host, (size_t)p->samples_total * p->M * sizeof(float), hipMemcpyHostToDevice, p->stream);
+    });
+}
+
+oiva_status oiva_bstft_analysis_dev(oiva_bstft* p, const void* x_dev, int f64, void** X_dev) {
+    OIVA_NEED(p && x_dev && X_dev, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(f64 == 0 || f64 == 1, OIVA_ERR_ARG, "f64 must be 0 (float32 audio) or 1 (float64 audio)");
+    DeviceGuard guard(p->device);
+    const long long n = p->samples_total * p->M;
+    return analysis_from(p, X_dev, [&] {
+        if (f64) return launch_sweep_cast(p->stream, static_cast<const double*>(x_dev), p->x, n);
+        return hipMemcpyAsync(p->x, x_dev, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, p->stream);
+    });
+}
+
+oiva_status oiva_bstft_synthesis_keep(oiva_bstft* p, const void* Y_dev, int K, void** y_dev) {
+    OIVA_NEED(p && Y_dev && y_dev, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(K >= 1 && K <= p->M, OIVA_ERR_ARG, "synthesis takes 1..M channels");
+    DeviceGuard guard(p->device);
+    const int rc = synthesis_to_x(p, Y_dev, K);
+    if (rc) return rc;
+    OIVA_TRY_HIP(hipEventRecord(p->stream.events[9], p->stream));      // (no download: that phase reads 0)
     OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
-    p->timed_a = true;
-    *X_dev = p->X;
+    p->timed_s = p->kept_s = true;
+    *y_dev = p->x;
     return OIVA_OK;
 }
 
@@ -156,29 +223,13 @@ oiva_status oiva_bstft_synthesis_dev(oiva_bstft* p, const void* Y_dev, int K, fl
     OIVA_NEED(p && Y_dev && y_host, OIVA_ERR_ARG, "null argument");
     OIVA_NEED(K >= 1 && K <= p->M, OIVA_ERR_ARG, "synthesis takes 1..M channels");
     DeviceGuard guard(p->device);
-    const int L = p->L, F = p->F;
-    // one inverse plan per channel count (the solver returns fewer channels than the analysis had)
-    if (!p->have_inv || p->inv_chan != K) {
-        if (p->have_inv) OIVA_TRY_FFT(hipfftDestroy(p->inv));
-        p->have_inv = false;
-        int n[1] = {L};
-        OIVA_TRY_FFT(hipfftPlanMany(&p->inv, 1, n, nullptr, 1, F, nullptr, 1, L, HIPFFT_C2R, (int)(p->frames_total * K)));
-        OIVA_TRY_FFT(hipfftSetStream(p->inv, p->stream));
-        p->have_inv = true;
-        p->inv_chan = K;
-    }
-    const long long n_out = p->frames_total * p->hop;
-    OIVA_TRY_HIP(hipEventRecord(p->stream.events[5], p->stream));
-    OIVA_TRY_HIP(launch_bstft_from_tfc(p->stream, static_cast<const float2*>(Y_dev), p->spec, p->frames_total, F, K));
-    OIVA_TRY_HIP(hipEventRecord(p->stream.events[6], p->stream));
-    OIVA_TRY_FFT(hipfftExecC2R(p->inv, reinterpret_cast<hipfftComplex*>(p->spec), p->frames));
-    OIVA_TRY_HIP(hipEventRecord(p->stream.events[7], p->stream));
-    OIVA_TRY_HIP(launch_bstft_overlap_add(p->stream, p->frames, p->win_s, p->x, p->rooms_dev, p->B, n_out, K, L, p->hop));
-    OIVA_TRY_HIP(hipEventRecord(p->stream.events[8], p->stream));
-    OIVA_TRY_HIP(hipMemcpyAsync(y_host, p->x, (size_t)n_out * K * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    const int rc = synthesis_to_x(p, Y_dev, K);
+    if (rc) return rc;
+    OIVA_TRY_HIP(hipMemcpyAsync(y_host, p->x, (size_t)p->frames_total * p->hop * K * sizeof(float), hipMemcpyDeviceToHost, p->stream));
     OIVA_TRY_HIP(hipEventRecord(p->stream.events[9], p->stream));
     OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
     p->timed_s = true;
+    p->kept_s = false;
     return OIVA_OK;
 }
 
@@ -189,7 +240,8 @@ oiva_status oiva_bstft_phase_ms(oiva_bstft* p, float* ms) {
     if (p->timed_a)
         for (int i = 0; i < 4; ++i) OIVA_TRY_HIP(hipEventElapsedTime(&ms[i], p->stream.events[i], p->stream.events[i + 1]));
     if (p->timed_s)
-        for (int i = 0; i < 4; ++i) OIVA_TRY_HIP(hipEventElapsedTime(&ms[4 + i], p->stream.events[5 + i], p->stream.events[6 + i]));
+        for (int i = 0; i < (p->kept_s ? 3 : 4); ++i)
+            OIVA_TRY_HIP(hipEventElapsedTime(&ms[4 + i], p->stream.events[5 + i], p->stream.events[6 + i]));
     return OIVA_OK;
 }
 

@@ -463,6 +463,53 @@ hipError_t launch_room_std(hipStream_t s, const double* premix, int S, int M, in
 hipError_t launch_room_mix(hipStream_t s, const double* premix, const double* std, const double* scale, const double* noise,
                            double sigma_n, int S, int M, int K, int n_out, double* mix, double* ref);
 
+// The sweep's hand-overs (kernels_sweep.hip, sweep.hip): room simulation -> batched STFT -> BSS Eval on the device.
+// One record per room of the group the sweep handle was made for; every field but ref_off is a function of the room's own
+// (n_out, frame, hop) and of the rooms before it.
+constexpr int kSweepMaxChan = 8;      // channels of y, as the batched solvers
+constexpr int kSweepChunk = 4096;     // samples per workgroup of the standard deviation: chunk j of a room is [j, j + 1) * kSweepChunk
+struct SweepRoom {
+    long long y_off;     // first sample of the room in the packed (sum T_b hop, C) synthesis
+    long long ref_off;   // first element of its (K + 1, n_out, M) references in the room handle's buffer (set by take_mix)
+    long long sig_off;   // first element of its (K + 1, m) rows in the packed ref / est of oiva_bsseval
+    long long fil_off;   // first sample of its filler row in the packed (sum m_b) filler
+    int n_out;           // samples of the mix
+    int ny;              // samples of the synthesis, T * hop
+    int m;               // samples that are evaluated, ny - (frame - hop)
+    int pad;
+};
+//   out (n) float32 = in (n) float64, round to nearest even
+hipError_t launch_sweep_cast(hipStream_t s, const double* in, float* out, long long n);
+//   std (B, 8): population standard deviation of the C channels of every room's y; part: 2 * B * 8 * max_chunks doubles
+hipError_t launch_sweep_std(hipStream_t s, const float* y, const SweepRoom* rooms, int B, int C, int max_chunks, double* part,
+                            double* std);
+//   order (B, 8): the channels by descending std, ties to the lower index; reorder == 0: the identity
+hipError_t launch_sweep_order(hipStream_t s, const double* std, int B, int C, int reorder, int* order);
+//   est[b, k, i] = y[b, i + offset, order[b, k]] (k < K), est[b, K, i] = filler[b, i], ref[b, j, i] = room_ref[b, j, i, ref_mic]
+//   (j <= K), i < m_b
+hipError_t launch_sweep_align(hipStream_t s, const float* y, const double* room_ref, const double* filler, const int* order,
+                              const SweepRoom* rooms, int B, int C, int M, int K, int ref_mic, int offset, int max_m, double* est,
+                              double* ref);
+// What the sweep sees of the other handles (defined next to each struct: room.hip, bsseval.hip, bstft.hip; not exported).
+struct RoomGroupView {      // the mixed group g0 of a room handle
+    int device, rooms, M, K;
+    const double* mix;      // packed (n_out_b, M) of the group's rooms
+    const double* ref;      // room i of the group at (K + 1) * mix_off[i], (K + 1, n_out_b, M)
+    long long mix_total;    // elements of mix
+};
+//   OIVA_ERR_STATE unless the group is mixed; n_out, mix_off: `rooms` entries each (at most max_rooms are written)
+int room_group_view(oiva_room* p, int g0, RoomGroupView* view, int* n_out, long long* mix_off, int max_rooms);
+struct BssSignalView {
+    int device, B, N, Lf;
+    long long sig_total;
+    double *ref, *est;
+};
+//   lengths: B entries (at most max_rooms are written)
+void bsseval_signal_view(oiva_bsseval* p, BssSignalView* view, int* lengths, int max_rooms);
+//   what oiva_bsseval_set_signals leaves behind once ref and est are written
+void bsseval_mark_signals(oiva_bsseval* p);
+void bstft_dims(oiva_bstft* p, int* device, int* B, int* M, int* frame, int* hop, long long* samples_total);
+
 // dense complex128 <-> complex64 conversion on the device
 hipError_t launch_cast_c128_to_c64(hipStream_t s, const double2* in, float2* out, long long n);
 hipError_t launch_cast_c64_to_c128(hipStream_t s, const float2* in, double2* out, long long n);

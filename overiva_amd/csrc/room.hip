@@ -210,6 +210,21 @@ int alloc_mix(oiva_room* p, int K) {
 
 }  // namespace
 
+// the sweep's view of a mixed group (sweep.hip): where its mix and its references lie on the device
+int oiva::room_group_view(oiva_room* p, int g0, RoomGroupView* view, int* n_out, long long* mix_off, int max_rooms) {
+    OIVA_NEED(p->have_sig && g0 >= 0 && g0 < p->B && g0 % p->group == 0 && p->mixed[g0], OIVA_ERR_STATE,
+              "this group of the room handle has not been mixed");
+    const int last = std::min(p->B, g0 + p->group) - 1;
+    view->device = p->device, view->rooms = last - g0 + 1, view->M = p->M, view->K = p->mix_K;
+    view->mix = p->mix, view->ref = p->ref;
+    view->mix_total = p->sig[last].mix_off + (long long)p->M * p->sig[last].n_out;
+    for (int b = g0; b <= last && b - g0 < max_rooms; ++b) {
+        n_out[b - g0] = p->sig[b].n_out;
+        mix_off[b - g0] = p->sig[b].mix_off;
+    }
+    return OIVA_OK;
+}
+
 extern "C" {
 
 oiva_status oiva_room_create(oiva_room** out, int device, int B, int S, int M, double fs, double c, int max_order, const double* room_dim,
