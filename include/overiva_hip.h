@@ -700,6 +700,39 @@ oiva_status oiva_sweep_phase_ms(oiva_sweep *p, float *ms);
 oiva_status oiva_sweep_get_order(oiva_sweep *p, int *order, double *std);
 oiva_status oiva_sweep_get_signals(oiva_sweep *p, oiva_bsseval *bsseval, double *ref_host_packed, double *est_host_packed);
 
+/*
+ * Seeded standard normals on the device (rng.hip, kernels_rng.hip; overiva_amd/rng.py): the sensor noise of the
+ * room simulation and the filler row of the sweep, drawn where they are used.  The generator is Philox-4x64-10: block j of a
+ * stream is the ten rounds on the counter (j, purpose, 0, 0) under the stream's key (key0, key1) -- what
+ * numpy.random.Philox(key=[key0, key1], counter=(j, purpose, 0, 0) - 1).random_raw(4) returns -- and every word w of it becomes
+ * u = ((w >> 12) + 0.5) 2^-52; words 0, 1 give z0 = r cos(2 pi u1), z1 = r sin(2 pi u1) with r = sqrt(-2 ln u0), words 2, 3 give
+ * z2, z3 likewise.  Element n of a stream is z[n mod 4] of block n / 4, so a stream is a prefix of every longer one with its key
+ * and purpose.  purpose: 0 for sensor noise, 1 for the filler row, other values are the caller's.  A value depends on (key,
+ * purpose, n) alone, not on the other streams of a handle or on the stream's place among them.
+ * One oiva_rng handle = n_streams streams of counts[i] elements (1..2^40 in all), packed stream after stream in float64.
+ *   oiva_rng_fill     : draws every stream, stream i under (key0[i], key1[i]); n_streams keys each
+ *   oiva_rng_fill_ms  : device ms of the kernel of the last fill
+ *   oiva_rng_get      : the packed values on the host (OIVA_ERR_STATE before the first fill)
+ *   oiva_rng_ptr      : where they lie on the device: valid until the next fill or the handle's end; with counts m_b it is a
+ *                       filler_dev of oiva_sweep_evaluate
+ *   oiva_rng_raw      : test hook: words (n_blocks, 4) of blocks first_block .. first_block + n_blocks - 1 (n_blocks <= 2^20)
+ *   oiva_rng_room_mix : oiva_room_mix with the noise of group g0 drawn into the room handle's own noise buffer instead of copied
+ *                       from the host: room g0 + i is the row-major (n_out, M) array of its stream under (key0[i], key1[i]),
+ *                       purpose 0; as many keys as the group has rooms.  Arguments, errors and the mix-down are oiva_room_mix's
+ * Every entry checks its arguments before any device call and is synchronous.
+ */
+typedef struct oiva_rng oiva_rng;
+oiva_status oiva_rng_create(oiva_rng **out, int device, int n_streams, const long long *counts, void *stream);
+oiva_status oiva_rng_destroy(oiva_rng *p);
+oiva_status oiva_rng_fill(oiva_rng *p, const unsigned long long *key0, const unsigned long long *key1, unsigned long long purpose);
+oiva_status oiva_rng_fill_ms(oiva_rng *p, float *ms);
+oiva_status oiva_rng_get(oiva_rng *p, double *host_packed);
+oiva_status oiva_rng_ptr(oiva_rng *p, void **dev_packed);
+oiva_status oiva_rng_raw(int device, unsigned long long key0, unsigned long long key1, unsigned long long purpose,
+                         unsigned long long first_block, int n_blocks, unsigned long long *words_host);
+oiva_status oiva_rng_room_mix(oiva_room *room, int g0, int K, double sinr, double snr, int ref_mic, const double *sources_var,
+                              const unsigned long long *key0, const unsigned long long *key1);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ onolab-tmu/overiva behind the reference's own Python signatures.
     from overiva_amd import bss_eval_batch, bss_eval_sources   # SDR / SIR / SAR of many rooms per call; the algorithm of DESIGN.md 3.10
     from overiva_amd import simulate_batch, rir_batch   # shoebox image-source rooms for many rooms per call; the algorithm of DESIGN.md 3.11
     from overiva_amd import sweep_batch        # geometry to SDR curves, every hand-over on the device
+    from overiva_amd import standard_normal_batch   # seeded normals drawn on the device: the noise and filler of seed=...
 
 Host code is Python (as the reference is); all arithmetic on the path runs in hand-written HIP
 kernels reached through the C ABI of ``liboveriva_hip.so`` (``include/overiva_hip.h``).  There is
@@ -32,10 +33,11 @@ from .pca_batch import auxiva_pca_batch  # noqa: F401
 from .overiva import (get_device, get_precision, last_solver_info, overiva, release_cached_buffers, set_device,  # noqa: F401
                       set_precision)
 from .plan import DeviceX, Plan  # noqa: F401
+from .rng import DeviceNormal, standard_normal_batch  # noqa: F401
 from .room import RoomBatch, rir_batch, simulate_batch  # noqa: F401
 from .separate import BatchSTFT, separate_batch  # noqa: F401
 from .sweep import SweepBatch, sweep_batch  # noqa: F401
 from .sharded import BinShardedSolver, disable_bin_sharding, enable_bin_sharding, shard_bounds  # noqa: F401
 
-__all__ = ["overiva", "separate_batch", "BatchSTFT", "DeviceBatch", "overiva_batch", "overiva_batch_ragged", "ogive_batch", "auxiva_pca_batch", "ilrma_batch", "ilrma", "bss_eval_batch", "bss_eval_sources", "simulate_batch", "rir_batch", "RoomBatch", "sweep_batch", "SweepBatch", "last_batch_info", "BatchPlan", "RaggedBatchPlan", "auxiva_pca", "ogive", "Plan", "DeviceX", "BinShardedSolver", "enable_bin_sharding", "disable_bin_sharding",
+__all__ = ["overiva", "separate_batch", "BatchSTFT", "DeviceBatch", "overiva_batch", "overiva_batch_ragged", "ogive_batch", "auxiva_pca_batch", "ilrma_batch", "ilrma", "bss_eval_batch", "bss_eval_sources", "simulate_batch", "rir_batch", "RoomBatch", "sweep_batch", "SweepBatch", "standard_normal_batch", "DeviceNormal", "last_batch_info", "BatchPlan", "RaggedBatchPlan", "auxiva_pca", "ogive", "Plan", "DeviceX", "BinShardedSolver", "enable_bin_sharding", "disable_bin_sharding",
            "shard_bounds", "release_cached_buffers", "set_device", "get_device", "set_precision", "get_precision", "last_solver_info", "HipError", "HipLibraryMissing"]

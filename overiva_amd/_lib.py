@@ -35,6 +35,7 @@ class HipError(RuntimeError):
 _lib = None
 
 _vp, _i, _ll, _fp = C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_float)
+_u64 = C.c_ulonglong
 
 # name -> argtypes ; every function returns int (see include/overiva_hip.h)
 SIGNATURES = {
@@ -185,6 +186,14 @@ SIGNATURES = {
     "oiva_sweep_phase_ms": [_vp, _fp],
     "oiva_sweep_get_order": [_vp, C.POINTER(_i), _vp],
     "oiva_sweep_get_signals": [_vp, _vp, _vp, _vp],
+    "oiva_rng_create": [C.POINTER(_vp), _i, _i, C.POINTER(_ll), _vp],
+    "oiva_rng_destroy": [_vp],
+    "oiva_rng_fill": [_vp, _vp, _vp, _u64],
+    "oiva_rng_fill_ms": [_vp, _fp],
+    "oiva_rng_get": [_vp, _vp],
+    "oiva_rng_ptr": [_vp, C.POINTER(_vp)],
+    "oiva_rng_raw": [_i, _u64, _u64, _u64, _u64, _i, _vp],
+    "oiva_rng_room_mix": [_vp, _i, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp],
 }
 
 

@@ -510,6 +510,29 @@ void bsseval_signal_view(oiva_bsseval* p, BssSignalView* view, int* lengths, int
 void bsseval_mark_signals(oiva_bsseval* p);
 void bstft_dims(oiva_bstft* p, int* device, int* B, int* M, int* frame, int* hop, long long* samples_total);
 
+// The device random generator (kernels_rng.hip, rng.hip): Philox-4x64-10 under a key per stream, counter
+// (block, purpose, 0, 0), four standard normals per block.  One record per stream; every value is a function of the stream's own
+// key, of the purpose and of its index in the stream.
+constexpr int kRngMaxGridX = 65535;
+constexpr int kRngMaxStreams = 65535;
+constexpr long long kRngMaxCount = 1ll << 40;      // elements of one handle
+constexpr int kRngMaxRaw = 1 << 20;                // blocks of one oiva_rng_raw call
+struct RngStream {
+    unsigned long long k0, k1;   // the stream's key
+    long long off;               // first element of its values in the packed output
+    long long count;             // its length
+};
+//   out packed by streams[i].off: elements [0, count) of every stream, nothing behind them; max_count: the longest stream
+hipError_t launch_rng_normal(hipStream_t s, const RngStream* streams, int n_streams, long long max_count, unsigned long long purpose,
+                             double* out);
+//   words (n, 4): the raw words of blocks first .. first + n - 1 of one stream
+hipError_t launch_rng_raw(hipStream_t s, unsigned long long k0, unsigned long long k1, unsigned long long purpose,
+                          unsigned long long first, int n, unsigned long long* words);
+//   the body of oiva_room_mix and oiva_rng_room_mix (room.hip): the group's noise from the host (noise_host, may be null: no
+//   noise), or, with keys, drawn into the handle's noise buffer: room g0 + i of the group under (key0[i], key1[i]), purpose 0
+int room_mix_body(oiva_room* p, int g0, int K, double sinr, double snr, int ref_mic, const double* sources_var,
+                  const double* noise_host, const unsigned long long* key0, const unsigned long long* key1);
+
 // dense complex128 <-> complex64 conversion on the device
 hipError_t launch_cast_c128_to_c64(hipStream_t s, const double2* in, float2* out, long long n);
 hipError_t launch_cast_c64_to_c128(hipStream_t s, const float2* in, double2* out, long long n);

@@ -225,6 +225,47 @@ int oiva::room_group_view(oiva_room* p, int g0, RoomGroupView* view, int* n_out,
     return OIVA_OK;
 }
 
+// oiva_room_mix, and oiva_rng_room_mix (rng.hip) with the keys of the group's rooms: the noise is then drawn where the copy from
+// the host would have put it, one stream per room at the room's place in the group's buffer, and the same mix-down runs
+int oiva::room_mix_body(oiva_room* p, int g0, int K, double sinr, double snr, int ref_mic, const double* sources_var,
+                        const double* noise_host, const unsigned long long* key0, const unsigned long long* key1) {
+    OIVA_NEED(p, OIVA_ERR_ARG, "null handle");
+    OIVA_NEED(K >= 1 && K <= p->S, OIVA_ERR_ARG, "n_targets must be in 1..S");
+    OIVA_NEED(ref_mic >= 0 && ref_mic < p->M, OIVA_ERR_ARG, "ref_mic must be in 0..M-1");
+    OIVA_NEED(p->have_sig && g0 >= 0 && g0 < p->B && p->convolved[g0], OIVA_ERR_STATE, "this group has not been convolved");
+    std::vector<double> scale;
+    double sigma_n = 0.;
+    int rc = mix_scales(p, K, sinr, snr, sources_var, &scale, &sigma_n);
+    if (rc) return rc;
+    DeviceGuard guard(p->device);
+    if ((rc = alloc_mix(p, K))) return rc;
+    const int last = std::min(p->B, g0 + p->group) - 1;
+    const size_t n = (size_t)p->sig[last].mix_off + (size_t)p->M * p->sig[last].n_out;
+    ScopedDev tmp(p->device);
+    OIVA_TRY_HIP(hipMemcpyAsync(p->scale, scale.data(), (size_t)p->S * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    if (noise_host) OIVA_TRY_HIP(hipMemcpyAsync(p->noise, noise_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    if (key0) {
+        std::vector<RngStream> streams(last - g0 + 1);
+        long long longest = 0;
+        for (int b = g0; b <= last; ++b) {
+            const long long count = (long long)p->M * p->sig[b].n_out;      // (ends inside the noise buffer: alloc_mix sized it so)
+            streams[b - g0] = RngStream{key0[b - g0], key1[b - g0], p->sig[b].mix_off, count};
+            longest = std::max(longest, count);
+        }
+        RngStream* streams_dev = nullptr;
+        tmp.take_filled(&streams_dev, streams.data(), streams.size() * sizeof(RngStream));
+        OIVA_TRY_HIP(tmp.status());
+        OIVA_TRY_HIP(launch_rng_normal(p->stream, streams_dev, (int)streams.size(), longest, 0ull, p->noise));
+    }
+    if ((rc = stage_mix(p, g0, K, sigma_n, ref_mic, noise_host != nullptr || key0 != nullptr))) {
+        (void)hipStreamSynchronize(p->stream);      // (the stream table is this call's)
+        return rc;
+    }
+    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));      // (scale is the caller's stack until here)
+    p->mixed[g0] = 1;
+    return OIVA_OK;
+}
+
 extern "C" {
 
 oiva_status oiva_room_create(oiva_room** out, int device, int B, int S, int M, double fs, double c, int max_order, const double* room_dim,
@@ -462,24 +503,7 @@ oiva_status oiva_room_get_premix(oiva_room* p, int g0, double* premix_host) {
 
 oiva_status oiva_room_mix(oiva_room* p, int g0, int K, double sinr, double snr, int ref_mic, const double* sources_var,
                           const double* noise_host) {
-    OIVA_NEED(p, OIVA_ERR_ARG, "null handle");
-    OIVA_NEED(K >= 1 && K <= p->S, OIVA_ERR_ARG, "n_targets must be in 1..S");
-    OIVA_NEED(ref_mic >= 0 && ref_mic < p->M, OIVA_ERR_ARG, "ref_mic must be in 0..M-1");
-    OIVA_NEED(p->have_sig && g0 >= 0 && g0 < p->B && p->convolved[g0], OIVA_ERR_STATE, "this group has not been convolved");
-    std::vector<double> scale;
-    double sigma_n = 0.;
-    int rc = mix_scales(p, K, sinr, snr, sources_var, &scale, &sigma_n);
-    if (rc) return rc;
-    DeviceGuard guard(p->device);
-    if ((rc = alloc_mix(p, K))) return rc;
-    const int last = std::min(p->B, g0 + p->group) - 1;
-    const size_t n = (size_t)p->sig[last].mix_off + (size_t)p->M * p->sig[last].n_out;
-    OIVA_TRY_HIP(hipMemcpyAsync(p->scale, scale.data(), (size_t)p->S * sizeof(double), hipMemcpyHostToDevice, p->stream));
-    if (noise_host) OIVA_TRY_HIP(hipMemcpyAsync(p->noise, noise_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-    if ((rc = stage_mix(p, g0, K, sigma_n, ref_mic, noise_host != nullptr))) return rc;
-    OIVA_TRY_HIP(hipStreamSynchronize(p->stream));      // (scale is the caller's stack until here)
-    p->mixed[g0] = 1;
-    return OIVA_OK;
+    return room_mix_body(p, g0, K, sinr, snr, ref_mic, sources_var, noise_host, nullptr, nullptr);
 }
 
 oiva_status oiva_room_get_mix(oiva_room* p, int g0, double* mix_host, double* ref_host) {

@@ -11,7 +11,8 @@ not pinned.
 Per (room, source, microphone): the images ``(nx, ny, nz)`` with ``|nx| + |ny| + |nz| <= max_order`` in the order nx, ny, nz
 ascending, each adding 81 taps of a Hann-windowed sinc at its delay, so an impulse response carries a fixed lag of 40 samples.
 Every sample has one owner that adds the taps in that order: a room's bits do not depend on B, on its place in the batch or on
-the other rooms.  The device draws no random numbers: ``noise`` is the caller's.
+the other rooms.  ``noise`` is the caller's, or, with ``seed``, drawn on the device from the seeded stream of DESIGN.md 3.13
+(``overiva_amd/rng.py``): room b's ``(n_out_b, n_mics)`` noise is its purpose-0 stream, read row by row.
 """
 import ctypes as C
 
@@ -19,6 +20,7 @@ import numpy as np
 
 from . import _lib, sharded
 from . import batch as _batch
+from . import rng as _rng
 from .overiva import get_device
 
 MAX_ORDER = 32
@@ -185,6 +187,7 @@ class RoomBatch(_lib.Handle):
         self.images = image_count(max_order)
         self.device = get_device() if device is None else int(device)
         self.rir_lengths, self.lengths, self.group, self.K = None, None, None, None
+        self.noise_source = None                 # of the last mix: "host", "device" or None (no noise)
         h = C.c_void_p()
         _lib.check(self.lib.oiva_room_create(C.byref(h), self.device, self.B, self.S, self.M, fs, c, max_order, _lib.ptr(room_dim),
                                              _lib.ptr(sources), _lib.ptr(mics), _lib.ptr(a6), rir_length or 0,
@@ -195,7 +198,8 @@ class RoomBatch(_lib.Handle):
         """what ``last_batch_info()`` reports after a run on this handle"""
         out = {"algorithm": "simulate", "precision": "float64", "batched": self.B, "sharded": False, "n_sources": self.S,
                "n_mics": self.M, "max_order": self.max_order, "images": self.images,
-               "rir_lengths": None if self.rir_lengths is None else list(self.rir_lengths), "rooms_per_group": self.group}
+               "rir_lengths": None if self.rir_lengths is None else list(self.rir_lengths), "rooms_per_group": self.group,
+               "noise": self.noise_source}
         if self.lengths is not None:
             if len(set(self.lengths)) > 1:
                 out.update(ragged=True, lengths=list(self.lengths))
@@ -250,9 +254,13 @@ class RoomBatch(_lib.Handle):
         off = np.concatenate([[0], np.cumsum(sizes)])
         return [flat[off[i]:off[i + 1]].reshape(self.S, self.M, self.out_lengths[b]) for i, b in enumerate(self.group_rooms(g0))]
 
-    def mix(self, g0=0, n_targets=1, sinr=10.0, snr=60.0, ref_mic=0, sources_var=None, noise=None):
-        """the mix-down of the group that starts at room g0 (convolved); noise: None or the group's (n_out_b, M) arrays"""
+    def mix(self, g0=0, n_targets=1, sinr=10.0, snr=60.0, ref_mic=0, sources_var=None, noise=None, seed_keys=None):
+        """the mix-down of the group that starts at room g0 (convolved); noise: None or the group's (n_out_b, M) arrays;
+        seed_keys: None or (key0, key1), one key per room of the group: the noise is drawn on the device, room by room from the
+        purpose-0 stream of its key (``overiva_amd/rng.py``), and nothing is copied from the host"""
         rooms = self.group_rooms(g0)
+        if seed_keys is not None and noise is not None:
+            raise ValueError("noise and seed_keys exclude each other: the noise is the caller's or the device's")
         packed = None
         if noise is not None:
             if len(noise) != len(rooms) or any(np.shape(a) != (self.out_lengths[b], self.M) for a, b in zip(noise, rooms)):
@@ -262,9 +270,17 @@ class RoomBatch(_lib.Handle):
         var = None if sources_var is None else np.ascontiguousarray(sources_var, dtype=np.float64)
         if var is not None and var.shape != (int(n_targets),):
             raise ValueError(f"sources_var must hold n_targets = {n_targets} values")
-        _lib.check(self.lib.oiva_room_mix(self.h, int(g0), int(n_targets), float(sinr), float(snr), int(ref_mic),
-                                          None if var is None else _lib.ptr(var), None if packed is None else _lib.ptr(packed)))
+        if seed_keys is not None:
+            k0, k1 = (np.ascontiguousarray(k, dtype=np.uint64) for k in seed_keys)
+            if k0.shape != (len(rooms),) or k1.shape != (len(rooms),):
+                raise ValueError(f"seed_keys must be two sequences of {len(rooms)} words, one key per room of the group")
+            _lib.check(self.lib.oiva_rng_room_mix(self.h, int(g0), int(n_targets), float(sinr), float(snr), int(ref_mic),
+                                                  None if var is None else _lib.ptr(var), _lib.ptr(k0), _lib.ptr(k1)))
+        else:
+            _lib.check(self.lib.oiva_room_mix(self.h, int(g0), int(n_targets), float(sinr), float(snr), int(ref_mic),
+                                              None if var is None else _lib.ptr(var), None if packed is None else _lib.ptr(packed)))
         self.K = int(n_targets)
+        self.noise_source = "device" if seed_keys is not None else None if noise is None else "host"
 
     def get_mix(self, g0=0):
         """the group's mix, a list of (n_out_b, M) arrays, and ref, a list of (K + 1, n_out_b, M) arrays"""
@@ -278,8 +294,9 @@ class RoomBatch(_lib.Handle):
                 for i, b in enumerate(rooms)]
         return mixes, refs
 
-    def simulate(self, mix_args=None, noise=None):
-        """every group through ``convolve`` (and ``mix`` with ``mix_args``): the premix of every room, or (mix, ref) of every room"""
+    def simulate(self, mix_args=None, noise=None, seed_keys=None):
+        """every group through ``convolve`` (and ``mix`` with ``mix_args``): the premix of every room, or (mix, ref) of every room;
+        noise and seed_keys ((key0, key1), one key per room of the batch) as ``mix`` takes them for a group"""
         premix, mixes, refs = [], [], []
         for g0 in range(0, self.B, self.group):
             self.convolve(g0)
@@ -287,7 +304,8 @@ class RoomBatch(_lib.Handle):
                 premix += self.get_premix(g0)
                 continue
             rooms = self.group_rooms(g0)
-            self.mix(g0, noise=None if noise is None else [noise[b] for b in rooms], **mix_args)
+            self.mix(g0, noise=None if noise is None else [noise[b] for b in rooms],
+                     seed_keys=None if seed_keys is None else tuple(k[rooms.start:rooms.stop] for k in seed_keys), **mix_args)
             m, r = self.get_mix(g0)
             mixes += m
             refs += r
@@ -330,7 +348,7 @@ def rir_batch(room_dim, sources, mics, fs=16000, max_order=17, absorption=0.35, 
 
 
 def simulate_batch(signals, room_dim, sources, mics, fs=16000, max_order=17, absorption=0.35, c=343.0, rir_length=None,
-                   n_targets=None, sinr=10.0, snr=60.0, ref_mic=0, sources_var=None, noise=None):
+                   n_targets=None, sinr=10.0, snr=60.0, ref_mic=0, sources_var=None, noise=None, seed=None, max_group=0):
     """
     Simulate B shoebox rooms at once: impulse responses as ``rir_batch()``, every source convolved with its response at every
     microphone and, with ``n_targets``, the scaling and mix-down of the reference's sweep (``overiva_sim.py:166-198``).  The
@@ -346,6 +364,13 @@ def simulate_batch(signals, room_dim, sources, mics, fs=16000, max_order=17, abs
         ``max(0, 10^(-sinr/10) sum(var) - sigma_n^2)`` equally.  ``n_targets == n_sources`` needs ``sinr=np.inf``
     noise: None (no noise is added) or unit-variance noise of the caller's, (batch, n_out, n_mics) or a sequence of
         (n_out_b, n_mics) arrays with ``n_out_b = n_samples_b + L_b - 1`` (``rir_batch()`` or ``rir_length`` tell L_b beforehand)
+    seed: None, or the seed of unit-variance noise drawn on the device (``standard_normal_batch()``; needs
+        ``n_targets`` and ``noise=None``): room b's noise is the row-major (n_out_b, n_mics) array of its purpose-0 stream.  An
+        int s in 0..2**64 - 1 gives room b the key (s, b): its noise then **depends on the room's index in the batch**.  A
+        sequence of B such ints gives room b the key (seed[b], 0) -- one seed per run, as the reference's argument lists carry
+        them -- and a room's noise does not depend on the batch.  Nothing but the seeds crosses the bus for the noise
+    max_group: 0, or the most rooms that go through the stages together, as ``RoomBatch.set_signals``; a room's bits do not
+        depend on it
 
     Returns
     -------
@@ -356,21 +381,29 @@ def simulate_batch(signals, room_dim, sources, mics, fs=16000, max_order=17, abs
     geometry = _check_geometry(room_dim, sources, mics, fs, max_order, absorption, c, rir_length)
     B, S, M = geometry[0].shape[0], geometry[1].shape[1], geometry[2].shape[1]
     sig, ragged = _check_signals(signals, B, S)
-    mix_args = None
+    mix_args = seed_keys = None
     if n_targets is not None:
         K, sinr, snr, ref_mic, var, noise = _check_mix(B, S, M, ragged, n_targets, sinr, snr, ref_mic, sources_var, noise)
         mix_args = dict(n_targets=K, sinr=sinr, snr=snr, ref_mic=ref_mic, sources_var=var)
+    if seed is not None:
+        if n_targets is None:
+            raise ValueError("seed names the noise of the mix-down: it needs n_targets")
+        if noise is not None:
+            raise ValueError("seed and noise exclude each other: the noise is the caller's (noise) or drawn on the device (seed)")
+        seed_keys = _rng.check_seed(seed, B)
+    if not _is_int(max_group) or max_group < 0:
+        raise ValueError(f"max_group must be an integer >= 0, got {max_group!r}")
     _refuse_sharding("simulate_batch")
     with RoomBatch(*geometry[:3], fs=geometry[4], max_order=geometry[6], absorption=geometry[3], c=geometry[5],
                    rir_length=geometry[7]) as rb:
         rb.compute_rir()
-        rb.set_signals(sig)
+        rb.set_signals(sig, max_group)
         if mix_args is not None and noise is not None:
             for b, a in enumerate(noise):
                 if a.shape[0] != rb.out_lengths[b]:
                     raise ValueError(f"noise: room {b} has {a.shape[0]} samples, its output has {rb.out_lengths[b]} "
                                      f"(n_samples + rir_length - 1 = {rb.lengths[b]} + {rb.rir_lengths[b]} - 1)")
-        out = rb.simulate(mix_args, noise)
+        out = rb.simulate(mix_args, noise, seed_keys)
         _batch._info = rb.info()
     stack = not ragged and len(set(rb.out_lengths)) == 1
     if mix_args is None:

@@ -11,7 +11,9 @@ is exact (the cast the host would do, a gather, float32 -> float64) or decides o
 deviations): the criteria are those of the chain of the three calls, bit for bit.
 
 **What still crosses the bus**: the source signals and the geometry in, ``noise`` in (the caller's), the filler in, the criteria
-out -- and a few words per launch.
+out -- and a few words per launch.  With ``seed`` the noise and the filler that the caller does not give are drawn on the device
+from the seeded stream of DESIGN.md 3.13 (``overiva_amd/rng.py``, csrc/kernels_rng.hip), straight into the buffers the mix-down
+and the gather read: then signals, geometry and seeds go in and the criteria come out.
 
 Alignment: this project's STFT has no delay, ``y[i]`` lines up with ``x[i]`` and the last ``frame - hop`` samples lack their
 later overlaps, so the reference's ``y[framesize // 2 : m + framesize // 2]`` is ``y[0 : m_b]`` here, with
@@ -26,6 +28,7 @@ from . import _lib
 from . import batch as _batch
 from . import metrics as _metrics
 from . import pca_batch as _pca_batch
+from . import rng as _rng
 from . import room as _room
 from . import separate as _separate
 from .batch import DeviceBatch
@@ -141,7 +144,7 @@ class SweepBatch(_lib.Handle):
     ``evaluate`` left."""
 
     _destroy = "oiva_sweep_destroy"
-    room = stft = ev = g0 = None
+    room = stft = ev = g0 = filler_gen = None
     rooms = ()
 
     def __init__(self, room_dim, sources, mics, frame, hop=None, n_targets=1, fs=16000, max_order=17, absorption=0.35, c=343.0,
@@ -166,7 +169,7 @@ class SweepBatch(_lib.Handle):
         self.lib = self.room.lib
         self.B, self.S, self.M, self.K = self.room.B, self.room.S, int(M), int(n_targets)
         self.frame, self.hop, self.ref_mic, self.Lf = int(frame), int(hop), int(ref_mic), int(filter_length)
-        self.out_lengths = self.eval_lengths = self.group = self.filler = None
+        self.out_lengths = self.eval_lengths = self.group = self.filler = self.filler_keys = None
         self.g0, self.stft, self.ev, self.rooms, self.last_C = None, None, None, (), 0
 
     def set_signals(self, signals, max_group=0):
@@ -179,10 +182,20 @@ class SweepBatch(_lib.Handle):
         self.eval_lengths = _eval_lengths(self.out_lengths, self.frame, self.hop)
         return self.group
 
-    def set_filler(self, filler=None):
+    def set_filler(self, filler=None, seed=None):
         """filler: B 1-D arrays of at least m_b samples each, or None: room b gets the first m_b draws of
         ``numpy.random.default_rng(0).standard_normal`` -- every room from a generator of its own, so that a room's row does not
-        depend on the batch it is in"""
+        depend on the batch it is in.  seed (an int, or one int per room, as ``sweep_batch`` takes it) instead of a filler: room
+        b's row is the first m_b values of its purpose-1 stream, drawn on the device when its group is opened"""
+        if seed is not None:
+            if filler is not None:
+                raise ValueError("filler and seed exclude each other: the row is the caller's or drawn on the device")
+            self.filler_keys, self.filler = _rng.check_seed(seed, self.B), None
+            if self.h:
+                self._draw_filler()
+            return
+        self.filler_keys = None
+        self._close_filler_gen()
         if filler is None:
             filler = [np.random.default_rng(0).standard_normal(m) for m in self.eval_lengths]
         if len(filler) != self.B:
@@ -198,11 +211,22 @@ class SweepBatch(_lib.Handle):
         packed = np.concatenate([self.filler[b] for b in self.rooms])
         _lib.check(self.lib.oiva_sweep_set_filler(self.h, _lib.ptr(packed)))
 
+    def _draw_filler(self):
+        """the open group's filler rows on the device: packed (sum m_b), the ``filler_dev`` of every ``evaluate``"""
+        self._close_filler_gen()
+        self.filler_gen = _rng.DeviceNormal([self.eval_lengths[b] for b in self.rooms], device=self.device)
+        self.filler_gen.fill(*(k[self.rooms.start:self.rooms.stop] for k in self.filler_keys), purpose=_rng.FILLER)
+
+    def _close_filler_gen(self):
+        if self.filler_gen is not None:
+            self.filler_gen.close()
+        self.filler_gen = None
+
     def open_group(self, g0=0):
         """the handles of the group that starts at room g0 (those of the group before are closed)"""
         if self.group is None:
             raise RuntimeError("signals not set")
-        if self.filler is None:
+        if self.filler is None and self.filler_keys is None:
             self.set_filler()
         self.close_group()
         self.rooms = self.room.group_rooms(g0)
@@ -217,14 +241,17 @@ class SweepBatch(_lib.Handle):
         self.h = h
         self.ev = _metrics.BssEval([self.eval_lengths[b] for b in self.rooms], self.K + 1, self.Lf, device=self.device)
         self.g0, self.last_C = int(g0), 0
-        self._upload_filler()
+        if self.filler_keys is not None:
+            self._draw_filler()
+        else:
+            self._upload_filler()
 
     def close_group(self):
         _lib.Handle.close(self)
-        for part in (self.stft, self.ev):
+        for part in (self.stft, self.ev, self.filler_gen):
             if part is not None:
                 part.close()
-        self.stft = self.ev = self.g0 = None
+        self.stft = self.ev = self.g0 = self.filler_gen = None
         self.rooms = ()
 
     def close(self):
@@ -235,9 +262,10 @@ class SweepBatch(_lib.Handle):
     def convolve(self, g0=0):
         self.room.convolve(g0)
 
-    def mix(self, g0=0, sinr=10.0, snr=60.0, sources_var=None, noise=None):
+    def mix(self, g0=0, sinr=10.0, snr=60.0, sources_var=None, noise=None, seed_keys=None):
         """as ``RoomBatch.mix`` with this handle's ``n_targets`` and ``ref_mic``"""
-        self.room.mix(g0, n_targets=self.K, sinr=sinr, snr=snr, ref_mic=self.ref_mic, sources_var=sources_var, noise=noise)
+        self.room.mix(g0, n_targets=self.K, sinr=sinr, snr=snr, ref_mic=self.ref_mic, sources_var=sources_var, noise=noise,
+                      seed_keys=seed_keys)
 
     def take_mix(self):
         """the open group's mix -> X on the device (float64 -> float32 and the analysis, no host copy): a ``DeviceBatch`` valid
@@ -252,7 +280,7 @@ class SweepBatch(_lib.Handle):
         if Y.frames != self.stft.frames or Y.n_freq != self.stft.n_freq:
             raise ValueError(f"Y holds frames {Y.frames} x {Y.n_freq} bins, the group {self.stft.frames} x {self.stft.n_freq}")
         _lib.check(self.lib.oiva_sweep_evaluate(self.h, self.stft.h, C.c_void_p(Y.ptr), int(Y.n_chan), 1 if reorder else 0, self.ev.h,
-                                                None))
+                                                None if self.filler_gen is None else C.c_void_p(self.filler_gen.ptr)))
         self.last_C = int(Y.n_chan)
         self.ev.run()
         mats = self.ev.get_criteria()
@@ -345,13 +373,15 @@ def _merge(per_group, n_targets):
 
 def sweep_batch(signals, room_dim, sources, mics, frame, hop=None, algorithms=None, n_targets=1, fs=16000, max_order=17,
                 absorption=0.35, c=343.0, rir_length=None, sinr=10.0, snr=60.0, ref_mic=0, sources_var=None, noise=None, filler=None,
-                filter_length=512, monitor_convergence=False, win_a=None, win_s=None, overdet_algos=OVERDET_ALGOS, max_group=0):
+                filter_length=512, monitor_convergence=False, win_a=None, win_s=None, overdet_algos=OVERDET_ALGOS, max_group=0,
+                seed=None):
     """
     One step of the reference's Monte-Carlo sweep (``overiva_sim.py:140-350``) for B rooms at once: shoebox rooms, mix-down, one
     STFT, every entry of ``algorithms`` on it, inverse STFT and BSS Eval at every checkpoint.  Between ``oiva_room_mix`` and the
     criteria the audio, X, Y, y and the references stay on the device.  **What still crosses the bus**: signals and geometry in,
-    ``noise`` in, the filler in, the criteria out.  The criteria equal, bit for bit, those of ``simulate_batch`` ->
-    ``mix.astype(float32)`` -> ``BatchSTFT`` / the batch plans / ``synthesis_device`` -> the ordering below -> ``bss_eval_batch``.
+    ``noise`` in, the filler in, the criteria out; with ``seed``: signals, geometry and seeds in, criteria out.  The criteria
+    equal, bit for bit, those of ``simulate_batch`` -> ``mix.astype(float32)`` -> ``BatchSTFT`` / the batch plans /
+    ``synthesis_device`` -> the ordering below -> ``bss_eval_batch``.
 
     Parameters
     ----------
@@ -364,8 +394,13 @@ def sweep_batch(signals, room_dim, sources, mics, frame, hop=None, algorithms=No
         ``init_eig``, ``W0`` and, for "ogive", ``step_size``, ``tol``, ``update``.  Skipped as the reference skips them:
         "auxiva_pca" with one target, "ogive" with more than one.  "ilrma" is refused.  "ogive" needs rooms of one output length.
     filler: (batch, >= m_b) or a sequence of 1-D arrays: the row that is held against the background (``overiva_sim.py:200``);
-        default: every room's first m_b draws of its own ``numpy.random.default_rng(0).standard_normal`` (the device draws no
-        random numbers)
+        default without ``seed``: every room's first m_b draws of its own ``numpy.random.default_rng(0).standard_normal``
+    seed: None, or the seed of what is drawn on the device (``standard_normal_batch()``): whichever of ``noise``
+        and ``filler`` is None.  Room b's noise is the row-major (n_out_b, n_mics) array of its purpose-0 stream, its filler the
+        first m_b values of its purpose-1 stream.  An int s in 0..2**64 - 1 gives room b the key (s, b): its draws then **depend
+        on the room's index in the batch**.  A sequence of B such ints gives room b the key (seed[b], 0), one seed per run as
+        the reference's argument lists carry them, and a room's draws do not depend on the batch.  ``seed`` with both ``noise``
+        and ``filler`` given is refused: nothing would be drawn.  Without ``seed`` nothing is drawn: ``noise=None`` is no noise
     filter_length: taps of the BSS Eval filter, 1..512
     monitor_convergence: evaluate along the way, at ``checkpoints(algo, n_iter, True)``; otherwise ``[0, n_iter]`` with the shared
         evaluation of the unprocessed microphones at 0
@@ -404,6 +439,11 @@ def sweep_batch(signals, room_dim, sources, mics, frame, hop=None, algorithms=No
         _eval_lengths(lens, frame, hop)
     entries = _check_algorithms(algorithms, K, lens, M, frame, hop, win_a, win_s, overdet_algos)
     filler = _check_filler(filler, B)
+    keys = None
+    if seed is not None:
+        if noise is not None and filler is not None:
+            raise ValueError("seed with both noise and filler given: nothing is left to draw on the device")
+        keys = _rng.check_seed(seed, B)
     if not _room._is_int(max_group) or max_group < 0:
         raise ValueError(f"max_group must be an integer >= 0, got {max_group!r}")
     _room._refuse_sharding("sweep_batch")
@@ -418,12 +458,17 @@ def sweep_batch(signals, room_dim, sources, mics, frame, hop=None, algorithms=No
         if any(e["algo"] == "ogive" for e in entries) and len(set(sb.out_lengths)) > 1:
             raise ValueError(f"OGIVE needs rooms of one output length, the rooms come out {sb.out_lengths} samples long: give "
                              "rir_length and signals of one length")
-        sb.set_filler(filler)
+        if keys is not None and filler is None:
+            sb.set_filler(seed=seed)
+        else:
+            sb.set_filler(filler)
+        draw_noise = keys is not None and noise is None
         results = [[] for _ in entries]
         for g0 in range(0, B, sb.group):
             sb.open_group(g0)
             sb.convolve(g0)
-            sb.mix(g0, sinr, snr, var, None if noise is None else [noise[b] for b in sb.rooms])
+            sb.mix(g0, sinr, snr, var, None if noise is None else [noise[b] for b in sb.rooms],
+                   tuple(k[sb.rooms.start:sb.rooms.stop] for k in keys) if draw_noise else None)
             Xd = sb.take_mix()
             init = None
             if not monitor_convergence or any(e["algo"] == "auxiva_pca" for e in entries):
@@ -433,7 +478,8 @@ def sweep_batch(signals, room_dim, sources, mics, frame, hop=None, algorithms=No
         groups = [len(sb.room.group_rooms(g0)) for g0 in range(0, B, sb.group)]
         _batch._info = {"algorithm": "sweep", "precision": "precise", "batched": B, "sharded": False, "n_mics": M, "n_targets": K,
                         "rooms_per_group": sb.group, "groups": groups, "algorithms": [e["name"] for e in entries],
-                        "filter_length": int(filter_length), "phase_ms": sb.phase_ms()}      # (of the last group's last calls)
+                        "filter_length": int(filter_length), "phase_ms": sb.phase_ms(),      # (of the last group's last calls)
+                        "noise": sb.room.noise_source}
         n_samples = list(sb.out_lengths)
     out = []
     for e, per_group in zip(entries, results):
