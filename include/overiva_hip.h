@@ -616,6 +616,52 @@ oiva_status oiva_bsseval_status(oiva_bsseval *p, int *status);
 oiva_status oiva_bsseval_time_stages(oiva_bsseval *p, int n, float *per_stage_ms);
 
 /*
+ * BSS Eval of many estimate sets against one set of references (bsssets.hip, kernels_bsssets.hip): the half of
+ * oiva_bsseval that depends on the references alone -- their lag sums, the Gram matrix G, its Cholesky factor and the factors of
+ * its N diagonal blocks -- is made once (prepare) and up to max_sets estimate sets are evaluated against it, any number of them
+ * per set of launches (evaluate).  One handle = one (lengths, N, filter_length, max_sets), limits as oiva_bsseval_create and
+ * max_sets >= 1; all B rooms are resident at once (no internal grouping: when the buffers do not fit, creation fails with the
+ * allocation message and leaves nothing behind).  For every room and set the results have the bits oiva_bsseval gives on the same
+ * signals; they do not depend on max_sets, on the sets evaluated together, on the set's place among them, on B or on the room's
+ * place.
+ *   ref / est packed as for oiva_bsseval_set_signals; set e is one such est.
+ *   oiva_bsssets_set_references: the references, host -> device; drops the preparation and every set's results
+ *   oiva_bsssets_set_estimates : the estimates of set e (0 .. max_sets - 1), host -> device
+ *   oiva_bsssets_take          : device to device from an oiva_bsseval handle that is as oiva_bsseval_set_signals leaves it (the
+ *                                caller sees to that): its estimates into set e, with_references its references too.  The handles
+ *                                must agree in device, B, lengths, N and filter_length (OIVA_ERR_ARG names what differs)
+ *   oiva_bsssets_prepare       : the reference half; the same pivot rule as oiva_bsseval, so the same rooms are flagged
+ *   oiva_bsssets_evaluate      : sets e0 .. e0 + n_sets - 1: lag sums with the estimates, right-hand sides, substitutions, quadratic
+ *                                forms, ratios.  OIVA_ERR_STATE before prepare (or after new references) and for a set whose
+ *                                estimates were never given.  Flagged rooms are skipped, the others run on
+ *   oiva_bsssets_get_criteria  : sdr, sir, sar (B, n_sets, N, N) indexed [room][set][estimate][reference], NaN where not evaluated;
+ *                                copies them out even when it returns OIVA_ERR_NUMERIC (the message names the flagged rooms as
+ *                                "problem(s) ...")
+ *   oiva_bsssets_status        : status[B], 1 for a flagged room (after prepare)
+ *   oiva_bsssets_get_gram      : test hook: G (B, N Lf, N Lf) (may be NULL), D (B, N, N Lf) and E (B, N) of the evaluated set e
+ *   oiva_bsssets_get_filters   : test hook: C (B, N, N Lf) and c (B, N[j], N[k], Lf) of the evaluated set e
+ *   oiva_bsssets_counts        : preparations and sets evaluated since creation
+ *   oiva_bsssets_phase_ms      : ms[4]: device ms of the last prepare, and of the lag sums, the substitutions (with the right-hand
+ *                                sides) and the criteria of the last evaluate (OIVA_ERR_STATE until both have run)
+ * Every entry checks its arguments before any device call and is synchronous.
+ */
+typedef struct oiva_bsssets oiva_bsssets;
+oiva_status oiva_bsssets_create(oiva_bsssets **out, int device, int B, const int *n_samples, int N, int filter_length,
+                                int diag_only, int max_sets, void *stream);
+oiva_status oiva_bsssets_destroy(oiva_bsssets *p);
+oiva_status oiva_bsssets_set_references(oiva_bsssets *p, const double *ref_host_packed);
+oiva_status oiva_bsssets_set_estimates(oiva_bsssets *p, int e, const double *est_host_packed);
+oiva_status oiva_bsssets_take(oiva_bsssets *p, oiva_bsseval *from, int e, int with_references);
+oiva_status oiva_bsssets_prepare(oiva_bsssets *p);
+oiva_status oiva_bsssets_evaluate(oiva_bsssets *p, int e0, int n_sets);
+oiva_status oiva_bsssets_get_criteria(oiva_bsssets *p, int e0, int n_sets, double *sdr, double *sir, double *sar);
+oiva_status oiva_bsssets_status(oiva_bsssets *p, int *status);
+oiva_status oiva_bsssets_get_gram(oiva_bsssets *p, int e, double *G_host, double *D_host, double *E_host);
+oiva_status oiva_bsssets_get_filters(oiva_bsssets *p, int e, double *C_host, double *c_host);
+oiva_status oiva_bsssets_counts(oiva_bsssets *p, long long *preparations, long long *sets_evaluated);
+oiva_status oiva_bsssets_phase_ms(oiva_bsssets *p, float *ms);
+
+/*
  * Shoebox rooms by the image-source method on the device (room.hip, kernels_room.hip): impulse responses, premix
  * (every source convolved with its response at every microphone) and mix-down of B rooms of S sources (1..16) and M microphones
  * (1..32), all arithmetic in float64.  One handle = one set of geometries; fs, c and max_order (0..32) are the batch's.

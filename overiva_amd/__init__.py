@@ -9,6 +9,7 @@ onolab-tmu/overiva behind the reference's own Python signatures.
     from overiva_amd import ilrma_batch, ilrma # ILRMA (NMF source model) for many rooms per call; the algorithm of DESIGN.md 3.9
     from overiva_amd import separate_batch     # audio in, audio out for many rooms, X and Y staying on the device
     from overiva_amd import bss_eval_batch, bss_eval_sources   # SDR / SIR / SAR of many rooms per call; the algorithm of DESIGN.md 3.10
+    from overiva_amd import bss_eval_sets_batch, bss_eval_sets, BssEvalSets   # the same for many sets of estimates per set of references: the reference half once
     from overiva_amd import simulate_batch, rir_batch   # shoebox image-source rooms for many rooms per call; the algorithm of DESIGN.md 3.11
     from overiva_amd import sweep_batch        # geometry to SDR curves, every hand-over on the device
     from overiva_amd import standard_normal_batch   # seeded normals drawn on the device: the noise and filler of seed=...
@@ -28,7 +29,7 @@ from .auxiva_pca import auxiva_pca  # noqa: F401
 from .batch import BatchPlan, DeviceBatch, RaggedBatchPlan, last_batch_info, ogive_batch, overiva_batch, overiva_batch_ragged  # noqa: F401
 from .ilrma import ilrma, ilrma_batch  # noqa: F401
 from .ive import ogive  # noqa: F401
-from .metrics import bss_eval_batch, bss_eval_sources  # noqa: F401
+from .metrics import BssEvalSets, bss_eval_batch, bss_eval_sets, bss_eval_sets_batch, bss_eval_sources  # noqa: F401
 from .pca_batch import auxiva_pca_batch  # noqa: F401
 from .overiva import (get_device, get_precision, last_solver_info, overiva, release_cached_buffers, set_device,  # noqa: F401
                       set_precision)
@@ -39,5 +40,5 @@ from .separate import BatchSTFT, separate_batch  # noqa: F401
 from .sweep import SweepBatch, sweep_batch  # noqa: F401
 from .sharded import BinShardedSolver, disable_bin_sharding, enable_bin_sharding, shard_bounds  # noqa: F401
 
-__all__ = ["overiva", "separate_batch", "BatchSTFT", "DeviceBatch", "overiva_batch", "overiva_batch_ragged", "ogive_batch", "auxiva_pca_batch", "ilrma_batch", "ilrma", "bss_eval_batch", "bss_eval_sources", "simulate_batch", "rir_batch", "RoomBatch", "sweep_batch", "SweepBatch", "standard_normal_batch", "DeviceNormal", "last_batch_info", "BatchPlan", "RaggedBatchPlan", "auxiva_pca", "ogive", "Plan", "DeviceX", "BinShardedSolver", "enable_bin_sharding", "disable_bin_sharding",
+__all__ = ["overiva", "separate_batch", "BatchSTFT", "DeviceBatch", "overiva_batch", "overiva_batch_ragged", "ogive_batch", "auxiva_pca_batch", "ilrma_batch", "ilrma", "bss_eval_batch", "bss_eval_sources", "bss_eval_sets_batch", "bss_eval_sets", "BssEvalSets", "simulate_batch", "rir_batch", "RoomBatch", "sweep_batch", "SweepBatch", "standard_normal_batch", "DeviceNormal", "last_batch_info", "BatchPlan", "RaggedBatchPlan", "auxiva_pca", "ogive", "Plan", "DeviceX", "BinShardedSolver", "enable_bin_sharding", "disable_bin_sharding",
            "shard_bounds", "release_cached_buffers", "set_device", "get_device", "set_precision", "get_precision", "last_solver_info", "HipError", "HipLibraryMissing"]

@@ -164,6 +164,19 @@ SIGNATURES = {
     "oiva_bsseval_get_criteria": [_vp, _vp, _vp, _vp],
     "oiva_bsseval_status": [_vp, C.POINTER(_i)],
     "oiva_bsseval_time_stages": [_vp, _i, _fp],
+    "oiva_bsssets_create": [C.POINTER(_vp), _i, _i, C.POINTER(_i), _i, _i, _i, _i, _vp],
+    "oiva_bsssets_destroy": [_vp],
+    "oiva_bsssets_set_references": [_vp, _vp],
+    "oiva_bsssets_set_estimates": [_vp, _i, _vp],
+    "oiva_bsssets_take": [_vp, _vp, _i, _i],
+    "oiva_bsssets_prepare": [_vp],
+    "oiva_bsssets_evaluate": [_vp, _i, _i],
+    "oiva_bsssets_get_criteria": [_vp, _i, _i, _vp, _vp, _vp],
+    "oiva_bsssets_status": [_vp, C.POINTER(_i)],
+    "oiva_bsssets_get_gram": [_vp, _i, _vp, _vp, _vp],
+    "oiva_bsssets_get_filters": [_vp, _i, _vp, _vp],
+    "oiva_bsssets_counts": [_vp, C.POINTER(_ll), C.POINTER(_ll)],
+    "oiva_bsssets_phase_ms": [_vp, _fp],
     "oiva_room_create": [C.POINTER(_vp), _i, _i, _i, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _i, _vp],
     "oiva_room_destroy": [_vp],
     "oiva_room_compute_rir": [_vp],

@@ -16,33 +16,27 @@
 // permuted one and in a ragged one.
 //
 // A flagged room (a pivot that is not finite or <= N Lf eps max_diag(G)) is skipped by every later kernel; the others run on.
+#include "bss_arith.h"
 #include "oiva_device.h"
 
 namespace oiva {
 namespace {
 
-constexpr int kTile = 128;          // samples of the lag pass staged per step
-constexpr int kLagLanes = 256;      // lags per workgroup of the lag pass: one per lane
+constexpr int kLagLanes = kBssLagLanes;
 constexpr int kNb = kBssBlock;      // block size of the factorisation, the substitutions and the quadratic forms
-constexpr int kPad = kNb + 1;       // row stride of a staged tile: column reads by consecutive lanes spread over the banks
+constexpr int kPad = kBssPad;       // row stride of a staged tile
 constexpr int kPadT = kNb + 2;      // row stride of a transposed panel: 16-byte aligned groups of four rows
-constexpr int kMaxVec = kBssMaxSrc * kBssMaxSrc + kBssMaxSrc;
+constexpr int kMaxVec = kBssMaxVec;
 
 __device__ __forceinline__ bool room_flagged(const int* flag, int room) { return flag[room] != 0; }
 
 // ---------------------------------------------------------------------------------------------
-// lag sums: one workgroup = (room, segment, signal b_x, 256 lags); lane = lag tau; N accumulators, one per reference s_i.
-// A step stages kTile samples of the N references and kTile + 256 of b_x; its products are added in ascending u from zero and
-// the step's sum is then added to the segment's: chains of kTile and of kBssSeg / kTile additions, not one of kBssSeg (the SAR
-// subtracts numbers a thousand times its denominator and answers to the last bits of G, D and E: DESIGN.md 3.10).
+// lag sums: one workgroup = (room, segment, signal b_x, 256 lags); the chain of a lane is bss_lag_body (bss_arith.h)
 // ---------------------------------------------------------------------------------------------
 template <int N>
 __global__ __launch_bounds__(kLagLanes) void bss_lag_kernel(const double* __restrict__ ref, const double* __restrict__ est,
                                                              const BssRoom* __restrict__ rooms, const int2* __restrict__ segs,
                                                              double* __restrict__ part, double* __restrict__ Epart, int Lf) {
-    constexpr int NP = (N + 1) & ~1;
-    __shared__ __attribute__((aligned(16))) double sa[kTile][NP];
-    __shared__ double sb[kTile + kLagLanes];
     const int tid = threadIdx.x;
     const int2 rs = segs[blockIdx.x];
     const BssRoom r = rooms[rs.x];
@@ -55,37 +49,8 @@ __global__ __launch_bounds__(kLagLanes) void bss_lag_kernel(const double* __rest
     const int u0 = seg * kBssSeg;
     const int u1 = min(n, u0 + kBssSeg);
     double acc[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) acc[i] = 0.;
-    double accE = 0.;
-    for (int t0 = u0; t0 < u1; t0 += kTile) {
-        const int len = min(kTile, u1 - t0);
-        for (int idx = tid; idx < kTile * N; idx += kLagLanes) {
-            const int i = idx / kTile;
-            const int u = idx - i * kTile;
-            sa[u][i] = u < len ? a[(size_t)i * n + t0 + u] : 0.;
-        }
-        for (int idx = tid; idx < kTile + kLagLanes; idx += kLagLanes) {
-            const long long g = (long long)t0 + tau0 + idx;
-            sb[idx] = g < n ? b[g] : 0.;
-        }
-        __syncthreads();
-        double tile[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) tile[i] = 0.;
-        double tileE = 0.;
-#pragma unroll 4
-        for (int u = 0; u < len; ++u) {
-            const double bv = sb[u + tid];
-#pragma unroll
-            for (int i = 0; i < N; ++i) tile[i] = fma(sa[u][i], bv, tile[i]);
-            tileE = fma(bv, bv, tileE);
-        }
-#pragma unroll
-        for (int i = 0; i < N; ++i) acc[i] += tile[i];
-        accE += tileE;
-        __syncthreads();
-    }
+    double accE;
+    bss_lag_body<N>(a, b, n, u0, u1, tau0, acc, accE);
     const int tau = tau0 + tid;
     if (tau < Lf) {
 #pragma unroll
@@ -102,14 +67,10 @@ __global__ __launch_bounds__(256) void bss_lag_sum_kernel(const BssRoom* __restr
     const size_t per = (size_t)2 * N * N * Lf;
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e < per) {
-        double s = 0.;
-        for (int g = 0; g < r.nseg; ++g) s += part[r.part_off + (size_t)g * per + e];
-        lag[(size_t)blockIdx.y * per + e] = s;
+        lag[(size_t)blockIdx.y * per + e] = bss_seg_sum(part + r.part_off + e, per, r.nseg);
     }
     if (e < (size_t)N) {
-        double s = 0.;
-        for (int g = 0; g < r.nseg; ++g) s += Epart[((size_t)r.seg_off + g) * N + e];
-        E[(size_t)blockIdx.y * N + e] = s;
+        E[(size_t)blockIdx.y * N + e] = bss_seg_sum(Epart + (size_t)r.seg_off * N + e, N, r.nseg);
     }
 }
 
@@ -120,45 +81,15 @@ __global__ __launch_bounds__(256) void bss_lag_sum_kernel(const BssRoom* __restr
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bss_assemble_kernel(const double* __restrict__ lag, double* __restrict__ G, double* __restrict__ Gf,
                                                             double* __restrict__ Hf, double* __restrict__ thr, int g0, int N, int Lf) {
-    const int nt = N * Lf;
     const int room = g0 + blockIdx.z;
-    const double* lg = lag + (size_t)room * 2 * N * N * Lf;
-    const int col = blockIdx.x * 256 + threadIdx.x;
-    const int row = blockIdx.y;
-    if (row == 0 && col == 0) {
-        double md = 0.;
-        for (int i = 0; i < N; ++i) md = fmax(md, lg[((size_t)i * N + i) * Lf]);
-        thr[room] = (double)nt * 2.220446049250313e-16 * md;
-    }
-    if (col >= nt) return;
-    const int i = row / Lf, p = row - i * Lf;
-    const int j = col / Lf, q = col - j * Lf;
-    const int tau = p - q;
-    double v;
-    if (tau > 0)
-        v = lg[((size_t)j * N + i) * Lf + tau];
-    else if (tau < 0)
-        v = lg[((size_t)i * N + j) * Lf - tau];
-    else
-        v = lg[((size_t)max(i, j) * N + min(i, j)) * Lf];
-    const size_t at = ((size_t)blockIdx.z * nt + row) * nt + col;
-    G[at] = v;
-    Gf[at] = v;
-    if (i == j) Hf[(((size_t)blockIdx.z * N + j) * Lf + p) * Lf + q] = v;
+    bss_assemble_body(lag + (size_t)room * 2 * N * N * Lf, G, Gf, Hf, thr, room, blockIdx.z, N, Lf);
 }
 
 // C[b][k] = D_k and c[b][j][k] = D_k[j]: the right-hand sides, overwritten by the substitutions
 __global__ __launch_bounds__(256) void bss_init_rhs_kernel(const double* __restrict__ lag, double* __restrict__ C, double* __restrict__ c,
                                                             int g0, int N, int Lf) {
     const int room = g0 + blockIdx.y;
-    const int nt = N * Lf;
-    const int e = blockIdx.x * 256 + threadIdx.x;       // (k, j, p)
-    if (e >= N * nt) return;
-    const int k = e / nt, jp = e - k * nt;
-    const int j = jp / Lf, p = jp - j * Lf;
-    const double v = lag[((size_t)room * 2 * N + N + k) * nt + jp];
-    C[((size_t)room * N + k) * nt + jp] = v;
-    c[((((size_t)room * N + j) * N + k) * Lf) + p] = v;
+    bss_init_rhs_body(lag + ((size_t)room * 2 * N + N) * N * Lf, C, c, room, N, Lf);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -274,180 +205,42 @@ __global__ __launch_bounds__(256) void bss_chol_update_kernel(double* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
-// substitution with the factor of one matrix per workgroup, R <= 8 right-hand sides X (R, dim): forward L y = x, or (BWD)
-// backward L^T x = y.  Per block: the diagonal block by wave 0, lane = row, the solved element handed on by a shuffle; then the
-// product of the solved block with every tile beside it leaves the rows still to come.
+// substitution with the factor of one matrix per workgroup, R <= 8 right-hand sides X (R, dim): bss_trsv_body (bss_arith.h)
 // ---------------------------------------------------------------------------------------------
 template <bool BWD>
 __global__ __launch_bounds__(256) void bss_trsv_kernel(const double* __restrict__ A, long long stride, int dim, double* __restrict__ X,
                                                         int R, const int* flag, int g0, int per_room) {
-    __shared__ double T[kNb][kPad];
-    __shared__ double Y[kNb][kBssMaxSrc];
-    const int tid = threadIdx.x;
     if (room_flagged(flag, g0 + blockIdx.x / per_room)) return;
-    A += (size_t)blockIdx.x * stride;
-    X += (size_t)blockIdx.x * R * dim;
-    const int nblk = (dim + kNb - 1) / kNb;
-    for (int kk = 0; kk < nblk; ++kk) {
-        const int k = BWD ? nblk - 1 - kk : kk;
-        const int k0 = k * kNb;
-        for (int idx = tid; idx < kNb * kNb; idx += 256) {
-            const int r = idx / kNb, cc = idx - r * kNb;
-            T[r][cc] = (k0 + r < dim && cc <= r) ? A[(size_t)(k0 + r) * dim + k0 + cc] : (r == cc ? 1. : 0.);
-        }
-        __syncthreads();
-        if (tid < 64) {
-            const int m = tid;
-            double y[kBssMaxSrc];
-#pragma unroll
-            for (int r = 0; r < kBssMaxSrc; ++r) y[r] = (r < R && k0 + m < dim) ? X[(size_t)r * dim + k0 + m] : 0.;
-            for (int s = 0; s < kNb; ++s) {
-                const int cc = BWD ? kNb - 1 - s : s;
-                const double piv = T[cc][cc];
-                const double l = BWD ? (m < cc ? T[cc][m] : 0.) : (m > cc ? T[m][cc] : 0.);
-#pragma unroll
-                for (int r = 0; r < kBssMaxSrc; ++r) {
-                    const double t = __shfl(y[r], cc, 64) / piv;
-                    y[r] = m == cc ? t : fma(-l, t, y[r]);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < kBssMaxSrc; ++r) {
-                Y[m][r] = y[r];
-                if (r < R && k0 + m < dim) X[(size_t)r * dim + k0 + m] = y[r];
-            }
-        }
-        __syncthreads();
-        const int jbeg = BWD ? 0 : k + 1, jend = BWD ? k : nblk;
-        for (int j = jbeg; j < jend; ++j) {
-            const int j0 = j * kNb;
-            for (int idx = tid; idx < kNb * kNb; idx += 256) {
-                const int r = idx / kNb, cc = idx - r * kNb;
-                if (BWD)      // rows of block k, columns of block j: T[c][m]
-                    T[r][cc] = k0 + r < dim ? A[(size_t)(k0 + r) * dim + j0 + cc] : 0.;
-                else          // rows of block j, columns of block k: T[m][c]
-                    T[r][cc] = j0 + r < dim ? A[(size_t)(j0 + r) * dim + k0 + cc] : 0.;
-            }
-            __syncthreads();
-            const int m = tid & 63;
-            for (int r = tid >> 6; r < R; r += 4) {
-                double acc = 0.;
-                for (int cc = 0; cc < kNb; ++cc) acc = fma(BWD ? T[cc][m] : T[m][cc], Y[cc][r], acc);
-                if (j0 + m < dim) X[(size_t)r * dim + j0 + m] -= acc;
-            }
-            __syncthreads();
-        }
-    }
+    bss_trsv_body<BWD>(A + (size_t)blockIdx.x * stride, dim, X + (size_t)blockIdx.x * R * dim, R);
 }
 
-// ---------------------------------------------------------------------------------------------
 // quadratic forms v^T Q v of nvec vectors with one matrix Q (the unfactored G of a room, or -- SMALL -- its block G_jj): one
-// workgroup per 64 rows; lane = row, wave w owns vectors w, w + 4, ...  Per vector the block's share sum_m v[m] (Q v)[m] is
-// written, the rows added in ascending order; the criteria kernel adds the blocks.
-//   large: vector v < nd is d = C_k - embed_j(c_kj) for pair (k, j) = (v / N, v % N), or (v, v) when only the pairs k = j are
-//          evaluated (nd = N); vector nd + k is C_k
-//   small: vector k is c_kj, j the block
-// ---------------------------------------------------------------------------------------------
-template <bool SMALL>
-__device__ __forceinline__ double bss_vec(const double* __restrict__ C, const double* __restrict__ c, int room, int jblk, int v, int e,
-                                           int N, int Lf, int nd) {
-    if (SMALL) return c[(((size_t)room * N + jblk) * N + v) * Lf + e];
-    const int nt = N * Lf;
-    if (v >= nd) return C[((size_t)room * N + (v - nd)) * nt + e];
-    const int k = nd == N ? v : v / N, j = nd == N ? v : v - k * N;
-    const double big = C[((size_t)room * N + k) * nt + e];
-    const int ej = e - j * Lf;
-    return (ej >= 0 && ej < Lf) ? big - c[(((size_t)room * N + j) * N + k) * Lf + ej] : big;
-}
-
+// workgroup per 64 rows, bss_quad_body (bss_arith.h)
 template <bool SMALL>
 __global__ __launch_bounds__(256) void bss_quad_kernel(const double* __restrict__ G, const double* __restrict__ C, const double* __restrict__ c,
                                                         double* __restrict__ q, int N, int Lf, int nd, int nvec, const int* flag, int g0) {
-    __shared__ double T[kNb][kPad];
-    __shared__ double V[kNb][kMaxVec + 1];
-    const int tid = threadIdx.x;
     const int nt = N * Lf;
     const int loc = SMALL ? blockIdx.y / N : blockIdx.y;        // room within the group
     const int jblk = SMALL ? blockIdx.y % N : 0;
     const int room = g0 + loc;
     if (room_flagged(flag, room)) return;
-    const int dim = SMALL ? Lf : nt;
+    const int nrb = ((SMALL ? Lf : nt) + kNb - 1) / kNb;
     const double* Q = G + (size_t)loc * nt * nt + (SMALL ? (size_t)jblk * Lf * (nt + 1) : 0);
-    const int nrb = (dim + kNb - 1) / kNb;
-    const int r0 = blockIdx.x * kNb;
-    const int m = tid & 63, w = tid >> 6;
-    constexpr int kPer = (kMaxVec + 3) / 4;
-    double acc[kPer];
-#pragma unroll
-    for (int s = 0; s < kPer; ++s) acc[s] = 0.;
-    for (int c0 = 0; c0 < dim; c0 += kNb) {
-        for (int idx = tid; idx < kNb * kNb; idx += 256) {
-            const int r = idx / kNb, cc = idx - r * kNb;
-            T[r][cc] = (r0 + r < dim && c0 + cc < dim) ? Q[(size_t)(r0 + r) * nt + c0 + cc] : 0.;
-        }
-        for (int idx = tid; idx < kNb * nvec; idx += 256) {
-            const int cc = idx / nvec, v = idx - cc * nvec;
-            V[cc][v] = c0 + cc < dim ? bss_vec<SMALL>(C, c, room, jblk, v, c0 + cc, N, Lf, nd) : 0.;
-        }
-        __syncthreads();
-        for (int cc = 0; cc < kNb; ++cc) {
-            const double g = T[m][cc];
-#pragma unroll
-            for (int s = 0; s < kPer; ++s)
-                if (w + 4 * s < nvec) acc[s] = fma(g, V[cc][w + 4 * s], acc[s]);
-        }
-        __syncthreads();
-    }
-    // the rows of this block: V[m][v] <- v[m] * (Q v)[m], then one lane per vector adds the 64 rows in order
-#pragma unroll
-    for (int s = 0; s < kPer; ++s) {
-        const int v = w + 4 * s;
-        if (v < nvec) V[m][v] = r0 + m < dim ? bss_vec<SMALL>(C, c, room, jblk, v, r0 + m, N, Lf, nd) * acc[s] : 0.;
-    }
-    __syncthreads();
-    if (tid < nvec) {
-        double s = 0.;
-        for (int r = 0; r < kNb; ++r) s += V[r][tid];
-        q[((size_t)blockIdx.y * kMaxVec + tid) * nrb + blockIdx.x] = s;
-    }
+    bss_quad_body<SMALL>(Q, C, c, q + (size_t)blockIdx.y * kMaxVec * nrb, N, Lf, nd, nvec, room, jblk);
 }
 
-__device__ __forceinline__ double bss_db(double num, double den) { return den > 0. ? 10. * log10(num / den) : (double)INFINITY; }
-
-// one workgroup per (pair, room): the two inner products with D_k (lane-strided sums closed by the fixed tree of block_sum), the block sums of the quadratic forms, the three ratios
+// one workgroup per (pair, room): bss_criteria_body (bss_arith.h)
 __global__ __launch_bounds__(256) void bss_criteria_kernel(const double* __restrict__ lag, const double* __restrict__ E,
                                                             const double* __restrict__ C, const double* __restrict__ c,
                                                             const double* __restrict__ qL, const double* __restrict__ qS,
                                                             double* __restrict__ sdr, double* __restrict__ sir, double* __restrict__ sar,
                                                             int N, int Lf, int nd, const int* flag, int g0) {
-    __shared__ double red[kWaves];
-    const int tid = threadIdx.x;
     const int loc = blockIdx.y, room = g0 + loc;
     if (room_flagged(flag, room)) return;
-    const int v = blockIdx.x;
-    const int k = nd == N ? v : v / N, j = nd == N ? v : v - k * N;
     const int nt = N * Lf;
-    const double* Dk = lag + ((size_t)room * 2 * N + N + k) * nt;
-    const double* Ck = C + ((size_t)room * N + k) * nt;
-    const double* ckj = c + (((size_t)room * N + j) * N + k) * Lf;
-    double s1 = 0., s2 = 0.;
-    for (int e = tid; e < Lf; e += 256) s1 = fma(Dk[(size_t)j * Lf + e], ckj[e], s1);
-    for (int e = tid; e < nt; e += 256) s2 = fma(Dk[e], Ck[e], s2);
-    const double d_small = block_sum(s1, red);
-    const double d_big = block_sum(s2, red);
-    if (tid != 0) return;
     const int nrbL = (nt + kNb - 1) / kNb, nrbS = (Lf + kNb - 1) / kNb;
-    double a = 0., interf = 0., tot = 0.;
-    for (int r = 0; r < nrbS; ++r) a += qS[(((size_t)loc * N + j) * kMaxVec + k) * nrbS + r];
-    for (int r = 0; r < nrbL; ++r) interf += qL[((size_t)loc * kMaxVec + v) * nrbL + r];
-    for (int r = 0; r < nrbL; ++r) tot += qL[((size_t)loc * kMaxVec + nd + k) * nrbL + r];
-    const double Ek = E[(size_t)room * N + k];
-    const double res = Ek - 2. * d_small + a;
-    const double art = Ek - 2. * d_big + tot;
-    const size_t at = ((size_t)room * N + k) * N + j;
-    sdr[at] = bss_db(a, res);
-    sir[at] = N == 1 ? (double)INFINITY : bss_db(a, interf);
-    sar[at] = bss_db(tot, art);
+    bss_criteria_body(lag + ((size_t)room * 2 * N + N) * nt, E, C, c, qL + (size_t)loc * kMaxVec * nrbL,
+                      qS + (size_t)loc * N * kMaxVec * nrbS, sdr, sir, sar, N, Lf, nd, room);
 }
 
 }  // namespace

@@ -427,6 +427,22 @@ hipError_t launch_bss_criteria(hipStream_t s, const double* lag, const double* E
                                double* qL, double* qS, double* sdr, double* sir, double* sar, int g0, int rooms, int N, int Lf,
                                int diag_only, const int* flag);
 
+// Many estimate sets per reference set (kernels_bsssets.hip, bsssets.hip): the buffers of S consecutive sets lie one set after the
+// other, each laid out as oiva_bsseval's; G, Gf and Hf hold all B rooms and are shared by the sets.
+//   S sets of N signals each (sig, the sets sig_stride apart) against the references: part [room segment][set][k][i][Lf], Epart
+//   [room segment][set][k], then out (S, B, N, N, Lf) and E (S, B, N) with the segments added in order.  Epart = E = null: no energies
+hipError_t launch_bsssets_lags(hipStream_t s, const double* ref, const double* sig, long long sig_stride, const BssRoom* rooms,
+                               const int2* segs, long long total_segs, int B, int S, int N, int Lf, double* part, double* Epart,
+                               double* out, double* E);
+//   rlag (B, N, N, Lf) into G, Gf (to be factored), Hf (the diagonal blocks, to be factored) and thr of all B rooms
+hipError_t launch_bsssets_assemble(hipStream_t s, const double* rlag, double* G, double* Gf, double* Hf, double* thr, int B, int N, int Lf);
+//   C <- D, c <- D[j], then both through the factors Gf and Hf, for S sets
+hipError_t launch_bsssets_solve(hipStream_t s, const double* Gf, const double* Hf, const double* D, double* C, double* c, int B, int S, int N,
+                                int Lf, const int* flag);
+//   the quadratic forms, then crit: per set sdr, sir, sar (B, N, N) [room, estimate, reference]
+hipError_t launch_bsssets_criteria(hipStream_t s, const double* D, const double* E, const double* G, const double* C, const double* c,
+                                   double* qL, double* qS, double* crit, int B, int S, int N, int Lf, int diag_only, const int* flag);
+
 // Shoebox image-source rooms (kernels_room.hip, room.hip): impulse responses, premix and mix-down of B rooms of S
 // sources and M microphones, float64.  One record per room; every field is the room's own.
 constexpr int kRoomFdl = 81;          // taps of one image's windowed sinc

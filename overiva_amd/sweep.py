@@ -136,15 +136,17 @@ def _check_filler(filler, B):
 
 class SweepBatch(_lib.Handle):
     """the staged form of ``sweep_batch``: a ``RoomBatch`` and, for the room group at hand, a ``BatchSTFT``, the sweep handle
-    (``oiva_sweep``) and a ``BssEval``.
+    (``oiva_sweep``), a ``BssEval`` the device gather writes into and a ``BssEvalSets`` that evaluates what was gathered: the
+    group's references are prepared once, every later evaluation runs the estimate half alone.
 
     ``set_signals`` (the impulse responses, then the signals; ``max_group`` as ``RoomBatch.set_signals``), ``set_filler``, then per
     group g0: ``open_group``, ``convolve``, ``mix``, ``take_mix`` (-> the ``DeviceBatch`` X every solver borrows) and
-    ``evaluate(Y, reorder)`` for every state to be measured.  ``get_order`` / ``get_eval_signals`` read what the last
-    ``evaluate`` left."""
+    ``evaluate(Y, reorder)`` for every state to be measured -- or ``gather(Y, reorder, e)`` for several states and one
+    ``evaluate_sets(n)`` for all of them.  ``get_order`` / ``get_eval_signals`` read what the last ``evaluate`` or ``gather``
+    left."""
 
     _destroy = "oiva_sweep_destroy"
-    room = stft = ev = g0 = filler_gen = None
+    room = stft = ev = sets = g0 = filler_gen = None
     rooms = ()
 
     def __init__(self, room_dim, sources, mics, frame, hop=None, n_targets=1, fs=16000, max_order=17, absorption=0.35, c=343.0,
@@ -170,7 +172,8 @@ class SweepBatch(_lib.Handle):
         self.B, self.S, self.M, self.K = self.room.B, self.room.S, int(M), int(n_targets)
         self.frame, self.hop, self.ref_mic, self.Lf = int(frame), int(hop), int(ref_mic), int(filter_length)
         self.out_lengths = self.eval_lengths = self.group = self.filler = self.filler_keys = None
-        self.g0, self.stft, self.ev, self.rooms, self.last_C = None, None, None, (), 0
+        self.g0, self.stft, self.ev, self.sets, self.rooms, self.last_C = None, None, None, None, (), 0
+        self.reference_preparations = self.sets_evaluated = self.groups_without_sets = 0
 
     def set_signals(self, signals, max_group=0):
         """signals: B arrays (S, n_b); computes the impulse responses on first use; -> rooms per group"""
@@ -222,8 +225,10 @@ class SweepBatch(_lib.Handle):
             self.filler_gen.close()
         self.filler_gen = None
 
-    def open_group(self, g0=0):
-        """the handles of the group that starts at room g0 (those of the group before are closed)"""
+    def open_group(self, g0=0, max_sets=1):
+        """the handles of the group that starts at room g0 (those of the group before are closed); max_sets: the most states
+        that are gathered before one ``evaluate_sets``.  When the ``BssEvalSets`` handle cannot be made for lack of memory the
+        group evaluates every state with a full ``BssEval.run()`` instead (``groups_without_sets`` counts such groups)"""
         if self.group is None:
             raise RuntimeError("signals not set")
         if self.filler is None and self.filler_keys is None:
@@ -240,6 +245,15 @@ class SweepBatch(_lib.Handle):
                                               self.Lf, None))
         self.h = h
         self.ev = _metrics.BssEval([self.eval_lengths[b] for b in self.rooms], self.K + 1, self.Lf, device=self.device)
+        try:
+            self.sets = _metrics.BssEvalSets([self.eval_lengths[b] for b in self.rooms], self.K + 1, self.Lf, max_sets=max(1, int(max_sets)),
+                                             device=self.device)
+        except _lib.HipError as err:
+            if not _metrics._is_out_of_memory(err):
+                raise
+            self.sets = None
+            self.groups_without_sets += 1
+        self.max_sets, self.references_taken, self.pending = max(1, int(max_sets)), False, []
         self.g0, self.last_C = int(g0), 0
         if self.filler_keys is not None:
             self._draw_filler()
@@ -248,10 +262,14 @@ class SweepBatch(_lib.Handle):
 
     def close_group(self):
         _lib.Handle.close(self)
-        for part in (self.stft, self.ev, self.filler_gen):
+        if self.sets is not None:
+            prep, done = self.sets.counts()
+            self.reference_preparations += prep
+            self.sets_evaluated += done
+        for part in (self.stft, self.ev, self.sets, self.filler_gen):
             if part is not None:
                 part.close()
-        self.stft = self.ev = self.g0 = self.filler_gen = None
+        self.stft = self.ev = self.sets = self.g0 = self.filler_gen = None
         self.rooms = ()
 
     def close(self):
@@ -276,27 +294,59 @@ class SweepBatch(_lib.Handle):
 
     def evaluate(self, Y, reorder):
         """Y: a ``DeviceBatch`` of n_targets..M channels (X itself, or a plan's ``demix_device``) -> sdr, sir, sar
-        (rooms, K + 1) and perm (rooms, K + 1) of the open group, the permutation chosen on the host as ``bss_eval_batch`` does"""
+        (rooms, K + 1) and perm (rooms, K + 1) of the open group, the permutation chosen on the host as ``bss_eval_batch`` does:
+        one state, gathered into set 0 and evaluated at once"""
+        self.gather(Y, reorder, 0)
+        return self.evaluate_sets(1)[0]
+
+    def gather(self, Y, reorder, e):
+        """the synthesis of Y, ordered and aligned, into the ``BssEval`` handle (``oiva_sweep_evaluate``) and from there, device to
+        device, into set e; the group's first gather also takes the references and prepares them"""
         if Y.frames != self.stft.frames or Y.n_freq != self.stft.n_freq:
             raise ValueError(f"Y holds frames {Y.frames} x {Y.n_freq} bins, the group {self.stft.frames} x {self.stft.n_freq}")
+        if not 0 <= e < self.max_sets:
+            raise ValueError(f"set {e} is not in 0..{self.max_sets - 1}")
         _lib.check(self.lib.oiva_sweep_evaluate(self.h, self.stft.h, C.c_void_p(Y.ptr), int(Y.n_chan), 1 if reorder else 0, self.ev.h,
                                                 None if self.filler_gen is None else C.c_void_p(self.filler_gen.ptr)))
         self.last_C = int(Y.n_chan)
-        self.ev.run()
-        mats = self.ev.get_criteria()
+        if self.sets is None:                                      # no room for the sets: the full evaluation, now
+            self.ev.run()
+            self.reference_preparations += 1
+            self.sets_evaluated += 1
+            self.pending.append((e, self.ev.get_criteria()))
+            return
+        self.sets.take(self.ev, e, with_references=not self.references_taken)
+        if not self.references_taken:
+            self.sets.prepare()
+            self.references_taken = True
+
+    def evaluate_sets(self, n_sets):
+        """the gathered sets 0 .. n_sets - 1 in one set of launches -> a list of (sdr, sir, sar, perm) as ``evaluate`` gives"""
+        R = len(self.rooms)
+        if self.sets is None:
+            by_set = dict(self.pending)
+            self.pending = []
+            per_set = [by_set[e] for e in range(n_sets)]
+        else:
+            self.sets.evaluate(0, n_sets)
+            mats = self.sets.get_criteria(0, n_sets)
+            per_set = [tuple(m[:, e] for m in mats) for e in range(n_sets)]
         cols = np.arange(self.K + 1)
-        perm = np.stack([_metrics.best_permutation(mats[1][b]) for b in range(len(self.rooms))])
-        return tuple(np.stack([m[b][perm[b], cols] for b in range(len(self.rooms))]) for m in mats) + (perm,)
+        out = []
+        for mats in per_set:
+            perm = np.stack([_metrics.best_permutation(mats[1][b]) for b in range(R)])
+            out.append(tuple(np.stack([m[b][perm[b], cols] for b in range(R)]) for m in mats) + (perm,))
+        return out
 
     def get_order(self):
-        """test hook: (order, std), both (rooms, C), of the last ``evaluate``"""
+        """test hook: (order, std), both (rooms, C), of the last ``evaluate`` or ``gather``"""
         n = len(self.rooms) * self.last_C
         order, std = (C.c_int * max(n, 1))(), np.empty(max(n, 1))
         _lib.check(self.lib.oiva_sweep_get_order(self.h, order, _lib.ptr(std)))
         return np.array(list(order), dtype=int)[:n].reshape(len(self.rooms), -1), std[:n].reshape(len(self.rooms), -1)
 
     def get_eval_signals(self):
-        """test hook: (ref, est), two lists of (K + 1, m_b) arrays: what the last ``evaluate`` left in the ``BssEval`` handle"""
+        """test hook: (ref, est), two lists of (K + 1, m_b) arrays: what the last ``evaluate`` or ``gather`` left in the ``BssEval`` handle"""
         sizes = [(self.K + 1) * self.eval_lengths[b] for b in self.rooms]
         ref, est = np.empty(sum(sizes)), np.empty(sum(sizes))
         _lib.check(self.lib.oiva_sweep_get_signals(self.h, self.ev.h, _lib.ptr(ref), _lib.ptr(est)))
@@ -312,19 +362,22 @@ class SweepBatch(_lib.Handle):
 
 
 def _run_entry(sb, Xd, entry, monitor, init):
-    """one entry of ``algorithms`` on the open group -> (checkpoints, [evaluation per checkpoint], solver seconds, ogive info)"""
+    """one entry of ``algorithms`` on the open group -> (checkpoints, [evaluation per checkpoint], solver seconds, ogive info).
+    Every checkpoint is gathered into a set of its own as it is reached; the entry's sets are evaluated together at its end"""
     algo, n_iter, proj_back, reorder = entry["algo"], entry["n_iter"], entry["proj_back"], entry["reorder"]
     F, M, K = sb.stft.n_freq, sb.M, entry["n_src"]
     plan = (_batch.BatchPlan(len(sb.rooms), sb.stft.frames[0], F, M, K, entry["model"], device=sb.device) if sb.dense else
             _batch.RaggedBatchPlan(sb.stft.frames, F, M, K, entry["model"], device=sb.device))
-    marks, evals, extra = [], [], {}
+    marks, evals, extra, gathered = [], [], {}, []
     spent = [0.0, time.perf_counter()]      # solver seconds so far, start of the running stretch
 
     def look(epoch):
         plan.status()                                              # (waits for the iterations: they are queued, not run, on return)
         spent[0] += time.perf_counter() - spent[1]
         marks.append(epoch)
-        evals.append(sb.evaluate(plan.demix_device(proj_back), reorder))
+        sb.gather(plan.demix_device(proj_back), reorder, len(gathered))
+        gathered.append(len(evals))
+        evals.append(None)
         spent[1] = time.perf_counter()
 
     with plan:
@@ -354,6 +407,8 @@ def _run_entry(sb, Xd, entry, monitor, init):
                 plan.iterate(step)
                 epoch += step
         look(n_iter)
+    for at, res in zip(gathered, sb.evaluate_sets(len(gathered))):
+        evals[at] = res
     return marks, evals, spent[0], extra
 
 
@@ -463,9 +518,10 @@ def sweep_batch(signals, room_dim, sources, mics, frame, hop=None, algorithms=No
         else:
             sb.set_filler(filler)
         draw_noise = keys is not None and noise is None
+        watched = lambda e: monitor_convergence and e["algo"] != "auxiva_pca"      # noqa: E731
         results = [[] for _ in entries]
         for g0 in range(0, B, sb.group):
-            sb.open_group(g0)
+            sb.open_group(g0, max_sets=max([1] + [len(checkpoints(e["algo"], e["n_iter"], True)) for e in entries if watched(e)]))
             sb.convolve(g0)
             sb.mix(g0, sinr, snr, var, None if noise is None else [noise[b] for b in sb.rooms],
                    tuple(k[sb.rooms.start:sb.rooms.stop] for k in keys) if draw_noise else None)
@@ -476,10 +532,14 @@ def sweep_batch(signals, room_dim, sources, mics, frame, hop=None, algorithms=No
             for e, res in zip(entries, results):
                 res.append(_run_entry(sb, Xd, e, monitor_convergence, init))
         groups = [len(sb.room.group_rooms(g0)) for g0 in range(0, B, sb.group)]
+        phase_ms = sb.phase_ms()                                 # (of the last group's last calls)
+        sb.close_group()                                         # (the counts of the last group)
         _batch._info = {"algorithm": "sweep", "precision": "precise", "batched": B, "sharded": False, "n_mics": M, "n_targets": K,
                         "rooms_per_group": sb.group, "groups": groups, "algorithms": [e["name"] for e in entries],
-                        "filter_length": int(filter_length), "phase_ms": sb.phase_ms(),      # (of the last group's last calls)
-                        "noise": sb.room.noise_source}
+                        "filter_length": int(filter_length), "phase_ms": phase_ms, "noise": sb.room.noise_source,
+                        "evaluation": "bss_eval" if sb.groups_without_sets else "bss_eval_sets",
+                        "groups_without_sets": sb.groups_without_sets, "reference_preparations": sb.reference_preparations,
+                        "sets_evaluated": sb.sets_evaluated}
         n_samples = list(sb.out_lengths)
     out = []
     for e, per_group in zip(entries, results):
