@@ -21,6 +21,59 @@ __device__ __forceinline__ void load_wconj(const float2* __restrict__ What, int 
     }
 }
 
+// The same in two steps for the head of power_kernel: load_w_raw requests the lane's W as it lies in memory, with nothing
+// between the requests that depends on one of them (load_wconj's conjugation after every element makes hipcc wait for every
+// element: M * KP / 2 dependent round trips), finish_wconj forms the values load_wconj returns once they have all been asked for.
+// Even M and KP: columns k0 + 2p and k0 + 2p + 1 of a row are 16 adjacent, aligned bytes (k0 = blockIdx.z * KP is even, a row is
+// M * 8 bytes); otherwise 8-byte loads.  A column >= K is not branched around: column 0 is read in its place and the value
+// zeroed afterwards (for even M a pair that starts below K ends below M, inside the row).
+template <int M, int KP>
+struct WRaw {
+    static constexpr bool kWide = M % 2 == 0 && KP % 2 == 0;
+    float4 v4[kWide ? KP / 2 : 1][kWide ? M : 1];
+    float2 v2[kWide ? 1 : KP][kWide ? 1 : M];
+};
+template <int M, int KP>
+__device__ __forceinline__ void load_w_raw(const float2* __restrict__ What, int f, int k0, int K, WRaw<M, KP>& w) {
+    const float2* row0 = What + (size_t)f * M * M;
+    if constexpr (WRaw<M, KP>::kWide) {
+#pragma unroll
+        for (int p = 0; p < KP / 2; ++p) {
+            const int c = k0 + 2 * p < K ? k0 + 2 * p : 0;
+#pragma unroll
+            for (int m = 0; m < M; ++m) w.v4[p][m] = *reinterpret_cast<const float4*>(row0 + m * M + c);
+        }
+    } else {
+#pragma unroll
+        for (int kk = 0; kk < KP; ++kk) {
+            const int c = k0 + kk < K ? k0 + kk : 0;
+#pragma unroll
+            for (int m = 0; m < M; ++m) w.v2[kk][m] = row0[m * M + c];
+        }
+    }
+}
+template <int M, int KP>
+__device__ __forceinline__ void finish_wconj(const WRaw<M, KP>& w, int k0, int K, float (&wr)[KP][M], float (&wi)[KP][M]) {
+#pragma unroll
+    for (int kk = 0; kk < KP; ++kk) {
+        const bool on = k0 + kk < K;
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            float re, im;
+            if constexpr (WRaw<M, KP>::kWide) {
+                const float4 v = w.v4[kk / 2][m];
+                re = kk % 2 ? v.z : v.x;
+                im = kk % 2 ? v.w : v.y;
+            } else {
+                re = w.v2[kk][m].x;
+                im = w.v2[kk][m].y;
+            }
+            wr[kk][m] = on ? re : 0.f;
+            wi[kk][m] = -(on ? im : 0.f);
+        }
+    }
+}
+
 // y = sum_m conj(w_m) x_m
 template <int M>
 __device__ __forceinline__ void demix_one(const float (&wr)[M], const float (&wi)[M], const float (&xr)[M],

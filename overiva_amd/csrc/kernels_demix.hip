@@ -57,8 +57,13 @@ __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict_
     const int nsteps = (len + 3) >> 2;
     [[maybe_unused]] const int ngroups = (nsteps + kPowUnroll - 1) / kPowUnroll;      // (the plain instantiation's walk)
 
+    // conj(W) of the lane's bin, requested raw and finished when all of it is on its way (load_w_raw, demix_arith.h): one memory
+    // round trip instead of one per element.  Not where holding the raw words beside the finished ones costs the
+    // instantiation a wave per SIMD (hipcc's resource remarks: one source per pass at 10..16 channels 52..76 -> 65..85 registers,
+    // the streamed form with four sources 91 -> 118): pow_blocks_per_cu feeds the choice of the geometry, which stays.
+    constexpr bool kRawW = NT ? KP <= 2 : (KP >= 2 || M <= 9);
     float wr[KP][M], wi[KP][M];
-    load_wconj<M, KP>(What, fc, k0, K, wr, wi);
+    [[maybe_unused]] WRaw<M, KP> wraw;
 
     const size_t frame_stride = (size_t)F * M;
     [[maybe_unused]] const float2* pbase = X + (size_t)fc * M;
@@ -98,13 +103,23 @@ __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict_
             }
         };
         static_assert(kPowStages == 2, "the loop is unrolled over the stages by hand");
-        // (W has arrived before the first request leaves: with loads of registers still counted at the head of the loop hipcc
-        //  drains the queue there, first step included)
+        // Step 0 of X and W travel together and are waited for ONCE, in front of the loop: with loads of registers still counted
+        // at the head of the loop hipcc drains the queue there, every step's requests included, so W must have arrived before the
+        // loop -- but not before the first request leaves.  The queue is empty behind the wait: consume(0)'s counted wait finds
+        // step 0 landed and only step 1 outstanding.  The register fence keeps every use of W behind the wait.
+        if constexpr (kRawW) {
+            issue(0, 0);
+            load_w_raw<M, KP>(What, fc, k0, K, wraw);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            finish_wconj<M, KP>(wraw, k0, K, wr, wi);
+        } else {
+            load_wconj<M, KP>(What, fc, k0, K, wr, wi);
+        }
 #pragma unroll
         for (int kk = 0; kk < KP; ++kk)
 #pragma unroll
             for (int m = 0; m < M; ++m) asm volatile("" : "+v"(wr[kk][m]), "+v"(wi[kk][m]));
-        issue(0, 0);
+        if constexpr (!kRawW) issue(0, 0);
         int n = 0;
         for (; n + 2 <= nsteps; n += 2) {       // stage indices are compile-time constants in the unrolled body
             issue(n + 1, 1); consume(n, 0);
@@ -116,6 +131,12 @@ __global__ __launch_bounds__(kBlock) void power_kernel(const float2* __restrict_
         // kPowUnroll steps are loaded before any of them is consumed: a wave keeps kPowUnroll * 64 * M * 8
         // bytes in flight, which is what hides HBM latency here (more resident waves only thrash the L1,
         // because a lane's M*8 bytes arrive through M/2 separate dwordx4 requests to the same lines).
+        if constexpr (kRawW) {
+            load_w_raw<M, KP>(What, fc, k0, K, wraw);
+            finish_wconj<M, KP>(wraw, k0, K, wr, wi);
+        } else {
+            load_wconj<M, KP>(What, fc, k0, K, wr, wi);
+        }
         for (int g = 0; g < ngroups; ++g) {
             const int i = (rev ? ngroups - 1 - g : g) * kPowUnroll;
             float xr[kPowUnroll][M], xi[kPowUnroll][M];
