@@ -779,6 +779,44 @@ oiva_status oiva_rng_raw(int device, unsigned long long key0, unsigned long long
 oiva_status oiva_rng_room_mix(oiva_room *room, int g0, int K, double sinr, double snr, int ref_mic, const double *sources_var,
                               const unsigned long long *key0, const unsigned long long *key1);
 
+/*
+ * Decay curve and reverberation time of many impulse responses on the device (decay.hip, kernels_decay.hip; DESIGN.md 3.14;
+ * overiva_amd/acoustics.py), all arithmetic in float64.  For a response h[0..L-1]: the Schroeder integral
+ * E[n] = sum_{k >= n} h[k]^2, summed in an order that is a function of (n, L) alone; theta_a = E[0] 10^(-start_db / 10) and
+ * theta_b = E[0] 10^(-(start_db + decay_db) / 10), both factors formed once on the host; i_a, i_b = the smallest n with
+ * E[n] <= theta_a, theta_b (-1: none, and both -1 for an all-zero response); sum_d, sum_nd = the sums of D[n] = 10 log10(E[n] / E[0])
+ * and of n D[n] over theta_b < E[n] <= theta_a.  The estimates follow on the host: (60 / decay_db) (i_b - i_a) / fs, and
+ * -60 / (m fs) with m the least-squares slope of D over [i_a, i_b).
+ * One oiva_decay handle = n_resp responses (1..2^22) of lengths[i] samples (1..2^24), packed one after the other.
+ *   oiva_decay_set_host  : the packed samples (sum lengths) from the host
+ *   oiva_decay_set_dev   : ... where they lie on the device: borrowed, must stay valid until the run
+ *   oiva_decay_set_room  : ... the room handle's own impulse responses, S M responses of Lr_b samples per room as
+ *                          oiva_room_get_rir lays them out; no copy.  OIVA_ERR_STATE before oiva_room_compute_rir (or after new
+ *                          absorptions), OIVA_ERR_ARG when device or table of lengths are not this handle's
+ *   oiva_decay_run       : fs > 0, start_db >= 0, decay_db > 0 (finite); keep_curve != 0 also writes every E[n]
+ *   oiva_decay_get       : e0, i_a, i_b, sum_d, sum_nd (n_resp each; each may be NULL) of the last run
+ *   oiva_decay_get_curve : the packed curves (sum lengths); OIVA_ERR_STATE unless the last run kept them
+ *   oiva_decay_ms        : device ms of the kernel of the last run
+ *   oiva_decay_room_set_absorption : new wall absorptions (B, 6) for a room handle: its impulse responses become stale, so
+ *                          oiva_room_compute_rir may run again on the same handle (k_max, the lengths and the device buffers are
+ *                          kept: they do not depend on the absorption); any convolved or mixed group is dropped, and
+ *                          oiva_room_convolve returns OIVA_ERR_STATE until the responses are computed.  Without this call a room
+ *                          handle computes its responses once, as before
+ * A response's results do not depend on the other responses, on its place in the handle or on the launch.  Every entry checks its
+ * arguments before any device call and is synchronous.
+ */
+typedef struct oiva_decay oiva_decay;
+oiva_status oiva_decay_create(oiva_decay **out, int device, int n_resp, const int *lengths, void *stream);
+oiva_status oiva_decay_destroy(oiva_decay *p);
+oiva_status oiva_decay_set_host(oiva_decay *p, const double *host_packed);
+oiva_status oiva_decay_set_dev(oiva_decay *p, const void *dev_packed);
+oiva_status oiva_decay_set_room(oiva_decay *p, oiva_room *room);
+oiva_status oiva_decay_run(oiva_decay *p, double fs, double start_db, double decay_db, int keep_curve);
+oiva_status oiva_decay_get(oiva_decay *p, double *e0, int *i_a, int *i_b, double *sum_d, double *sum_nd);
+oiva_status oiva_decay_get_curve(oiva_decay *p, double *curve_host_packed);
+oiva_status oiva_decay_ms(oiva_decay *p, float *ms);
+oiva_status oiva_decay_room_set_absorption(oiva_room *room, const double *absorption6);
+
 #ifdef __cplusplus
 }
 #endif

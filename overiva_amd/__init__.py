@@ -13,6 +13,7 @@ onolab-tmu/overiva behind the reference's own Python signatures.
     from overiva_amd import simulate_batch, rir_batch   # shoebox image-source rooms for many rooms per call; the algorithm of DESIGN.md 3.11
     from overiva_amd import sweep_batch        # geometry to SDR curves, every hand-over on the device
     from overiva_amd import standard_normal_batch   # seeded normals drawn on the device: the noise and filler of seed=...
+    from overiva_amd import measure_rt60_batch, absorption_for_rt60   # decay curve and RT60 of every response; the absorption for a wanted RT60
 
 Host code is Python (as the reference is); all arithmetic on the path runs in hand-written HIP
 kernels reached through the C ABI of ``liboveriva_hip.so`` (``include/overiva_hip.h``).  There is
@@ -25,6 +26,7 @@ from . import _lib as _lib_mod
 _lib_mod._set_ipc_env_at_import()
 
 from ._lib import HipError, HipLibraryMissing  # noqa: E402,F401
+from .acoustics import DecayBatch, absorption_for_rt60, edc_batch, measure_rt60_batch, truncation_horizon  # noqa: E402,F401
 from .auxiva_pca import auxiva_pca  # noqa: F401
 from .batch import BatchPlan, DeviceBatch, RaggedBatchPlan, last_batch_info, ogive_batch, overiva_batch, overiva_batch_ragged  # noqa: F401
 from .ilrma import ilrma, ilrma_batch  # noqa: F401
@@ -40,5 +42,5 @@ from .separate import BatchSTFT, separate_batch  # noqa: F401
 from .sweep import SweepBatch, sweep_batch  # noqa: F401
 from .sharded import BinShardedSolver, disable_bin_sharding, enable_bin_sharding, shard_bounds  # noqa: F401
 
-__all__ = ["overiva", "separate_batch", "BatchSTFT", "DeviceBatch", "overiva_batch", "overiva_batch_ragged", "ogive_batch", "auxiva_pca_batch", "ilrma_batch", "ilrma", "bss_eval_batch", "bss_eval_sources", "bss_eval_sets_batch", "bss_eval_sets", "BssEvalSets", "simulate_batch", "rir_batch", "RoomBatch", "sweep_batch", "SweepBatch", "standard_normal_batch", "DeviceNormal", "last_batch_info", "BatchPlan", "RaggedBatchPlan", "auxiva_pca", "ogive", "Plan", "DeviceX", "BinShardedSolver", "enable_bin_sharding", "disable_bin_sharding",
+__all__ = ["overiva", "separate_batch", "BatchSTFT", "DeviceBatch", "overiva_batch", "overiva_batch_ragged", "ogive_batch", "auxiva_pca_batch", "ilrma_batch", "ilrma", "bss_eval_batch", "bss_eval_sources", "bss_eval_sets_batch", "bss_eval_sets", "BssEvalSets", "simulate_batch", "rir_batch", "RoomBatch", "sweep_batch", "SweepBatch", "standard_normal_batch", "DeviceNormal", "measure_rt60_batch", "edc_batch", "DecayBatch", "absorption_for_rt60", "truncation_horizon", "last_batch_info", "BatchPlan", "RaggedBatchPlan", "auxiva_pca", "ogive", "Plan", "DeviceX", "BinShardedSolver", "enable_bin_sharding", "disable_bin_sharding",
            "shard_bounds", "release_cached_buffers", "set_device", "get_device", "set_precision", "get_precision", "last_solver_info", "HipError", "HipLibraryMissing"]

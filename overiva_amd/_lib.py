@@ -207,6 +207,16 @@ SIGNATURES = {
     "oiva_rng_ptr": [_vp, C.POINTER(_vp)],
     "oiva_rng_raw": [_i, _u64, _u64, _u64, _u64, _i, _vp],
     "oiva_rng_room_mix": [_vp, _i, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp],
+    "oiva_decay_create": [C.POINTER(_vp), _i, _i, C.POINTER(_i), _vp],
+    "oiva_decay_destroy": [_vp],
+    "oiva_decay_set_host": [_vp, _vp],
+    "oiva_decay_set_dev": [_vp, _vp],
+    "oiva_decay_set_room": [_vp, _vp],
+    "oiva_decay_run": [_vp, C.c_double, C.c_double, C.c_double, _i],
+    "oiva_decay_get": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "oiva_decay_get_curve": [_vp, _vp],
+    "oiva_decay_ms": [_vp, _fp],
+    "oiva_decay_room_set_absorption": [_vp, _vp],
 }
 
 

@@ -549,6 +549,25 @@ hipError_t launch_rng_raw(hipStream_t s, unsigned long long k0, unsigned long lo
 int room_mix_body(oiva_room* p, int g0, int K, double sinr, double snr, int ref_mic, const double* sources_var,
                   const double* noise_host, const unsigned long long* key0, const unsigned long long* key1);
 
+// The decay measurement (kernels_decay.hip, decay.hip): Schroeder integral, threshold crossings and the masked sums
+// of the fit for a packed batch of responses, float64.  One record per response; every result is a function of the response's own
+// samples and length.
+constexpr int kDecayTile = 1024;            // samples per tile, counted from sample 0: kBlock lanes of 4 consecutive samples
+constexpr int kDecayMaxLen = 1 << 24;       // samples of one response
+constexpr int kDecayMaxResp = 1 << 22;      // responses of one handle
+struct DecayRec {
+    long long off;       // first sample of the response in the packed input (and in the packed curve)
+    int len;             // its length
+    int pad;
+};
+//   e0 (n_resp), idx (n_resp, 2) = i_a, i_b (-1: none), sums (n_resp, 2) = sum D, sum n D over theta_b < E[n] <= theta_a with
+//   theta = E[0] * fa, E[0] * fb; curve: null or packed like `in`
+hipError_t launch_decay(hipStream_t s, const DecayRec* recs, int n_resp, const double* in, double fa, double fb, double* curve, double* e0,
+                        int* idx, double* sums);
+//   binds n_resp responses that lie packed at `dev` on `device` (borrowed) to a decay handle: OIVA_ERR_ARG unless the device and
+//   the table of lengths are the handle's (decay.hip; the caller is oiva_decay_set_room in room.hip)
+int decay_bind(oiva_decay* p, int device, const double* dev, const int* lengths, int n_resp);
+
 // dense complex128 <-> complex64 conversion on the device
 hipError_t launch_cast_c128_to_c64(hipStream_t s, const double2* in, float2* out, long long n);
 hipError_t launch_cast_c64_to_c128(hipStream_t s, const float2* in, double2* out, long long n);

@@ -6,6 +6,8 @@
 //   set_signals : packed signals (sum_b S n_b) float64, host -> device; sizes the transforms and the room groups
 //   convolve    : one group of rooms, room by room: pad | D2Z of the S signals and the S M responses | product | Z2D | unpack
 //   mix         : one group of rooms, room by room: standard deviations at ref_mic | weighted sums -> mix, ref
+//   oiva_decay_room_set_absorption : new wall absorptions: the responses become stale and compute_rir may run again (the image
+//                 kernel alone: k_max, the lengths and the buffers stay); oiva_decay_set_room lends the responses to a decay handle
 // The convolution is ONE transform per signal, of nfft_b = the power of two >= n_b + Lr_b - 1 points: a room's plans follow from
 // its own (nfft_b, S, M), and rooms with the same nfft share them.  When the premix of all rooms does not fit the device (or
 // max_group asks for less) the rooms go through convolve and mix in groups; a room's bits do not depend on the grouping, on B or
@@ -367,6 +369,13 @@ oiva_status oiva_room_compute_rir(oiva_room* p) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null handle");
     OIVA_NEED(!p->have_rir, OIVA_ERR_STATE, "the impulse responses of this handle are computed already");
     DeviceGuard guard(p->device);
+    if (p->rir) {      // after new absorptions: k_max, the lengths and the buffer do not depend on them
+        const int rc = stage_rir(p);
+        if (rc) return rc;
+        OIVA_TRY_HIP(hipStreamSynchronize(p->stream));
+        p->have_rir = true;
+        return OIVA_OK;
+    }
     int rc = stage_kmax(p);
     if (rc) return rc;
     std::vector<int> kmax(p->B);
@@ -480,6 +489,7 @@ oiva_status oiva_room_groups(oiva_room* p, int* rooms_per_group) {
 oiva_status oiva_room_convolve(oiva_room* p, int g0) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null handle");
     OIVA_NEED(p->have_sig, OIVA_ERR_STATE, "signals not set");
+    OIVA_NEED(p->have_rir, OIVA_ERR_STATE, "the absorptions changed: compute_rir has not run since");
     OIVA_NEED(g0 >= 0 && g0 < p->B && g0 % p->group == 0, OIVA_ERR_ARG, "g0 must be the first room of a group");
     DeviceGuard guard(p->device);
     std::fill(p->convolved.begin(), p->convolved.end(), 0);      // (one premix buffer: the group before is gone)
@@ -523,6 +533,7 @@ oiva_status oiva_room_time_stages(oiva_room* p, int n, int K, double sinr, doubl
     OIVA_NEED(K >= 1 && K <= p->S, OIVA_ERR_ARG, "n_targets must be in 1..S");
     OIVA_NEED(ref_mic >= 0 && ref_mic < p->M, OIVA_ERR_ARG, "ref_mic must be in 0..M-1");
     OIVA_NEED(p->have_sig, OIVA_ERR_STATE, "signals not set");
+    OIVA_NEED(p->have_rir, OIVA_ERR_STATE, "the absorptions changed: compute_rir has not run since");
     std::vector<double> scale;
     double sigma_n = 0.;
     int rc = mix_scales(p, K, sinr, snr, nullptr, &scale, &sigma_n);
@@ -553,6 +564,29 @@ oiva_status oiva_room_time_stages(oiva_room* p, int n, int K, double sinr, doubl
     for (int s = 0; s < kStages; ++s) per_stage_ms[s] = (float)(sum[s] / n);
     const int last_g0 = (p->B - 1) / p->group * p->group;
     p->convolved[last_g0] = p->mixed[last_g0] = 1;
+    return OIVA_OK;
+}
+
+// ---- the decay measurement's view of the room handle (oiva_decay_*, decay.hip) ---------------------------------
+oiva_status oiva_decay_set_room(oiva_decay* decay, oiva_room* p) {
+    OIVA_NEED(decay && p, OIVA_ERR_ARG, "null handle");
+    OIVA_NEED(p->have_rir, OIVA_ERR_STATE, "compute_rir has not run");
+    std::vector<int> lengths;
+    lengths.reserve((size_t)p->B * p->S * p->M);
+    for (const RoomRec& r : p->rooms) lengths.insert(lengths.end(), (size_t)p->S * p->M, r.Lr);
+    return decay_bind(decay, p->device, p->rir, lengths.data(), (int)lengths.size());
+}
+
+oiva_status oiva_decay_room_set_absorption(oiva_room* p, const double* absorption6) {
+    OIVA_NEED(p && absorption6, OIVA_ERR_ARG, "null argument");
+    for (int i = 0; i < p->B * 6; ++i) OIVA_NEED(absorption6[i] >= 0. && absorption6[i] < 1., OIVA_ERR_ARG, "absorption must be in [0, 1)");
+    DeviceGuard guard(p->device);
+    for (int b = 0; b < p->B; ++b)
+        for (int w = 0; w < 6; ++w) p->rooms[b].beta[w] = std::sqrt(1. - absorption6[b * 6 + w]);
+    p->have_rir = false;
+    std::fill(p->convolved.begin(), p->convolved.end(), 0);
+    std::fill(p->mixed.begin(), p->mixed.end(), 0);
+    OIVA_TRY_HIP(hipMemcpy(p->rooms_dev, p->rooms.data(), (size_t)p->B * sizeof(RoomRec), hipMemcpyHostToDevice));
     return OIVA_OK;
 }
 

@@ -85,6 +85,16 @@ def _check_geometry(room_dim, sources, mics, fs, max_order, absorption, c, rir_l
             raise ValueError(f"{name} must be a finite number > 0, got {v!r}")
     if not _is_int(max_order) or not 0 <= max_order <= MAX_ORDER:
         raise ValueError(f"max_order must be an integer in 0..{MAX_ORDER}, got {max_order!r}")
+    a = _check_absorption(absorption, B)
+    if rir_length is not None and (not _is_int(rir_length) or rir_length < 1):
+        raise ValueError(f"rir_length must be None or an integer >= 1, got {rir_length!r}")
+    if rir_length is not None and rir_length > MAX_RIR:
+        raise ValueError(f"rir_length must be at most {MAX_RIR}, got {rir_length}")
+    return room_dim, sources, mics, a, float(fs), float(c), int(max_order), rir_length and int(rir_length)
+
+
+def _check_absorption(absorption, B):
+    """a scalar, (batch,) or (batch, 6) -> float64 C-contiguous (batch, 6)"""
     a = _real_array("absorption", absorption)
     if a.ndim == 0:
         a = np.full((B, 6), float(a))
@@ -94,11 +104,7 @@ def _check_geometry(room_dim, sources, mics, fs, max_order, absorption, c, rir_l
         raise ValueError(f"absorption must be a scalar, (batch,) or (batch, 6), got shape {a.shape}")
     if np.any(a < 0) or np.any(a >= 1):
         raise ValueError("absorption must be in [0, 1)")
-    if rir_length is not None and (not _is_int(rir_length) or rir_length < 1):
-        raise ValueError(f"rir_length must be None or an integer >= 1, got {rir_length!r}")
-    if rir_length is not None and rir_length > MAX_RIR:
-        raise ValueError(f"rir_length must be at most {MAX_RIR}, got {rir_length}")
-    return room_dim, sources, mics, np.ascontiguousarray(a), float(fs), float(c), int(max_order), rir_length and int(rir_length)
+    return np.ascontiguousarray(a)
 
 
 def _check_signals(signals, B, S):
@@ -224,6 +230,28 @@ class RoomBatch(_lib.Handle):
         _lib.check(self.lib.oiva_room_get_rir(self.h, _lib.ptr(flat)))
         off = np.concatenate([[0], np.cumsum(sizes)])
         return [flat[off[b]:off[b + 1]].reshape(self.S, self.M, L) for b, L in enumerate(self.rir_lengths)]
+
+    def set_absorption(self, absorption):
+        """new wall absorptions -- a scalar, (B,) or (B, 6), as the constructor takes them: the impulse responses become stale and
+        ``compute_rir`` may run again on this handle (k_max, the lengths and the device buffers stay: they do not depend on the
+        absorption).  Any convolved or mixed group is dropped; ``convolve`` raises until ``compute_rir`` has run"""
+        a6 = _check_absorption(absorption, self.B)
+        _lib.check(self.lib.oiva_decay_room_set_absorption(self.h, _lib.ptr(a6)))
+
+    def measure_rt60(self, decay_db=20.0, start_db=5.0):
+        """``(rt60_cross, rt60_fit)`` of every impulse response, measured where it lies (``measure_rt60_batch()``, DESIGN.md
+        3.14): two lists of B arrays (S, M).  Only the estimates' ingredients leave the device"""
+        from . import acoustics
+
+        fs, decay_db, start_db = acoustics._check_params(self.fs, decay_db, start_db)
+        if self.rir_lengths is None:
+            raise RuntimeError("compute_rir has not run")
+        pairs = self.S * self.M
+        with acoustics.DecayBatch([L for L in self.rir_lengths for _ in range(pairs)], device=self.device) as d:
+            cross, fit, _, _ = d.set_room(self).run(fs, start_db, decay_db).rt60()
+            _batch._info = dict(d.info(), n_rooms=self.B, n_sources=self.S, n_mics=self.M)
+        shape = (self.B, self.S, self.M)
+        return list(cross.reshape(shape)), list(fit.reshape(shape))
 
     def set_signals(self, signals, max_group=0):
         """signals: B arrays (S, n_b); sizes the room groups"""
