@@ -616,7 +616,7 @@ oiva_status oiva_bsseval_status(oiva_bsseval *p, int *status);
 oiva_status oiva_bsseval_time_stages(oiva_bsseval *p, int n, float *per_stage_ms);
 
 /*
- * BSS Eval of many estimate sets against one set of references (bsssets.hip, kernels_bsssets.hip): the half of
+ * BSS Eval of many estimate sets against one set of references (bsseval.hip, kernels_bsseval.hip): the half of
  * oiva_bsseval that depends on the references alone -- their lag sums, the Gram matrix G, its Cholesky factor and the factors of
  * its N diagonal blocks -- is made once (prepare) and up to max_sets estimate sets are evaluated against it, any number of them
  * per set of launches (evaluate).  One handle = one (lengths, N, filter_length, max_sets), limits as oiva_bsseval_create and

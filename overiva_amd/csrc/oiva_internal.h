@@ -397,51 +397,39 @@ hipError_t launch_bstft_from_tfc(hipStream_t s, const float2* Y, float2* spec, l
 hipError_t launch_bstft_overlap_add(hipStream_t s, const float* frames, const float* win, float* y, const BstftRoom* rooms, int B,
                                     long long n_out, int C, int L, int hop);
 
-// BSS Eval (kernels_bsseval.hip, bsseval.hip): SDR / SIR / SAR of B rooms, float64.  One record per room; a dense batch is the
-// special case of equal records.  Every field is a function of the room's own (n, N, Lf).
+// BSS Eval (kernels_bsseval.hip, bsseval.hip): SDR / SIR / SAR of S sets of estimates against one set of references, B rooms,
+// float64.  One record per room; a dense batch is the special case of equal records.  Every field is a function of the room's own
+// (n, N, Lf).  The buffers of consecutive sets lie one set after the other; G, Gf and Hf hold the rooms of one group and are shared
+// by the sets; a single evaluation (oiva_bsseval) is one set, a sets handle (oiva_bsssets) one group.
 constexpr int kBssMaxSrc = 8;       // sources per room
 constexpr int kBssMaxFilter = 512;  // filter taps
 constexpr int kBssSeg = 2048;       // samples per segment of the lag sums: segment g of a room is [g * kBssSeg, min(n, (g + 1) * kBssSeg))
 constexpr int kBssBlock = 64;       // block size of the Cholesky factorisation, the substitutions and the quadratic forms
 struct BssRoom {
-    long long sig_off;   // first element of the room's (N, n) signals in the packed references / estimates
-    long long part_off;  // its partial lag sums [nseg][2N][N][Lf]
+    long long sig_off;   // first element of the room's (N, n) signals in the packed signals of a set
     int n;               // samples
     int nseg;            // ceil(n / kBssSeg)
     int seg_off;         // its first segment in the flat list of (room, segment) pairs
     int pad;
 };
-//   part / Epart per segment, then lag (B, 2N, N, Lf) and E (B, N) with the segments added in order
-hipError_t launch_bss_lags(hipStream_t s, const double* ref, const double* est, const BssRoom* rooms, const int2* segs,
-                           long long total_segs, int B, int N, int Lf, double* part, double* Epart, double* lag, double* E);
-//   rooms g0 .. g0 + rooms - 1 into the group's G, Gf (to be factored), Hf (the diagonal blocks, to be factored); thr, C and c
-//   are indexed by the room of the batch
-hipError_t launch_bss_assemble(hipStream_t s, const double* lag, double* G, double* Gf, double* Hf, double* thr, double* C, double* c,
-                               int g0, int rooms, int N, int Lf);
+//   S sets of N signals each (sig, the sets sig_stride apart) against the references: part [room segment][set][k][i][Lf], Epart
+//   [room segment][set][k], then out (S, B, N, N, Lf) and E (S, B, N) with the segments added in order
+hipError_t launch_bss_lags(hipStream_t s, const double* ref, const double* sig, long long sig_stride, const BssRoom* rooms,
+                           const int2* segs, long long total_segs, int B, int S, int N, int Lf, double* part, double* Epart, double* out,
+                           double* E);
+//   rooms g0 .. g0 + rooms - 1 of rlag (B, N, N, Lf) into the group's G, Gf (to be factored), Hf (the diagonal blocks, to be
+//   factored); thr is indexed by the room of the batch
+hipError_t launch_bss_assemble(hipStream_t s, const double* rlag, double* G, double* Gf, double* Hf, double* thr, int g0, int rooms, int N,
+                               int Lf);
 //   nmat dense dim x dim matrices, lower triangle in place; matrix m belongs to room g0 + m / per_room, whose flag a bad pivot sets
 hipError_t launch_bss_cholesky(hipStream_t s, double* A, int nmat, int dim, int* flag, const double* thr, int g0, int per_room);
-//   X (nmat, R, dim) <- (L L^T)^-1 X
-hipError_t launch_bss_solve(hipStream_t s, const double* A, int nmat, int dim, double* X, int R, const int* flag, int g0, int per_room);
-//   the quadratic forms of the group's rooms, then sdr / sir / sar (B, N, N) [room, estimate, reference]
-hipError_t launch_bss_criteria(hipStream_t s, const double* lag, const double* E, const double* G, const double* C, const double* c,
-                               double* qL, double* qS, double* sdr, double* sir, double* sar, int g0, int rooms, int N, int Lf,
-                               int diag_only, const int* flag);
-
-// Many estimate sets per reference set (kernels_bsssets.hip, bsssets.hip): the buffers of S consecutive sets lie one set after the
-// other, each laid out as oiva_bsseval's; G, Gf and Hf hold all B rooms and are shared by the sets.
-//   S sets of N signals each (sig, the sets sig_stride apart) against the references: part [room segment][set][k][i][Lf], Epart
-//   [room segment][set][k], then out (S, B, N, N, Lf) and E (S, B, N) with the segments added in order.  Epart = E = null: no energies
-hipError_t launch_bsssets_lags(hipStream_t s, const double* ref, const double* sig, long long sig_stride, const BssRoom* rooms,
-                               const int2* segs, long long total_segs, int B, int S, int N, int Lf, double* part, double* Epart,
-                               double* out, double* E);
-//   rlag (B, N, N, Lf) into G, Gf (to be factored), Hf (the diagonal blocks, to be factored) and thr of all B rooms
-hipError_t launch_bsssets_assemble(hipStream_t s, const double* rlag, double* G, double* Gf, double* Hf, double* thr, int B, int N, int Lf);
-//   C <- D, c <- D[j], then both through the factors Gf and Hf, for S sets
-hipError_t launch_bsssets_solve(hipStream_t s, const double* Gf, const double* Hf, const double* D, double* C, double* c, int B, int S, int N,
-                                int Lf, const int* flag);
-//   the quadratic forms, then crit: per set sdr, sir, sar (B, N, N) [room, estimate, reference]
-hipError_t launch_bsssets_criteria(hipStream_t s, const double* D, const double* E, const double* G, const double* C, const double* c,
-                                   double* qL, double* qS, double* crit, int B, int S, int N, int Lf, int diag_only, const int* flag);
+//   C <- D, c <- D[j], then both through the group's factors Gf and Hf, for S sets of (B, N, N Lf)
+hipError_t launch_bss_solve(hipStream_t s, const double* Gf, const double* Hf, const double* D, double* C, double* c, int g0, int rooms,
+                            int B, int S, int N, int Lf, const int* flag);
+//   the quadratic forms of the group's rooms, then crit: per set sdr, sir, sar (B, N, N) [room, estimate, reference]
+hipError_t launch_bss_criteria(hipStream_t s, const double* D, const double* E, const double* G, const double* C, const double* c,
+                               double* qL, double* qS, double* crit, int g0, int rooms, int B, int S, int N, int Lf, int diag_only,
+                               const int* flag);
 
 // Shoebox image-source rooms (kernels_room.hip, room.hip): impulse responses, premix and mix-down of B rooms of S
 // sources and M microphones, float64.  One record per room; every field is the room's own.

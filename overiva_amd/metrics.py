@@ -16,7 +16,7 @@ falls back to ``lstsq``; here a room whose factorisation meets a pivot that is n
 A room's bits do not depend on B, on its place in the batch or on the lengths of the other rooms.
 
 ``bss_eval_sets_batch()`` and ``bss_eval_sets()`` evaluate E sets of estimates against one set of references
-(``oiva_bsssets_*``, csrc/kernels_bsssets.hip): the lag sums of the references, G and its factors are made once per room and the
+(``oiva_bsssets_*``, the same kernels with a set axis): the lag sums of the references, G and its factors are made once per room and the
 E sets go through one set of launches.  For every room and set the results have the bits of ``bss_eval_batch`` on that set alone.
 """
 import ctypes as C
@@ -103,16 +103,11 @@ def best_permutation(sir):
     return np.array(best, dtype=int)
 
 
-class BssEval(_lib.Handle):
-    """one handle = B rooms of ``lengths[b]`` samples x N sources and one ``filter_length`` on one GPU (``oiva_bsseval``).
+class _BssHandle(_lib.Handle):
+    """what ``BssEval`` and ``BssEvalSets`` share: B rooms of ``lengths[b]`` samples x N sources and one ``filter_length`` on one
+    GPU.  A subclass names its C functions by ``_prefix`` and gives ``create`` its own last-but-one argument (``extra``)."""
 
-    Stages: ``set_signals``, then ``correlate``, ``factor``, ``solve``, ``criteria`` in order (or ``run`` for all four, which
-    also walks the room groups when the Gram matrices of all rooms do not fit the device at once; ``max_group`` asks for groups
-    of at most that many rooms).  ``get_gram`` / ``get_filters`` / ``get_criteria`` / ``status`` read what the stages left."""
-
-    _destroy = "oiva_bsseval_destroy"
-
-    def __init__(self, lengths, N, filter_length=512, diag_only=False, max_group=0, device=None, stream=None):
+    def __init__(self, lengths, N, filter_length, diag_only, extra, device, stream):
         lens = [int(n) for n in lengths]
         if not lens or min(lens) < 1:
             raise ValueError("at least one room of at least one sample is needed")
@@ -125,31 +120,77 @@ class BssEval(_lib.Handle):
         self.device = get_device() if device is None else int(device)
         h = C.c_void_p()
         ns = (C.c_int * self.B)(*lens)
-        _lib.check(self.lib.oiva_bsseval_create(C.byref(h), self.device, self.B, ns, self.N, self.Lf, int(self.diag_only),
-                                                int(max_group), C.c_void_p(stream) if stream else None))
+        _lib.check(self._fn("create")(C.byref(h), self.device, self.B, ns, self.N, self.Lf, int(self.diag_only), int(extra),
+                                      C.c_void_p(stream) if stream else None))
         self.h = h
-        g = C.c_int()
-        _lib.check(self.lib.oiva_bsseval_groups(self.h, C.byref(g)))
-        self.group = g.value
 
-    def info(self):
-        """what ``last_batch_info()`` reports after a run on this handle"""
-        out = {"algorithm": "bss_eval", "precision": "float64", "batched": self.B, "sharded": False, "n_sources": self.N,
-               "filter_length": self.Lf, "rooms_per_group": self.group}
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def _info(self, algorithm, rooms_per_group):
+        out = {"algorithm": algorithm, "precision": "float64", "batched": self.B, "sharded": False, "n_sources": self.N,
+               "filter_length": self.Lf, "rooms_per_group": rooms_per_group}
         if len(set(self.lengths)) > 1:
             out.update(ragged=True, lengths=list(self.lengths))
         else:
             out["n_samples"] = self.lengths[0]
         return out
 
+    def _packed(self, name, sig):
+        if len(sig) != self.B or any(np.shape(a) != (self.N, n) for a, n in zip(sig, self.lengths)):
+            raise ValueError(f"{name} must be {self.B} arrays of shapes ({self.N}, n_b), n_b = {self.lengths}")
+        return np.concatenate([np.ascontiguousarray(a, dtype=np.float64).ravel() for a in sig])
+
+    def _gram(self, with_g, *set_index):
+        nt = self.N * self.Lf
+        G = np.empty((self.B, nt, nt)) if with_g else None
+        D, E = np.empty((self.B, self.N, nt)), np.empty((self.B, self.N))
+        _lib.check(self._fn("get_gram")(self.h, *set_index, None if G is None else _lib.ptr(G), _lib.ptr(D), _lib.ptr(E)))
+        return G, D, E
+
+    def _filters(self, *set_index):
+        Cb, cs = np.empty((self.B, self.N, self.N * self.Lf)), np.empty((self.B, self.N, self.N, self.Lf))
+        _lib.check(self._fn("get_filters")(self.h, *set_index, _lib.ptr(Cb), _lib.ptr(cs)))
+        return Cb, np.ascontiguousarray(cs.transpose(0, 2, 1, 3))            # (the device keeps c as [room, j, k])
+
+    def _criteria(self, shape, check, *sets):
+        out = [np.empty(shape) for _ in range(3)]
+        rc = self._fn("get_criteria")(self.h, *sets, *[_lib.ptr(a) for a in out])
+        if rc != _lib.ERR_NUMERIC or check:
+            _lib.check(rc)
+        return tuple(out)
+
+    def status(self):
+        """(B,) bool: True where the room's factorisation was flagged"""
+        st = (C.c_int * self.B)()
+        _lib.check(self._fn("status")(self.h, st))
+        return np.array(list(st), dtype=bool)
+
+
+class BssEval(_BssHandle):
+    """one handle = B rooms of ``lengths[b]`` samples x N sources and one ``filter_length`` on one GPU (``oiva_bsseval``).
+
+    Stages: ``set_signals``, then ``correlate``, ``factor``, ``solve``, ``criteria`` in order (or ``run`` for all four, which
+    also walks the room groups when the Gram matrices of all rooms do not fit the device at once; ``max_group`` asks for groups
+    of at most that many rooms).  ``get_gram`` / ``get_filters`` / ``get_criteria`` / ``status`` read what the stages left."""
+
+    _prefix = "oiva_bsseval_"
+    _destroy = "oiva_bsseval_destroy"
+
+    def __init__(self, lengths, N, filter_length=512, diag_only=False, max_group=0, device=None, stream=None):
+        super().__init__(lengths, N, filter_length, diag_only, max_group, device, stream)
+        g = C.c_int()
+        _lib.check(self.lib.oiva_bsseval_groups(self.h, C.byref(g)))
+        self.group = g.value
+
+    def info(self):
+        """what ``last_batch_info()`` reports after a run on this handle"""
+        return self._info("bss_eval", self.group)
+
     def set_signals(self, ref, est):
         """ref, est: B arrays (N, n_b) each"""
-        packed = []
-        for name, sig in (("ref", ref), ("est", est)):
-            if len(sig) != self.B or any(np.shape(a) != (self.N, n) for a, n in zip(sig, self.lengths)):
-                raise ValueError(f"{name} must be {self.B} arrays of shapes ({self.N}, n_b), n_b = {self.lengths}")
-            packed.append(np.concatenate([np.ascontiguousarray(a, dtype=np.float64).ravel() for a in sig]))
-        _lib.check(self.lib.oiva_bsseval_set_signals(self.h, _lib.ptr(packed[0]), _lib.ptr(packed[1])))
+        ref, est = self._packed("ref", ref), self._packed("est", est)
+        _lib.check(self.lib.oiva_bsseval_set_signals(self.h, _lib.ptr(ref), _lib.ptr(est)))
 
     def stage(self, name):
         _lib.check(self.lib.oiva_bsseval_stage(self.h, STAGES.index(name)))
@@ -175,33 +216,16 @@ class BssEval(_lib.Handle):
 
     def get_gram(self, with_g=True):
         """G (B, N Lf, N Lf) (None unless ``with_g``; needs ``factor``), D (B, N, N Lf), E (B, N)"""
-        nt = self.N * self.Lf
-        G = np.empty((self.B, nt, nt)) if with_g else None
-        D, E = np.empty((self.B, self.N, nt)), np.empty((self.B, self.N))
-        _lib.check(self.lib.oiva_bsseval_get_gram(self.h, None if G is None else _lib.ptr(G), _lib.ptr(D), _lib.ptr(E)))
-        return G, D, E
+        return self._gram(with_g)
 
     def get_filters(self):
         """the large solutions C (B, N[k], N Lf) and the small ones c (B, N[k], N[j], Lf): ``c[b, k, j] = G_jj^-1 D_k[j]``"""
-        nt = self.N * self.Lf
-        Cb, cs = np.empty((self.B, self.N, nt)), np.empty((self.B, self.N, self.N, self.Lf))
-        _lib.check(self.lib.oiva_bsseval_get_filters(self.h, _lib.ptr(Cb), _lib.ptr(cs)))
-        return Cb, np.ascontiguousarray(cs.transpose(0, 2, 1, 3))            # (the device keeps c as [room, j, k])
+        return self._filters()
 
     def get_criteria(self, check=True):
         """sdr, sir, sar (B, N, N) indexed [room, estimate, reference], NaN where a pair was not evaluated; with ``check`` a
         flagged room raises ``LinAlgError`` naming every such room"""
-        out = [np.empty((self.B, self.N, self.N)) for _ in range(3)]
-        rc = self.lib.oiva_bsseval_get_criteria(self.h, *[_lib.ptr(a) for a in out])
-        if rc != _lib.ERR_NUMERIC or check:
-            _lib.check(rc)
-        return tuple(out)
-
-    def status(self):
-        """(B,) bool: True where the room's factorisation was flagged"""
-        st = (C.c_int * self.B)()
-        _lib.check(self.lib.oiva_bsseval_status(self.h, st))
-        return np.array(list(st), dtype=bool)
+        return self._criteria((self.B, self.N, self.N), check)
 
     def time_stages(self, n):
         """n full runs with events around every stage: {stage: ms per run}"""
@@ -266,7 +290,7 @@ def bss_eval_sources(reference_sources, estimated_sources, compute_permutation=T
 SETS_PHASES = ("prepare", "correlate", "solve", "criteria")
 
 
-class BssEvalSets(_lib.Handle):
+class BssEvalSets(_BssHandle):
     """one handle = B rooms of ``lengths[b]`` samples x N sources, one ``filter_length`` and room for ``max_sets`` sets of
     estimates against one set of references on one GPU (``oiva_bsssets``).
 
@@ -275,44 +299,19 @@ class BssEvalSets(_lib.Handle):
     ``evaluate(e0, n_sets)`` runs the estimate half of those sets in one set of launches.  All rooms are resident at once: a
     handle that does not fit the device fails to be created (``HipError``), and the caller makes smaller ones."""
 
+    _prefix = "oiva_bsssets_"
     _destroy = "oiva_bsssets_destroy"
 
     def __init__(self, lengths, N, filter_length=512, diag_only=False, max_sets=1, device=None, stream=None):
-        lens = [int(n) for n in lengths]
-        if not lens or min(lens) < 1:
-            raise ValueError("at least one room of at least one sample is needed")
-        if not 1 <= N <= MAX_SOURCES:
-            raise ValueError(f"bss_eval runs on 1..{MAX_SOURCES} sources, got {N}")
-        if not 1 <= filter_length <= MAX_FILTER:
-            raise ValueError(f"filter_length must be in 1..{MAX_FILTER}, got {filter_length}")
         if int(max_sets) < 1:
             raise ValueError(f"max_sets must be >= 1, got {max_sets}")
-        self.lib = _lib.load()
-        self.lengths, self.B, self.N, self.Lf, self.diag_only = lens, len(lens), int(N), int(filter_length), bool(diag_only)
         self.max_sets = int(max_sets)
-        self.device = get_device() if device is None else int(device)
-        h = C.c_void_p()
-        ns = (C.c_int * self.B)(*lens)
-        _lib.check(self.lib.oiva_bsssets_create(C.byref(h), self.device, self.B, ns, self.N, self.Lf, int(self.diag_only),
-                                                self.max_sets, C.c_void_p(stream) if stream else None))
-        self.h = h
+        super().__init__(lengths, N, filter_length, diag_only, max_sets, device, stream)
 
     def info(self):
         """what ``last_batch_info()`` reports after a run on this handle"""
         prep, done = self.counts()
-        out = {"algorithm": "bss_eval_sets", "precision": "float64", "batched": self.B, "sharded": False, "n_sources": self.N,
-               "filter_length": self.Lf, "rooms_per_group": self.B, "n_sets": self.max_sets, "reference_preparations": prep,
-               "sets_evaluated": done}
-        if len(set(self.lengths)) > 1:
-            out.update(ragged=True, lengths=list(self.lengths))
-        else:
-            out["n_samples"] = self.lengths[0]
-        return out
-
-    def _packed(self, name, sig):
-        if len(sig) != self.B or any(np.shape(a) != (self.N, n) for a, n in zip(sig, self.lengths)):
-            raise ValueError(f"{name} must be {self.B} arrays of shapes ({self.N}, n_b), n_b = {self.lengths}")
-        return np.concatenate([np.ascontiguousarray(a, dtype=np.float64).ravel() for a in sig])
+        return dict(self._info("bss_eval_sets", self.B), n_sets=self.max_sets, reference_preparations=prep, sets_evaluated=done)
 
     def set_references(self, ref):
         """ref: B arrays (N, n_b); drops the preparation"""
@@ -340,32 +339,15 @@ class BssEvalSets(_lib.Handle):
         """sdr, sir, sar (B, n_sets, N, N) indexed [room, set, estimate, reference], NaN where a pair was not evaluated; with
         ``check`` a flagged room raises ``LinAlgError`` naming every such room"""
         n_sets = self.max_sets - int(e0) if n_sets is None else int(n_sets)
-        out = [np.empty((self.B, max(n_sets, 0), self.N, self.N)) for _ in range(3)]
-        rc = self.lib.oiva_bsssets_get_criteria(self.h, int(e0), n_sets, *[_lib.ptr(a) for a in out])
-        if rc != _lib.ERR_NUMERIC or check:
-            _lib.check(rc)
-        return tuple(out)
-
-    def status(self):
-        """(B,) bool: True where the room's factorisation was flagged"""
-        st = (C.c_int * self.B)()
-        _lib.check(self.lib.oiva_bsssets_status(self.h, st))
-        return np.array(list(st), dtype=bool)
+        return self._criteria((self.B, max(n_sets, 0), self.N, self.N), check, int(e0), n_sets)
 
     def get_gram(self, e, with_g=True):
         """G (B, N Lf, N Lf) (None unless ``with_g``), and D (B, N, N Lf), E (B, N) of the evaluated set e"""
-        nt = self.N * self.Lf
-        G = np.empty((self.B, nt, nt)) if with_g else None
-        D, E = np.empty((self.B, self.N, nt)), np.empty((self.B, self.N))
-        _lib.check(self.lib.oiva_bsssets_get_gram(self.h, int(e), None if G is None else _lib.ptr(G), _lib.ptr(D), _lib.ptr(E)))
-        return G, D, E
+        return self._gram(with_g, int(e))
 
     def get_filters(self, e):
         """of the evaluated set e, the large solutions C (B, N[k], N Lf) and the small ones c (B, N[k], N[j], Lf)"""
-        nt = self.N * self.Lf
-        Cb, cs = np.empty((self.B, self.N, nt)), np.empty((self.B, self.N, self.N, self.Lf))
-        _lib.check(self.lib.oiva_bsssets_get_filters(self.h, int(e), _lib.ptr(Cb), _lib.ptr(cs)))
-        return Cb, np.ascontiguousarray(cs.transpose(0, 2, 1, 3))            # (the device keeps c as [room, j, k])
+        return self._filters(int(e))
 
     def counts(self):
         """(preparations, sets evaluated) since the handle was made"""

@@ -128,7 +128,7 @@ def test_symbols_declared_bound_and_exported(lib):
         assert sym in _lib.SIGNATURES, sym
         assert getattr(lib, sym).restype is C.c_int
     assert {s for s in _lib.SIGNATURES if s.startswith("oiva_bsssets_")} == set(SYMBOLS)
-    assert "kernels_bsssets.hip" in build.SOURCES and "bsssets.hip" in build.SOURCES
+    assert "kernels_bsseval.hip" in build.SOURCES and "bsseval.hip" in build.SOURCES
     for name in ("BssEvalSets", "bss_eval_sets_batch", "bss_eval_sets"):
         assert name in overiva_amd.__all__ and getattr(overiva_amd, name) is getattr(metrics, name)
         assert name in overiva_amd.__doc__
@@ -142,11 +142,13 @@ def test_sets_kernels_use_no_scratch_memory():
     from overiva_amd import build
 
     build.build_library()
-    usage = build.kernel_usage(("kernels_bsssets",))
+    usage = build.kernel_usage(("kernels_bsseval",))
     names = " ".join(usage)
-    for kernel in ("bsssets_lag_kernel", "bsssets_lag_sum_kernel", "bsssets_assemble_kernel", "bsssets_init_rhs_kernel",
-                   "bsssets_trsv_kernel", "bsssets_quad_kernel", "bsssets_criteria_kernel"):
+    for kernel in ("bss_lag_kernel", "bss_lag_sum_kernel", "bss_assemble_kernel", "bss_init_rhs_kernel", "bss_trsv_kernel",
+                   "bss_quad_kernel", "bss_criteria_kernel", "bss_chol_diag_kernel", "bss_chol_panel_kernel", "bss_chol_update_kernel"):
         assert kernel in names, kernel
+    # the eight lag instantiations, forward and backward substitution, the large and the small quadratic forms
+    assert len(usage) == 8 + 1 + 1 + 1 + 2 + 2 + 1 + 3
     for name, u in usage.items():
         assert u["scratch"] == 0, (name, u)
 
