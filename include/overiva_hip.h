@@ -259,6 +259,13 @@ int oiva_plan_set_x_resident_mb(oiva_plan *p, double mb);
  * non-temporally (0: every load is plain); *reason: 0 off, 1 X fits the budget whole, 2 the passes run other kernels, 3 the
  * geometry does not keep every load step inside one frame group, 4 a share was chosen. */
 int oiva_plan_get_x_resident(oiva_plan *p, int *n16, int *nt, int *reason);
+/* Where that policy streams (reason 4), the covariance pass at 8 channels runs the row instantiation of its kernel: every load
+ * step requested row by row, resident groups plain and streamed groups non-temporal at the same addresses, through a shorter
+ * ring (csrc/kernels_cov.hip).  enable == 0 ($OIVA_COV_ROWS=0 at plan creation) forces the lane-addressed
+ * instantiation that every other plan runs: for A/B measurements and for the tests.  Same bits either way.  Drops captured
+ * graphs.  oiva_plan_get_cov_rows: *rows = 1 where the next covariance launch takes the row instantiation, else 0. */
+int oiva_plan_set_cov_rows(oiva_plan *p, int enable);
+int oiva_plan_get_cov_rows(oiva_plan *p, int *rows);
 /* Replay the iteration from a captured hipGraph instead of eager launches (default off). */
 int oiva_plan_use_graph(oiva_plan *p, int enable);
 /* Arithmetic: an OR of OIVA_PREC_* (default OIVA_PREC_FAST).  Call it before oiva_plan_covariance so that the
@@ -375,6 +382,12 @@ int oiva_test_x_policy(int T, int F, int M, int cov_tc, int pow_tcp, double budg
  * default) instead of budget_mb; *budget_used (may be NULL) receives the budget applied. */
 int oiva_test_x_choice(int T, int F, int M, int prec_flags, int cov_kind, int cov_tc, int pow_kind, int pow_tcp, double budget_mb, int from_env,
                        int *out, double *budget_used);
+/* host only: which instantiation of the 8-channel covariance kernel a plan with these kernels, this geometry, this budget and
+ * this setting of oiva_plan_set_cov_rows launches (arguments as oiva_test_x_choice): *rows = 1 the row form, 0 the lane form */
+int oiva_test_cov_rows(int T, int F, int M, int prec_flags, int cov_kind, int cov_tc, int pow_kind, int pow_tcp, double budget_mb, int rows_on,
+                       int *rows);
+/* Test hook: workgroups of cov_dma_kernel<M, kc> (rows != 0: of its row instantiation) that one CU of the current device holds */
+int oiva_test_cov_blocks_per_cu(int M, int kc, int rows, int *n);
 /* Test hook: the kernels and geometry a plan of this shape and these settings would run on `device` (csrc/kernel_choice.h), by
  * the functions a plan chooses with; nothing is allocated.  prec_flags: OIVA_PREC_*; quad_on / hmfma_on: the switches of
  * oiva_plan_set_cov_quad / _hmfma; *_splits_req: 0 or the splits asked for.  out (18): covariance kind, nsplit, tc, kc, nbg, pad,

@@ -83,6 +83,8 @@ SIGNATURES = {
     "oiva_plan_set_power_reverse": [_vp, _i],
     "oiva_plan_set_x_resident_mb": [_vp, C.c_double],
     "oiva_plan_get_x_resident": [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    "oiva_plan_set_cov_rows": [_vp, _i],
+    "oiva_plan_get_cov_rows": [_vp, C.POINTER(_i)],
     "oiva_plan_use_graph": [_vp, _i],
     "oiva_plan_set_precision": [_vp, _i],
     "oiva_plan_set_resident": [_vp, _i],
@@ -108,6 +110,8 @@ SIGNATURES = {
     "oiva_test_get_ppart": [_vp, _vp, C.POINTER(_i)],
     "oiva_test_power_order": [_i, _i, _i, _i, C.POINTER(_i)],
     "oiva_test_x_choice": [_i] * 8 + [C.c_double, _i, C.POINTER(_i), C.POINTER(C.c_double)],
+    "oiva_test_cov_rows": [_i] * 8 + [C.c_double, _i, C.POINTER(_i)],
+    "oiva_test_cov_blocks_per_cu": [_i, _i, _i, C.POINTER(_i)],
     "oiva_test_x_policy": [_i, _i, _i, _i, _i, C.c_double, C.POINTER(_i), _vp, _vp],
     "oiva_test_time_stage": [_vp, _i, _i, _fp],
     "oiva_test_live_buffers": [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],

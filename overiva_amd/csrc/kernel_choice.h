@@ -48,6 +48,7 @@ struct CovGeom {
     int pad = 0;  // odd channel count of 9..15: the kinds that read the padded X read the copy of X padded to M + 1 channels
     int part32 = 0; // Hmfma: the partial blocks leave as float32 (each the float64 sum of its chains, rounded once)
     int xplain = 16; // cov_dma_kernel: the frame groups g of a split with g % 16 < xplain are loaded plain, the others nt (XPolicy)
+    int rows = 0;    // cov_dma_kernel: its row instantiation (cov_rows_form below), filled in at launch time like xplain
 };
 // Which frame chunk the y-th dispatched row of power_kernel's grid takes when the pass runs against the covariance pass
 // (DESIGN §3).  The covariance pass walks `cs` splits of `ctc` frames ascending and side by side, so the X it read last -- what
@@ -131,6 +132,12 @@ inline XPolicy choose_x_policy(double budget_mb, int T, int F, int M, bool cov_f
     x.n16 = std::min(kXPeriod - 1, (int)(budget * kXPeriod / (frame_bytes * T)));
     return x;
 }
+
+// Which instantiation of cov_dma_kernel<8, KC> a launch takes: the row form (every step requested row by row, plain or nt, through
+// a ring of kCovRowStages stages: kernels_cov.hip) exactly where the policy streams, the lane-addressed form everywhere else --
+// X that fits the budget, the policy off, other kernels, other geometries -- and wherever the switch is off ($OIVA_COV_ROWS=0,
+// oiva_plan_set_cov_rows: for A/B and for the tests).  Same bits either way.
+constexpr bool cov_rows_form(const XPolicy& x, bool rows_on) { return rows_on && x.nt; }
 
 // ---- the traits ----------------------------------------------------------------------------------------------------------------
 enum class Partials { F64, Acc, F32IfPart32 };      // float64 always | the accumulator's type | float32 when CovGeom::part32

@@ -162,8 +162,17 @@ __global__ __launch_bounds__(kBlock) void cov_kernel(const float2* __restrict__ 
 // ordering is the wave's own vmcnt.  The LDS reads and both counted waits sit in one asm block (ring_read,
 // oiva_device.h): hipcc otherwise drains the whole DMA queue (vmcnt(0)) in front of any LDS read it can see.
 // The weights r[t,k] of the wave's four frame phases are wave-uniform and come through the scalar cache.
+// ROWS: the instantiation that runs where the load policy of X streams (8 channels; kernel_choice.h, launch_cov).  ONE addressing
+// form: every step is requested row by row (XRows), a resident group with plain requests, a streamed one with nt requests of the
+// same addresses, and read back with ring_read_rows, through a ring of S = kCovRowStages stages ("The streamed
+// covariance pass").  The lane-addressed instantiation (ROWS = false) serves every other plan: its plain steps are requested lane
+// by lane, and the two forms of a step sit side by side in its loop.
 // ---------------------------------------------------------------------------------------------
 constexpr int kDmaStages = 4;
+#ifndef OIVA_COV_ROW_STAGES
+#define OIVA_COV_ROW_STAGES 2      // (tools/build_variant.py ... -DOIVA_COV_ROW_STAGES=3: the other depths, for measuring)
+#endif
+constexpr int kCovRowStages = OIVA_COV_ROW_STAGES;
 
 // (tools/build_variant.py ... -DOIVA_COVDMA_TRACE: 100 MHz wall-clock stamps of every workgroup, read by tools/r6/covdma_trace.py)
 #ifdef OIVA_COVDMA_TRACE
@@ -178,7 +187,7 @@ __device__ long long g_cd_trace[8 * 2048];
     } while (0)
 #endif
 
-template <int M, int KC>
+template <int M, int KC, bool ROWS = false, int S = ROWS ? kCovRowStages : kDmaStages>
 __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __restrict__ X, const float* __restrict__ R,
                                                             float* __restrict__ wscale, int model, int raw,
                                                             double* __restrict__ Vpart, int T, int F, int K, int tc, int xplain) {
@@ -186,8 +195,9 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
     constexpr int PIECES = M / 2;                       // 16-byte pieces of one M-vector
     constexpr int STAGE = PIECES * 64;                  // float4 per stage per wave
     static_assert(M % 2 == 0 && (PIECES == 2 || PIECES == 4), "LDS-DMA path: M in {4, 8}");
-    __shared__ float4 ring[kWaves * kDmaStages * STAGE];
-    static_assert(sizeof(float4) * kWaves * kDmaStages * STAGE >= sizeof(float) * kChunk * kLdsStride,
+    static_assert(S >= 2 && S <= 4 && (!ROWS || M == 8), "S - 1 steps in flight; the row form exists where the policy streams");
+    __shared__ float4 ring[kWaves * S * STAGE];
+    static_assert(sizeof(float4) * kWaves * S * STAGE >= sizeof(float) * kChunk * kLdsStride,
                   "reduction scratch aliases the ring");
 
     const int tid = threadIdx.x;
@@ -216,10 +226,10 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
     }
 
     float ginv[KC];
-    float4* wring = ring + wave * kDmaStages * STAGE;                       // wave-uniform
-    const unsigned rd_base = (unsigned)(uintptr_t)(wring) + lane * 16;      // LDS byte address of this lane's slot
+    float4* wring = ring + wave * S * STAGE;                                // wave-uniform
+    const unsigned rd_base = (unsigned)(uintptr_t)(wring) + lane * 16;      // LDS byte address of this lane's slot (lane form)
     const size_t frame_stride = (size_t)F * M;
-    const float2* pbase = X + (size_t)fc * M;
+    const float2* pbase = X + (size_t)fc * M;                               // (lane form)
     // the load policy of X (kernel_choice.h; 8 channels: at 4 the registers of the second form would cost <4, 2> a wave per SIMD):
     // step i is frame group i of this split, plain or nt; wave-uniform
     using Rows = XRows<M>;
@@ -230,16 +240,24 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
     // issue the M/2 DMA requests of step i into stage s; steps past the end re-request the last frame
     // (legal address, never consumed) so that every step adds the same count to vmcnt
     auto issue = [&](int i, int s) {
-        if (!plain(i)) {
-            Rows::issue_nt(X, frame_stride, row_off, lane, t_begin + wave * kPhasesPerWave + 16 * i, i < nsteps ? t_end : 0, T, wring + s * STAGE);
-            return;
-        }
-        const int t = t_begin + q + 16 * i;
-        const int tcl = (i < nsteps && t < t_end) ? t : T - 1;
-        const float2* src = pbase + (size_t)tcl * frame_stride;
+        if constexpr (ROWS) {       // the same four addresses either way: the two branches differ in the cache-policy bits alone
+            const int t0 = t_begin + wave * kPhasesPerWave + 16 * i, t_lim = i < nsteps ? t_end : 0;
+            if (plain(i))
+                Rows::template issue<0>(X, frame_stride, row_off, lane, t0, t_lim, T, wring + s * STAGE);
+            else
+                Rows::template issue<2>(X, frame_stride, row_off, lane, t0, t_lim, T, wring + s * STAGE);
+        } else {
+            if (!plain(i)) {
+                Rows::issue_nt(X, frame_stride, row_off, lane, t_begin + wave * kPhasesPerWave + 16 * i, i < nsteps ? t_end : 0, T, wring + s * STAGE);
+                return;
+            }
+            const int t = t_begin + q + 16 * i;
+            const int tcl = (i < nsteps && t < t_end) ? t : T - 1;
+            const float2* src = pbase + (size_t)tcl * frame_stride;
 #pragma unroll
-        for (int j = 0; j < PIECES; ++j)
-            __builtin_amdgcn_global_load_lds((gvoid_t*)(src + 2 * j), (lvoid_t*)(wring + s * STAGE + j * 64), 16, 0, 0);
+            for (int j = 0; j < PIECES; ++j)
+                __builtin_amdgcn_global_load_lds((gvoid_t*)(src + 2 * j), (lvoid_t*)(wring + s * STAGE + j * 64), 16, 0, 0);
+        }
     };
     // lane masks selecting the lane's phase among the wave's four frames (arithmetic select: a ?: chain on
     // a lane-varying condition gets compiled into branches with the scalar loads inside them)
@@ -259,10 +277,14 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
             w[kk] = activation_weight(r, ginv[kk]) * live;
         }
         float4 v[PIECES];
-        if (plain(i))
-            ring_read<PIECES, (kDmaStages - 1) * PIECES>(rd_base + s * STAGE * 16, v);
-        else
-            ring_read_rows<PIECES, (kDmaStages - 1) * PIECES>(rd_rows + s * STAGE * 16, v);
+        if constexpr (ROWS) {
+            ring_read_rows<PIECES, (S - 1) * PIECES>(rd_rows + s * STAGE * 16, v);
+        } else {
+            if (plain(i))
+                ring_read<PIECES, (S - 1) * PIECES>(rd_base + s * STAGE * 16, v);
+            else
+                ring_read_rows<PIECES, (S - 1) * PIECES>(rd_rows + s * STAGE * 16, v);
+        }
 #if defined(OIVA_COVDMA_ABLATE) && (OIVA_COVDMA_ABLATE & 1)      // variant build (tools/build_variant.py): no arithmetic
         if constexpr (kPacked) {
             if (v[0].x == 12345.f) pacc.add(reinterpret_cast<const v2f(&)[M]>(v), v2f{w[0], w[1]});
@@ -291,10 +313,15 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
     };
 
     CD_STAMP(0);
-    issue(0, 0);
-    issue(1, 1);
-    issue(2, 2);
-    // scale normalisation of the activations (overiva.py:158-159) while the first three steps are on their way
+    if constexpr (!ROWS) {
+        issue(0, 0);
+        issue(1, 1);
+        issue(2, 2);
+    } else {
+#pragma unroll
+        for (int u = 0; u < S - 1; ++u) issue(u, u);
+    }
+    // scale normalisation of the activations (overiva.py:158-159) while the first S - 1 steps are on their way
 #pragma unroll
     for (int kk = 0; kk < KC; ++kk) {
         const int k = k0 + kk;
@@ -312,16 +339,36 @@ __global__ __launch_bounds__(kBlock, 2) void cov_dma_kernel(const float2* __rest
 
     CD_STAMP(1);
     int i = 0;
-    for (; i + 4 <= nsteps; i += 4) {       // stage indices are compile-time constants in the unrolled body
-        issue(i + 3, 3); consume(i, 0);
-        issue(i + 4, 0); consume(i + 1, 1);
-        issue(i + 5, 1); consume(i + 2, 2);
-        issue(i + 6, 2); consume(i + 3, 3);
+    if constexpr (!ROWS) {
+        // (written out: from the loop over the stages below hipcc makes other code for this form -- <8, 2> 256 registers and 56
+        //  bytes of scratch per lane instead of 250 and none)
+        static_assert(ROWS || S == 4, "the lane form's loop is unrolled over its four stages by hand");
+        for (; i + 4 <= nsteps; i += 4) {       // stage indices are compile-time constants in the unrolled body
+            issue(i + 3, 3); consume(i, 0);
+            issue(i + 4, 0); consume(i + 1, 1);
+            issue(i + 5, 1); consume(i + 2, 2);
+            issue(i + 6, 2); consume(i + 3, 3);
+        }
+        // 0..3 remaining steps; the stage sequence restarts at 0 because i is a multiple of 4
+        if (i < nsteps) { issue(i + 3, 3); consume(i, 0); }
+        if (i + 1 < nsteps) { issue(i + 4, 0); consume(i + 1, 1); }
+        if (i + 2 < nsteps) { issue(i + 5, 1); consume(i + 2, 2); }
+    } else {
+        for (; i + S <= nsteps; i += S) {
+#pragma unroll
+            for (int u = 0; u < S; ++u) {
+                issue(i + u + S - 1, (u + S - 1) % S);
+                consume(i + u, u);
+            }
+        }
+        // 0..S-2 remaining steps; the stage sequence restarts at 0 because i is a multiple of S
+#pragma unroll
+        for (int u = 0; u < S - 1; ++u)
+            if (i + u < nsteps) {
+                issue(i + u + S - 1, (u + S - 1) % S);
+                consume(i + u, u);
+            }
     }
-    // 0..3 remaining steps; the stage sequence restarts at 0 because i is a multiple of 4
-    if (i < nsteps) { issue(i + 3, 3); consume(i, 0); }
-    if (i + 1 < nsteps) { issue(i + 4, 0); consume(i + 1, 1); }
-    if (i + 2 < nsteps) { issue(i + 5, 1); consume(i + 2, 2); }
     CD_STAMP(2);
     // drain the DMA queue before the ring is reused as reduction scratch
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -346,9 +393,18 @@ using CovKernel = void (*)(const float2*, const float*, float*, int, int, double
 
 // (M, KC, unit weights) -> kernel instantiation, handed to fn together with its KC.  Register budget:
 // KC * M^2 accumulators of ACC must stay below ~144 registers.
+// rows: the row instantiation of cov_dma_kernel (CovGeom::rows: 8 channels in float32, the policy of X streams); anything else
+// that asks for it is an error, not a quiet lane form.
 template <int M, typename ACC, typename Fn>
-hipError_t dispatch_kc(int kc, bool unit, Fn&& fn) {
+hipError_t dispatch_kc(int kc, bool unit, bool rows, Fn&& fn) {
     constexpr int kRegs = M * M * (int)(sizeof(ACC) / 4);
+    if (rows) {
+        if constexpr (M == 8 && sizeof(ACC) == 4) {
+            if (!unit && kc == 1) return fn((CovKernel<ACC>)cov_dma_kernel<M, 1, true>, 1);
+            if (!unit && kc == 2) return fn((CovKernel<ACC>)cov_dma_kernel<M, 2, true>, 2);
+        }
+        return hipErrorInvalidValue;
+    }
     if (unit) return kc == 1 ? fn((CovKernel<ACC>)cov_kernel<M, 1, true, ACC>, 1) : hipErrorInvalidValue;
     if constexpr ((M == 4 || M == 8) && sizeof(ACC) == 4) {       // LDS-DMA ring where available
         switch (kc) {
@@ -385,16 +441,16 @@ hipError_t dispatch_kc(int kc, bool unit, Fn&& fn) {
 }
 
 template <typename ACC, typename Fn>
-hipError_t dispatch_cov(int M, int kc, bool unit, Fn&& fn) {
+hipError_t dispatch_cov(int M, int kc, bool unit, bool rows, Fn&& fn) {
     switch (M) {
-        case 1: return dispatch_kc<1, ACC>(kc, unit, fn);
-        case 2: return dispatch_kc<2, ACC>(kc, unit, fn);
-        case 3: return dispatch_kc<3, ACC>(kc, unit, fn);
-        case 4: return dispatch_kc<4, ACC>(kc, unit, fn);
-        case 5: return dispatch_kc<5, ACC>(kc, unit, fn);
-        case 6: return dispatch_kc<6, ACC>(kc, unit, fn);
-        case 7: return dispatch_kc<7, ACC>(kc, unit, fn);
-        case 8: return dispatch_kc<8, ACC>(kc, unit, fn);
+        case 1: return dispatch_kc<1, ACC>(kc, unit, rows, fn);
+        case 2: return dispatch_kc<2, ACC>(kc, unit, rows, fn);
+        case 3: return dispatch_kc<3, ACC>(kc, unit, rows, fn);
+        case 4: return dispatch_kc<4, ACC>(kc, unit, rows, fn);
+        case 5: return dispatch_kc<5, ACC>(kc, unit, rows, fn);
+        case 6: return dispatch_kc<6, ACC>(kc, unit, rows, fn);
+        case 7: return dispatch_kc<7, ACC>(kc, unit, rows, fn);
+        case 8: return dispatch_kc<8, ACC>(kc, unit, rows, fn);
     }
     return hipErrorInvalidValue;
 }
@@ -445,24 +501,25 @@ hipError_t launch_cov(hipStream_t s, const float2* X, const float2* Xpad, const 
     }
     const int kc = R == nullptr ? 1 : g.kc;
     if (f64)
-        return dispatch_cov<double>(M, kc, R == nullptr, [&](CovKernel<double> kern, int KC) {
+        return dispatch_cov<double>(M, kc, R == nullptr, g.rows != 0, [&](CovKernel<double> kern, int KC) {
             kern<<<dim3(g.nbg, g.nsplit, (K + KC - 1) / KC), dim3(kBlock), 0, s>>>(X, R, wscale, model, raw,
                                                                                  static_cast<double*>(Vpart), T, F, K, g.tc, g.xplain);
             return hipGetLastError();
         });
-    return dispatch_cov<float>(M, kc, R == nullptr, [&](CovKernel<float> kern, int KC) {
+    return dispatch_cov<float>(M, kc, R == nullptr, g.rows != 0, [&](CovKernel<float> kern, int KC) {
         return launch_dominant(kern, dim3(g.nbg, g.nsplit, (K + KC - 1) / KC), dim3(kBlock), 0, s, X, R, wscale, model, raw,
                                static_cast<double*>(Vpart), T, F, K, g.tc, g.xplain);
     });
 }
 
-// workgroups of this instantiation that one CU holds at once (registers / LDS limited)
-hipError_t cov_blocks_per_cu(int M, int kc, bool f64, int* n) {
+// workgroups of this instantiation that one CU holds at once (registers / LDS limited); rows: of its row instantiation (the
+// geometry is chosen on the lane form's answer: the two hold the same two workgroups, tests/test_cov_rows_host.py)
+hipError_t cov_blocks_per_cu(int M, int kc, bool f64, int* n, bool rows) {
     if (f64)
-        return dispatch_cov<double>(M, kc, false, [&](CovKernel<double> kern, int) {
+        return dispatch_cov<double>(M, kc, false, rows, [&](CovKernel<double> kern, int) {
             return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, kern, kBlock, 0);
         });
-    return dispatch_cov<float>(M, kc, false, [&](CovKernel<float> kern, int) {
+    return dispatch_cov<float>(M, kc, false, rows, [&](CovKernel<float> kern, int) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, kern, kBlock, 0);
     });
 }

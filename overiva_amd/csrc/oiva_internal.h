@@ -73,6 +73,7 @@ __host__ __device__ inline int power_chunk_tail_first(int y, int n, const PowOrd
 //   f64: accumulate in float64 (the reference's arithmetic: its float64 r_inv promotes overiva.py:179 to complex128)
 // Xpad: (T, F, M + 1) copy of X with one zero channel behind every bin's M (odd 9..15 channels; launch_pad_channels), read by
 // the vector-ALU kernels when g.pad is set; else nullptr
+// g.xplain, g.rows: the load policy of X and the instantiation of cov_dma_kernel<8, KC> that follows it (kernel_choice.h)
 hipError_t launch_cov(hipStream_t s, const float2* X, const float2* Xpad, const float* R, float* Wt, float* wscale, int model, int raw,
                       void* Vpart, bool f64, int T, int F, int M, int K, const CovGeom& g);
 hipError_t launch_pad_channels(hipStream_t s, const float2* X, float2* Xpad, long long n_tf, int M);
@@ -111,7 +112,7 @@ hipError_t launch_cov_hmfma(hipStream_t s, const float2* X, const float* Wt, dou
 hipError_t launch_cov_hmfma64(hipStream_t s, const float2* X, const double* Wt, double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g);
 hipError_t launch_cov_half16_f64(hipStream_t s, const float2* X, const float* R, float* Wt, float* wscale, int model, int raw,
                                  double* Vpart, int T, int F, int M, int Mv, int K, const CovGeom& g);
-hipError_t cov_blocks_per_cu(int M, int kc, bool f64, int* n);
+hipError_t cov_blocks_per_cu(int M, int kc, bool f64, int* n, bool rows = false);
 
 // Demix + source power, overiva.py:140 + the norms at :153/:155.
 //   What (F,M,M) c64 row-major;  Ppart [nb][T][K]

@@ -56,6 +56,7 @@ struct oiva_plan {
     int power_reverse = 1;        // oiva_plan_set_power_reverse ($OIVA_POWER_REVERSE=0: off): the power pass walks X against the covariance pass; 2: and takes its chunks tail first even in a grid of one round
     int pow_splits_req = 0;                       // oiva_plan_set_pow_splits (0: the rule's own count), kept for the choices that follow it
     double x_resident_mb = kXResidentDefaultMB;   // oiva_plan_set_x_resident_mb ($OIVA_X_RESIDENT_MB; <= 0: off): how much of X the two streaming passes keep in the Infinity Cache (XPolicy, kernel_choice.h)
+    bool cov_rows_on = true;                      // oiva_plan_set_cov_rows ($OIVA_COV_ROWS=0: off): where the policy of X streams, the covariance pass runs its row instantiation (cov_rows_form, kernel_choice.h)
     CovGeom stg{};              // geometry of the projection-back statistics pass (16-bin groups, independent of cov)
     PowGeom pw{};
     int n_cu = 256;
@@ -207,7 +208,9 @@ int ensure_vpart(oiva_plan* p) {
 XPolicy x_policy(const oiva_plan* p) { return choose_x_policy(p->x_resident_mb, p->T, p->F, p->M, p->cov_f64(), p->cov, p->pw); }
 CovGeom cov_geom_now(const oiva_plan* p) {
     CovGeom g = p->cov;
-    g.xplain = x_policy(p).xplain();
+    const XPolicy x = x_policy(p);
+    g.xplain = x.xplain();
+    g.rows = cov_rows_form(x, p->cov_rows_on) ? 1 : 0;
     return g;
 }
 
@@ -583,6 +586,8 @@ int oiva_plan_create(oiva_plan** out, int device, int T, int F, int M, int K, in
         p->power_reverse = (r && r[0] == '0') ? 0 : (r && r[0] == '2') ? 2 : 1;
         const char* x = std::getenv("OIVA_X_RESIDENT_MB");
         if (x && x[0]) p->x_resident_mb = std::atof(x);
+        const char* cr = std::getenv("OIVA_COV_ROWS");
+        p->cov_rows_on = !(cr && cr[0] == '0');
     }
     choose_cov_geom(p, 0);
     choose_pow_geom(p, 0);
@@ -1248,6 +1253,17 @@ int oiva_plan_get_x_resident(oiva_plan* p, int* n16, int* nt, int* reason) {
     return OIVA_OK;
 }
 
+int oiva_plan_set_cov_rows(oiva_plan* p, int enable) {
+    OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
+    return change_geometry(p, [&] { p->cov_rows_on = enable != 0; return OIVA_OK; });
+}
+
+int oiva_plan_get_cov_rows(oiva_plan* p, int* rows) {
+    OIVA_NEED(p && rows, OIVA_ERR_ARG, "null argument");
+    *rows = cov_geom_now(p).rows;
+    return OIVA_OK;
+}
+
 int oiva_plan_use_graph(oiva_plan* p, int enable) {
     OIVA_NEED(p, OIVA_ERR_ARG, "null plan");
     DeviceGuard guard(p->device);
@@ -1719,6 +1735,23 @@ int oiva_test_x_choice(int T, int F, int M, int prec_flags, int cov_kind, int co
     const XPolicy x = choose_x_policy(budget_mb, T, F, M, (prec_flags & OIVA_PREC_COV_F64) != 0, cg, pg);
     out[0] = x.n16, out[1] = x.nt ? 1 : 0, out[2] = (int)x.why;
     if (budget_used) *budget_used = budget_mb;
+    return OIVA_OK;
+}
+
+int oiva_test_cov_rows(int T, int F, int M, int prec_flags, int cov_kind, int cov_tc, int pow_kind, int pow_tcp, double budget_mb, int rows_on, int* rows) {
+    OIVA_NEED(rows && T >= 1 && F >= 1 && M >= 1 && cov_tc >= 1 && pow_tcp >= 1, OIVA_ERR_ARG, "bad arguments");
+    OIVA_NEED(cov_kind >= 0 && cov_kind < kCovKinds && pow_kind >= 0 && pow_kind < kPowKinds, OIVA_ERR_ARG, "unknown kernel kind");
+    CovGeom cg{};
+    cg.kind = (CovKind)cov_kind, cg.tc = cov_tc, cg.nsplit = ceil_div(T, cov_tc);
+    PowGeom pg{};
+    pg.kind = (PowKind)pow_kind, pg.tcp = pow_tcp, pg.nsplit = ceil_div(T, pow_tcp);
+    *rows = cov_rows_form(choose_x_policy(budget_mb, T, F, M, (prec_flags & OIVA_PREC_COV_F64) != 0, cg, pg), rows_on != 0) ? 1 : 0;
+    return OIVA_OK;
+}
+
+int oiva_test_cov_blocks_per_cu(int M, int kc, int rows, int* n) {
+    OIVA_NEED(n && M >= 1 && M <= 8 && kc >= 1, OIVA_ERR_ARG, "bad arguments");
+    OIVA_TRY_HIP(cov_blocks_per_cu(M, kc, false, n, rows != 0));
     return OIVA_OK;
 }
 

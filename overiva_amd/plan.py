@@ -246,6 +246,19 @@ class Plan(_lib.Handle):
         _lib.check(self.lib.oiva_plan_get_x_resident(self.h, C.byref(n16), C.byref(nt), C.byref(why)))
         return n16.value, bool(nt.value), self.X_RESIDENT_REASONS[why.value]
 
+    def set_cov_rows(self, enable=True):
+        """covariance pass at 8 channels where the load policy of X streams: the row instantiation of its kernel (default;
+        ``$OIVA_COV_ROWS=0`` at plan creation: off) or the lane-addressed one that every other plan runs; same bits, drops
+        captured graphs"""
+        _lib.check(self.lib.oiva_plan_set_cov_rows(self.h, 1 if enable else 0))
+
+    def cov_rows(self):
+        """whether the next covariance launch takes the row instantiation: exactly where ``x_resident()`` answers ``"share"``
+        and the switch is on"""
+        rows = C.c_int()
+        _lib.check(self.lib.oiva_plan_get_cov_rows(self.h, C.byref(rows)))
+        return bool(rows.value)
+
     def use_graph(self, enable=True):
         _lib.check(self.lib.oiva_plan_use_graph(self.h, 1 if enable else 0))
 

@@ -10,7 +10,7 @@
 // vector by four consecutive instructions ("addr": "lane").  "addr": "row" is the row-contiguous form of an nt step: lane l takes
 // bytes [16 l, 16 l + 16) of row j in instruction j, into LDS, and reads its own 64-B vector back from there (the covariance
 // kernel's ring takes it as it is; the power kernel gets a landing area of one step per step in flight).  Plain steps are
-// lane-strided in every row of the table.
+// lane-strided in every row of the table but the rings' ("plain_addr", "cov_plain_addr").
 // One policy per frame, the rule of csrc/kernel_choice.h: frames in groups of 16 counted from the start of their covariance
 // split, a group resident (plain load) or streamed (nt load, or plain as the control).  Layout `il`: group % 16 < n16 (resident
 // and streamed groups interleaved through every split); layout `first`: the first groups of every split.
@@ -29,6 +29,11 @@
 //            `pow ... addr row` rows of the same shares are repeated beside them as the yardstick of the same run.  Then the same
 //            in 8 chunks of 500 frames (one workgroup per CU), and X of one shard of two and of four (262 and 131 MB, all plain,
 //            384 workgroups): register loads against the ring.
+//   q = "f": the covariance stream through a ring of S = 2, 3, 4 stages ("cov_stages", counted wait (S - 1) * 4), its plain steps
+//            lane-addressed or row-contiguous ("cov_plain_addr"), shares 0 and 268 MB interleaved, alone and alternating with the
+//            power stream in the kernel's present form (ring of 2 stages, row-contiguous, 8 chunks of 500 frames).  The covariance
+//            kernel's present form (4 stages, lane-addressed plain steps) stands in front of and behind every block as the
+//            yardstick of the same run.  Then X of one shard of two and of four, all plain, at the shards' splits.
 //   q = "d": (the program's first question, docs/HISTORY_rounds_1-3.md §3.1) buffers of 128 .. 500 MiB streamed by 2048 concurrent
 //            workgroups, every pass in the same direction against passes of alternating direction
 // No step waits on anything but its own kernels; the whole sweep is about 170 rows of 7 launches of < 0.2 ms (1-2 s of GPU time
@@ -67,6 +72,8 @@ struct Policy {
     int contig;   // 1: nt steps row-contiguous through LDS
     int ring;     // pow: 0 the landing-area form, S = 2..4 a ring of S stages per wave
     int rowplain; // ring: 1 plain steps row-contiguous too, 0 lane-addressed
+    int cov_ring; // cov: stages of the ring per wave, 2..4 (0: the kernel's four)
+    int cov_rowplain; // cov: 1 plain steps row-contiguous too, 0 lane-addressed
 };
 struct Shape {
     int T, F;
@@ -87,16 +94,18 @@ __device__ __forceinline__ const char* piece(const char* X, const Shape& sh, boo
     return X + row + (rows ? lane * 16 : (lane & 15) * kM8 + j * 16);
 }
 
-// ---- the covariance pass's stream: LDS-DMA ring of four stages per wave ----
+// ---- the covariance pass's stream: LDS-DMA ring of S stages per wave (the kernel's: 4), S - 1 steps in flight, counted vmcnt ----
+// Policy::cov_rowplain: plain steps row-contiguous like the nt ones (one addressing form, one read form); 0: lane-addressed
+template <int S>
 __global__ __launch_bounds__(256, 2) void cov_stream(const char* __restrict__ X, float* out, Shape sh, Policy p) {
-    __shared__ float4 ring[4 * 4 * 256];
+    __shared__ float4 ring[4 * S * 256];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int f0 = blockIdx.x * 16;
     const int t_begin = blockIdx.y * sh.tc;
     const int t_end = min(sh.T, t_begin + sh.tc);
     const int nsteps = (t_end - t_begin + 15) >> 4;
-    float4* wring = ring + wave * 4 * 256;
+    float4* wring = ring + wave * S * 256;
     const unsigned rd_base = (unsigned)(uintptr_t)wring + lane * 16;
     auto plain = [&](int i) { return resident(p, min(t_begin + 16 * i + 4 * wave, sh.T - 1)) || !p.rest_nt; };
     const unsigned rd_rows = (unsigned)(uintptr_t)wring + ((lane >> 4) * 16 + (lane & 15)) * 64;
@@ -106,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void cov_stream(const char* __restrict__ X,
         if (plain(i)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                __builtin_amdgcn_global_load_lds((gvoid_t*)piece(X, sh, false, tl, t_end, f0, lane, j), (lvoid_t*)(wring + s * 256 + j * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gvoid_t*)piece(X, sh, p.cov_rowplain, tl, t_end, f0, lane, j), (lvoid_t*)(wring + s * 256 + j * 64), 16, 0, 0);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -116,46 +125,49 @@ __global__ __launch_bounds__(256, 2) void cov_stream(const char* __restrict__ X,
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     auto consume = [&](int i, int s) {
         float4 v0, v1, v2, v3;
-        if (!plain(i) && p.contig)
+        if (plain(i) ? p.cov_rowplain : p.contig)
             asm volatile(
-                "s_waitcnt vmcnt(12)\n\t"
+                "s_waitcnt vmcnt(%5)\n\t"
                 "ds_read_b128 %0, %4\n\t"
                 "ds_read_b128 %1, %4 offset:16\n\t"
                 "ds_read_b128 %2, %4 offset:32\n\t"
                 "ds_read_b128 %3, %4 offset:48\n\t"
                 "s_waitcnt lgkmcnt(0)"
                 : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
-                : "v"(rd_rows + s * 4096)
+                : "v"(rd_rows + s * 4096), "n"((S - 1) * 4)
                 : "memory");
         else
             asm volatile(
-                "s_waitcnt vmcnt(12)\n\t"
+                "s_waitcnt vmcnt(%5)\n\t"
                 "ds_read_b128 %0, %4\n\t"
                 "ds_read_b128 %1, %4 offset:1024\n\t"
                 "ds_read_b128 %2, %4 offset:2048\n\t"
                 "ds_read_b128 %3, %4 offset:3072\n\t"
                 "s_waitcnt lgkmcnt(0)"
                 : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
-                : "v"(rd_base + s * 4096)
+                : "v"(rd_base + s * 4096), "n"((S - 1) * 4)
                 : "memory");
         acc.x += v0.x + v1.x + v2.x + v3.x;
         acc.y += v0.y + v1.y + v2.y + v3.y;
         acc.z += v0.z + v1.z + v2.z + v3.z;
         acc.w += v0.w + v1.w + v2.w + v3.w;
     };
-    issue(0, 0);
-    issue(1, 1);
-    issue(2, 2);
+#pragma unroll
+    for (int u = 0; u < S - 1; ++u) issue(u, u);
     int i = 0;
-    for (; i + 4 <= nsteps; i += 4) {
-        issue(i + 3, 3); consume(i, 0);
-        issue(i + 4, 0); consume(i + 1, 1);
-        issue(i + 5, 1); consume(i + 2, 2);
-        issue(i + 6, 2); consume(i + 3, 3);
+    for (; i + S <= nsteps; i += S) {
+#pragma unroll
+        for (int u = 0; u < S; ++u) {      // stage indices are compile-time constants in the unrolled body
+            issue(i + u + S - 1, (u + S - 1) % S);
+            consume(i + u, u);
+        }
     }
-    if (i < nsteps) { issue(i + 3, 3); consume(i, 0); }
-    if (i + 1 < nsteps) { issue(i + 4, 0); consume(i + 1, 1); }
-    if (i + 2 < nsteps) { issue(i + 5, 1); consume(i + 2, 2); }
+#pragma unroll
+    for (int u = 0; u < S - 1; ++u)
+        if (i + u < nsteps) {
+            issue(i + u + S - 1, (u + S - 1) % S);
+            consume(i + u, u);
+        }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (acc.x + acc.y + acc.z + acc.w == 12345.678f) out[0] = acc.x;
 }
@@ -336,9 +348,12 @@ struct Bench {
     }
     void pass(const char* kern, int n, const Policy& p) {
         const bool c = !strcmp(kern, "cov") || (!strcmp(kern, "pair") && (n & 1));      // pair: power, covariance, power, ...
-        if (c)
-            cov_stream<<<dim3(cov.F / 16, (cov.T + cov.tc - 1) / cov.tc), 256>>>(X, out, cov, p);
-        else if (p.ring == 0)
+        if (c) {
+            const dim3 grid(cov.F / 16, (cov.T + cov.tc - 1) / cov.tc);
+            if (p.cov_ring == 2) cov_stream<2><<<grid, 256>>>(X, out, cov, p);
+            if (p.cov_ring == 3) cov_stream<3><<<grid, 256>>>(X, out, cov, p);
+            if (p.cov_ring == 0 || p.cov_ring == 4) cov_stream<4><<<grid, 256>>>(X, out, cov, p);
+        } else if (p.ring == 0)
             pow_stream<<<dim3(pow.F / 64, (pow.T + pow.tc - 1) / pow.tc), 256>>>(X, out, pow, p);
         else {
             const dim3 grid(pow.F / 64, (pow.T + pow.tc - 1) / pow.tc);
@@ -370,6 +385,9 @@ struct Bench {
                p.rest_nt ? "nt" : "plain", p.ring ? "ring" : (p.contig ? "row" : "lane"));
         if (p.ring) printf("\"stages\": %d, \"plain_addr\": \"%s\", ", p.ring, p.rowplain ? "row" : "lane");
         if (!strcmp(q, "e")) printf("\"x_mb\": %.0f, \"tcp\": %d, ", (double)bytes / 1e6, pow.tc);
+        if (!strcmp(q, "f"))
+            printf("\"x_mb\": %.0f, \"ctc\": %d, \"tcp\": %d, \"cov_stages\": %d, \"cov_plain_addr\": \"%s\", ", (double)bytes / 1e6, cov.tc, pow.tc,
+                   p.cov_ring ? p.cov_ring : 4, p.cov_rowplain ? "row" : "lane");
         printf("\"share_mb\": %.1f, \"pass_us\": [", share_mb(p));
         for (int n = 0; n < kPasses; ++n) printf("%s%.1f", n ? ", " : "", us[n]);
         printf("], \"steady_us\": %.1f, \"steady_tbps\": %.2f}\n", steady, (double)bytes / steady / 1e6);
@@ -438,6 +456,28 @@ int main() {
         for (int S = 2; S <= 4; ++S)
             for (int rowplain = 0; rowplain < 2; ++rowplain) b.row("e", "pow", Policy{ctc, 0, -1, 0, 0, S, rowplain});
         b.row("e", "pow", Policy{ctc, 0, -1, 0, 0});
+    }
+    b.cov = Shape{T, F, 1008};
+    b.bytes = b.flush_bytes;
+    // (f) the covariance stream: ring of S stages, plain steps lane-addressed or row-contiguous, alone and alternating with the power
+    // stream in its present form (ring of 2 stages, row-contiguous, 8 chunks of 500 frames); the kernel's form (4 stages, lane-
+    // addressed plain steps) in front of and behind every block as the yardstick of the same run
+    b.pow = Shape{T, F, 500};
+    for (int n16 : {0, 8})
+        for (int k : {0, 2}) {
+            b.row("f", kerns[k], Policy{ctc, n16, -1, 1, 1, 2, 1, 4, 0});
+            for (int S = 2; S <= 4; ++S)
+                for (int rowplain = 0; rowplain < (n16 ? 2 : 1); ++rowplain) b.row("f", kerns[k], Policy{ctc, n16, -1, 1, 1, 2, 1, S, rowplain});
+            b.row("f", kerns[k], Policy{ctc, n16, -1, 1, 1, 2, 1, 4, 0});
+        }
+    // ... and X of one shard of two and of four, all plain, at the shards' splits (8 of 512 frames, 14 of 288): lane against row
+    for (int shards : {2, 4}) {
+        b.cov = Shape{T, F / shards, shards == 2 ? 512 : 288};
+        b.bytes = (size_t)T * (F / shards) * kM8;
+        b.row("f", "cov", Policy{b.cov.tc, 0, -1, 0, 0, 0, 0, 4, 0});
+        for (int S = 2; S <= 4; ++S)
+            for (int rowplain = 0; rowplain < 2; ++rowplain) b.row("f", "cov", Policy{b.cov.tc, 0, -1, 0, 0, 0, 0, S, rowplain});
+        b.row("f", "cov", Policy{b.cov.tc, 0, -1, 0, 0, 0, 0, 4, 0});
     }
     b.pow = Shape{T, F, 336};
     b.cov = Shape{T, F, 1008};
