@@ -485,6 +485,26 @@ oiva_status oiva_batch_create_ragged(oiva_batch **out, int device, int B, const 
                                      void *stream);
 
 /*
+ * Complex128 data (opt-in): X is held as the caller's complex128 and every stage -- demix and powers, r, gamma
+ * and the weights, the scale of W, both covariances, the per-bin algebra, Y and the projection back -- runs in float64
+ * (kernels_batch_c128.hip; the per-bin update is the shared float64 one).  A batch of either create call.
+ *   oiva_batch_set_data_c128    : puts a fresh batch into the mode; OIVA_ERR_STATE once X is set.  Afterwards
+ *                                 oiva_batch_set_x_host takes complex128 only (f64 = 1, copied as it is: OIVA_ERR_ARG otherwise),
+ *                                 oiva_batch_set_x_dev borrows a packed complex128 device array, oiva_batch_demix with f64 = 1
+ *                                 returns what the device computed and with f64 = 0 its rounded copy; _covariance, _set_w,
+ *                                 _set_w_eig, _iterate (five launches per iteration whatever B), _get_w, _status, _get_cx and
+ *                                 _time_stages work unchanged.  OGIVE, ILRMA, the PCA entry points and oiva_batch_demix_dev return
+ *                                 OIVA_ERR_ARG ("complex128").
+ *   oiva_batch_c128_get_weights : test hook: the activation weights 1 / max(r / gamma, eps) of the last iteration, (sum T_b, K)
+ *   oiva_batch_c128_get_cov     : test hook: the weighted covariances of the last iteration, every problem's frame splits added
+ *                                 in order and divided by its T_b, (B*F, K, M, M) complex128
+ * A room's bits do not depend on B, on its place in the batch or on the other rooms' lengths.
+ */
+oiva_status oiva_batch_set_data_c128(oiva_batch *b);
+oiva_status oiva_batch_c128_get_weights(oiva_batch *b, double *w);
+oiva_status oiva_batch_c128_get_cov(oiva_batch *b, void *V);
+
+/*
  * Batched PCA + determined AuxIVA (auxiva_pca.py:63-92 on B problems; overiva_amd/pca_batch.py, auxiva_pca_batch): the outer
  * batch (M channels, K < M sources) finds every bin's principal subspace and projects X onto it on the device, an inner batch
  * of the same B, F and frames with M = K runs the determined iteration on the projected X, and the composed filters demix the

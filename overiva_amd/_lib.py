@@ -134,6 +134,9 @@ SIGNATURES = {
     "oiva_batch_ogive_begin": [_vp, _i, _i],
     "oiva_batch_ogive_iterate": [_vp, _i, _i, C.c_double, C.c_double, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double)],
     "oiva_batch_create_ragged": [C.POINTER(_vp), _i, _i, C.POINTER(_i), _i, _i, _i, _i, _vp],
+    "oiva_batch_set_data_c128": [_vp],
+    "oiva_batch_c128_get_weights": [_vp, _vp],
+    "oiva_batch_c128_get_cov": [_vp, _vp],
     "oiva_batch_set_w_pca": [_vp, _vp],
     "oiva_batch_project_dev": [_vp, C.POINTER(_vp)],
     "oiva_batch_compose_w": [_vp, _vp],

@@ -10,9 +10,15 @@ at once: the iteration is four launches whatever B, replayed from one captured g
 ``overiva(X[b], ...)`` with the same arguments in the ``precise`` arithmetic, and its bits do not depend on B or on its place in
 the batch.
 
+``data="complex128"`` (``overiva_batch``, ``overiva_batch_ragged``, ``BatchPlan``, ``RaggedBatchPlan``) is the opt-in complex128
+data path: X is held on the device as the caller's complex128 and every stage -- powers, activations, the scale of W, both
+covariances, the per-bin algebra, Y and the projection back -- runs in float64 (csrc/kernels_batch_c128.hip): the
+reference's complex128 arithmetic on the reference's complex128 data.  It has its own bits (not those of the default path on
+complex64-representable input) and the same independence of B and of the room's place.
+
 Arithmetic: always ``precise`` (float64 sums of exact float64 products in the covariance passes, float64 per-bin algebra, W_hat
 carried in complex128) -- what ``"auto"`` picks for these call sizes anyway; ``set_precision()`` does not change it.  X lives on
-the device as complex64; complex128 input is converted on the device.
+the device as complex64 and complex128 input is converted on the device, unless ``data="complex128"`` is given.
 """
 import ctypes as C
 import sys
@@ -25,12 +31,13 @@ from .overiva import _complex_dtype, get_device
 
 _overiva_module = sys.modules[__package__ + ".overiva"]   # (the package's attribute `overiva` is the function)
 MAX_CHANNELS = 8
+DATA_MODES = ("complex64", "complex128")
 ILRMA_STAGES = ("t_update", "v_update", "r_rewrite", "weighted_cov", "ip_update", "power", "normalise")   # OIVA_ILRMA_STAGE_*
 _info = {}
 
 
 def last_batch_info():
-    """what the last batched call ran: ``{"precision": "precise", "batched": B, ...}``; after ``auxiva_pca_batch()`` also
+    """what the last batched call ran: ``{"precision": "precise", "batched": B, "data": "complex64" | "complex128", ...}``; after ``auxiva_pca_batch()`` also
     ``algorithm`` ("auxiva_pca") and ``reduced`` (the channel count of the inner solve); after
     ``ogive_batch()`` also ``epochs`` (B ints: epochs each problem ran) and ``converged`` (B bools: its stopping rule fired); after
     ``ilrma_batch()`` also ``algorithm`` ("ilrma") and ``n_components``; after
@@ -75,18 +82,26 @@ class BatchPlan(_lib.Handle):
     ``ilrma_iterate`` run ILRMA (ilrma.py); ``ilrma_stage`` runs one stage of an epoch, ``get_nmf`` reads the source model.
 
     On the device X and Y are packed along the frames, (sum T_b, F, .): ``frames`` holds the B frame counts (here B times T)
-    and ``offsets`` every problem's first frame."""
+    and ``offsets`` every problem's first frame.
+
+    ``data="complex128"``: X is held as complex128 and every stage runs in float64.  ``set_x`` then takes complex128 only and
+    uploads it as it is, ``set_x_device`` borrows a complex128 device array, ``demix(dtype=np.complex128)`` returns what the
+    device computed and ``demix(dtype=np.complex64)`` its rounded copy.  OGIVE, ILRMA, the PCA entry points and ``demix_device``
+    raise ``ValueError`` on such a plan; ``get_weights`` / ``get_weighted_cov`` read the last iteration's stages back."""
 
     _destroy = "oiva_batch_destroy"
     dense = True          # X and Y are handed over as one (B, T, F, .) array
     n_components = 0      # columns of the ILRMA source model, set by ilrma_begin
+    data = "complex64"    # the data path: "complex128" holds X as complex128 and runs every stage in float64
 
-    def __init__(self, B, T, F, M, K, model="laplace", device=None, stream=None):
-        self._open([int(T)] * int(B), int(T), F, M, K, model, device, stream)
+    def __init__(self, B, T, F, M, K, model="laplace", device=None, stream=None, data="complex64"):
+        self._open([int(T)] * int(B), int(T), F, M, K, model, device, stream, data)
 
-    def _open(self, frames, T, F, M, K, model, device, stream):
+    def _open(self, frames, T, F, M, K, model, device, stream, data="complex64"):
         if model not in _lib.MODEL_IDS:
             raise ValueError(f"model must be 'laplace' or 'gauss', got {model!r}")
+        _check_data(data)
+        self.data = data
         self.lib = _lib.load()
         self.frames = frames
         self.offsets = np.concatenate([[0], np.cumsum(frames)]).astype(int)
@@ -97,6 +112,12 @@ class BatchPlan(_lib.Handle):
         _lib.check(self._create(h, C.c_void_p(stream) if stream else None))
         self.h = h
         self._keep = None
+        if data == "complex128":
+            _lib.check(self.lib.oiva_batch_set_data_c128(self.h))
+
+    def _no_c128(self, what):
+        if self.data == "complex128":
+            raise ValueError(f"{what} does not run on a complex128 plan (data='complex128'): use the default data='complex64'")
 
     def _create(self, h, stream):
         return self.lib.oiva_batch_create(C.byref(h), self.device, self.B, self.T, self.F, self.M, self.K,
@@ -108,13 +129,16 @@ class BatchPlan(_lib.Handle):
 
     def info(self):
         """what ``last_batch_info()`` reports after a run on this plan"""
-        return {"precision": "precise", "batched": self.B, "sharded": False, "shape": (self.T, self.F, self.M, self.K)}
+        return {"precision": "precise", "batched": self.B, "sharded": False, "shape": (self.T, self.F, self.M, self.K),
+                "data": self.data}
 
     def set_x(self, X):
-        """X: (B, T, F, M) complex64 or complex128 host array (complex128 is converted on the device)"""
+        """X: (B, T, F, M) complex64 or complex128 host array (complex128 is converted on the device); on a complex128 plan
+        complex128 only, uploaded as it is"""
         X = np.asarray(X)
         if X.shape != self.shape:
             raise ValueError(f"X has shape {X.shape}, batch expects {self.shape}")
+        _check_data(self.data, X.dtype)
         if X.dtype != np.complex128:
             X = np.ascontiguousarray(X, dtype=np.complex64)
         else:
@@ -122,7 +146,7 @@ class BatchPlan(_lib.Handle):
         _lib.check(self.lib.oiva_batch_set_x_host(self.h, _lib.ptr(X), 1 if X.dtype == np.complex128 else 0))
 
     def set_x_device(self, dev_ptr, keepalive=None):
-        """borrow a complex64 device array of ``shape`` (e.g. a torch tensor's data_ptr())"""
+        """borrow a complex64 device array of ``shape`` (e.g. a torch tensor's data_ptr()); on a complex128 plan a complex128 one"""
         self._keep = keepalive
         _lib.check(self.lib.oiva_batch_set_x_dev(self.h, C.c_void_p(int(dev_ptr))))
 
@@ -151,6 +175,7 @@ class BatchPlan(_lib.Handle):
     def set_w_pca(self, return_eigenvalues=False):
         """W = the K principal eigenvectors of every bin's input covariance, ascending (the reference's ``w[:, :, -K:]``,
         auxiva_pca.py:75-81), from the Jacobi eigensolver on the device; optionally returns all eigenvalues (B, F, M), ascending"""
+        self._no_c128("set_w_pca")
         ev = np.empty((self.B, self.F, self.M), np.float64) if return_eigenvalues else None
         _lib.check(self.lib.oiva_batch_set_w_pca(self.h, _lib.ptr(ev) if ev is not None else None))
         return ev
@@ -158,6 +183,7 @@ class BatchPlan(_lib.Handle):
     def project_device(self):
         """x -> W^H x for every problem in one launch (auxiva_pca.py:79-81 after ``set_w_pca``): a ``DeviceBatch`` of K channels in
         a device array of this plan that ``demix`` does not write, valid until the next ``project_device`` on the plan"""
+        self._no_c128("project_device")
         dev = C.c_void_p()
         _lib.check(self.lib.oiva_batch_project_dev(self.h, C.byref(dev)))
         return DeviceBatch(dev.value, self.frames, self.F, self.K, self.dense, owner=self)
@@ -167,6 +193,8 @@ class BatchPlan(_lib.Handle):
         ran on ``project_device()``'s output: y = W_red^H (P^H x) = (P W_red)^H x"""
         if not isinstance(inner, BatchPlan) or inner is self:
             raise ValueError("compose_w takes the plan of the reduced problems")
+        self._no_c128("compose_w")
+        inner._no_c128("compose_w")
         if (inner.B, inner.F) != (self.B, self.F):
             raise ValueError(f"the reduced plan holds {inner.B} problems of {inner.F} bins, this one {self.B} of {self.F}")
         if not inner.M == inner.K == self.K:
@@ -177,11 +205,13 @@ class BatchPlan(_lib.Handle):
         _lib.check(self.lib.oiva_batch_iterate(self.h, int(n)))
 
     def ogive_begin(self, update="demix", model="laplace"):
+        self._no_c128("OGIVE")
         _lib.check(self.lib.oiva_batch_ogive_begin(self.h, _ive.UPDATE_IDS[update], _lib.MODEL_IDS[model]))
 
     def ogive_iterate(self, first_epoch, n, step_size=0.1, tol=1e-3):
         """up to n epochs; returns, per problem, (epochs of this call that changed its state, stopping rule met, max ||delta|| of
         its last epoch) as (B,) arrays"""
+        self._no_c128("OGIVE")
         ran, conv, md = (C.c_int * self.B)(), (C.c_int * self.B)(), (C.c_double * self.B)()
         _lib.check(self.lib.oiva_batch_ogive_iterate(self.h, int(first_epoch), int(n), float(step_size), float(tol), ran, conv, md))
         return np.array(list(ran), dtype=int), np.array(list(conv), dtype=bool), np.array(list(md))
@@ -189,6 +219,7 @@ class BatchPlan(_lib.Handle):
     def ilrma_begin(self, T0, V0):
         """start ILRMA (needs K = M, X, the covariance and W set): T0 (B, K, F, L) and V0 (B, K, L, T) float64, strictly
         positive; forms R = T0 V0 and P = |y|^2 from the current W"""
+        self._no_c128("ILRMA")
         T0 = np.ascontiguousarray(T0, dtype=np.float64)
         V0 = np.ascontiguousarray(V0, dtype=np.float64)
         if T0.ndim != 4 or T0.shape[:3] != (self.B, self.K, self.F) or V0.shape != (self.B, self.K, T0.shape[3], self.T):
@@ -197,10 +228,12 @@ class BatchPlan(_lib.Handle):
         self.n_components = int(T0.shape[3])
 
     def ilrma_iterate(self, n=1):
+        self._no_c128("ILRMA")
         _lib.check(self.lib.oiva_batch_ilrma_iterate(self.h, int(n)))
 
     def ilrma_stage(self, stage):
         """one stage of an epoch: a name of ``ILRMA_STAGES`` or its index"""
+        self._no_c128("ILRMA")
         _lib.check(self.lib.oiva_batch_ilrma_stage(self.h, ILRMA_STAGES.index(stage) if isinstance(stage, str) else int(stage)))
 
     def get_nmf(self):
@@ -237,12 +270,15 @@ class BatchPlan(_lib.Handle):
         return out
 
     def demix(self, proj_back=True, dtype=np.complex64):
-        """Y (B, T, F, K) in complex64 or complex128"""
+        """Y (B, T, F, K) in complex64 or complex128; on a complex128 plan complex128 is what the device computed in float64
+        and complex64 its rounded copy"""
         return self._demix_packed(proj_back, dtype).reshape(self.B, self.T, self.F, self.K)
 
     def demix_device(self, proj_back=True):
         """Y stays on the device: a ``DeviceBatch`` (B, T, F, K), or packed (sum T_b, F, K) on a ragged plan; valid until the next
-        call on the plan (the contract of ``Plan.demix_device``)"""
+        call on the plan (the contract of ``Plan.demix_device``).  A ``DeviceBatch`` and its consumers are complex64: refused on
+        a complex128 plan"""
+        self._no_c128("demix_device")
         dev = C.c_void_p()
         _lib.check(self.lib.oiva_batch_demix_dev(self.h, 1 if proj_back else 0, C.byref(dev)))
         return DeviceBatch(dev.value, self.frames, self.F, self.K, self.dense, owner=self)
@@ -261,6 +297,20 @@ class BatchPlan(_lib.Handle):
         _lib.check(self.lib.oiva_batch_status(self.h, st))
         return np.array(list(st), dtype=bool)
 
+    def get_weights(self):
+        """test hook of a complex128 plan: the activation weights 1 / max(r / gamma, eps) of the last iteration, (B, T, K)
+        float64, or packed (sum T_b, K) on a ragged plan"""
+        out = np.empty((int(self.offsets[-1]), self.K), np.float64)
+        _lib.check(self.lib.oiva_batch_c128_get_weights(self.h, _lib.ptr(out)))
+        return out.reshape(self.B, self.T, self.K) if self.dense else out
+
+    def get_weighted_cov(self):
+        """test hook of a complex128 plan: the weighted covariances V of the last iteration, every room's frame splits added in
+        order and divided by its T: (B, F, K, M, M) complex128"""
+        out = np.empty((self.B, self.F, self.K, self.M, self.M), np.complex128)
+        _lib.check(self.lib.oiva_batch_c128_get_cov(self.h, _lib.ptr(out)))
+        return out
+
     def time_stages(self, n):
         """n eager iterations with events around every stage (ms per iteration per stage), and ms per iteration of a replayed
         graph of n (<= 32) iterations; both advance the state"""
@@ -268,6 +318,14 @@ class BatchPlan(_lib.Handle):
         arr = (C.c_float * _lib.N_STAGES)()
         _lib.check(self.lib.oiva_batch_time_stages(self.h, int(n), C.byref(total), arr))
         return total.value, dict(zip(_lib.STAGE_NAMES, list(arr)))
+
+
+def _check_data(data, dtype=None):
+    """``data`` names a data path; with ``dtype``: the complex128 path takes complex128 input only"""
+    if data not in DATA_MODES:
+        raise ValueError(f"data must be one of {DATA_MODES}, got {data!r}")
+    if data == "complex128" and dtype is not None and np.dtype(dtype) != np.complex128:
+        raise ValueError(f"data='complex128' needs complex128 input, got {np.dtype(dtype)}")
 
 
 def _check_common(name, found, B, F, M, n_src, model, W0, n_iter, update=None, bool_counts=True, w0_reduced=False):
@@ -386,7 +444,7 @@ def _run_overiva(plan, X, dtype, n_iter, proj_back, W0, init_eig, return_filters
 
 
 def overiva_batch(X, n_src=None, n_iter=20, proj_back=True, W0=None, model="laplace", init_eig=False, return_filters=False,
-                  callback=None):
+                  callback=None, data="complex64"):
     """
     ``overiva()`` (reference overiva.py:28-204) on B problems of one shape at once.
 
@@ -399,15 +457,19 @@ def overiva_batch(X, n_src=None, n_iter=20, proj_back=True, W0=None, model="lapl
     W0: ndarray broadcastable to (nfrequencies, nchannels, nsrc) (one start for all), or (batch, nfrequencies, nchannels, nsrc)
     callback: func
         Called with the current (batch, nframes, nfrequencies, nsrc) estimate at epochs 0, 10, 20, ...
+    data: "complex64" (default) or "complex128"
+        "complex128": X must be complex128; it is held as it is and every stage runs in float64 (the module docstring); Y, W
+        and the callback's estimates are complex128
 
     Returns
     -------
     Y (batch, nframes, nfrequencies, nsrc) in the dtype of X, or ``(Y, W)`` with W (batch, nfrequencies, nchannels, nsrc).
     A problem whose W ends non-finite raises ``numpy.linalg.LinAlgError`` naming every such problem.
     """
+    _check_data(data, np.asarray(X).dtype)
     X, dtype, K = _check_args(X, n_src, model, W0, n_iter)
     B, T, F, M = X.shape
-    with BatchPlan(B, T, F, M, K, model) as plan:
+    with BatchPlan(B, T, F, M, K, model, data=data) as plan:
         return _run_overiva(plan, X, dtype, n_iter, proj_back, W0, init_eig, return_filters, callback)
 
 
@@ -488,9 +550,9 @@ class RaggedBatchPlan(BatchPlan):
 
     dense = False
 
-    def __init__(self, frames, F, M, K, model="laplace", device=None, stream=None):
+    def __init__(self, frames, F, M, K, model="laplace", device=None, stream=None, data="complex64"):
         frames = [int(t) for t in frames]
-        self._open(frames, max(frames) if frames else 0, F, M, K, model, device, stream)
+        self._open(frames, max(frames) if frames else 0, F, M, K, model, device, stream, data)
 
     def _create(self, h, stream):
         return self.lib.oiva_batch_create_ragged(C.byref(h), self.device, self.B, (C.c_int * self.B)(*self.frames), self.F, self.M,
@@ -510,6 +572,8 @@ class RaggedBatchPlan(BatchPlan):
         if isinstance(X, (list, tuple)):
             if len(X) != self.B or any(np.shape(x) != (t, self.F, self.M) for x, t in zip(X, self.frames)):
                 raise ValueError(f"X must be {self.B} arrays of shapes (T_b, {self.F}, {self.M}), T_b = {self.frames}")
+            for x in X:
+                _check_data(self.data, np.asarray(x).dtype)
             dt = np.complex128 if any(np.asarray(x).dtype == np.complex128 for x in X) else np.complex64
             X = np.concatenate([np.asarray(x, dtype=dt) for x in X], axis=0)
         BatchPlan.set_x(self, X)
@@ -531,7 +595,7 @@ class RaggedBatchPlan(BatchPlan):
 
 
 def overiva_batch_ragged(Xs, n_src=None, n_iter=20, proj_back=True, W0=None, model="laplace", init_eig=False, return_filters=False,
-                         callback=None):
+                         callback=None, data="complex64"):
     """
     ``overiva()`` (reference overiva.py:28-204) on B problems of different frame counts at once.
 
@@ -544,6 +608,8 @@ def overiva_batch_ragged(Xs, n_src=None, n_iter=20, proj_back=True, W0=None, mod
     W0: ndarray broadcastable to (nfrequencies, nchannels, nsrc) (one start for all), or (batch, nfrequencies, nchannels, nsrc)
     callback: func
         Called with the list of current estimates Y_b (nframes_b, nfrequencies, nsrc) at epochs 0, 10, 20, ...
+    data: "complex64" (default) or "complex128"
+        as ``overiva_batch``: complex128 problems held as they are, every stage in float64
 
     Returns
     -------
@@ -552,7 +618,10 @@ def overiva_batch_ragged(Xs, n_src=None, n_iter=20, proj_back=True, W0=None, mod
     arguments, whatever the other problems.  A problem whose W ends non-finite raises ``numpy.linalg.LinAlgError`` naming
     every such problem.
     """
+    _check_data(data)
+    for x in Xs if hasattr(Xs, "__len__") else ():
+        _check_data(data, np.asarray(x).dtype)
     Xs, dtype, K = _check_ragged_args(Xs, n_src, model, W0, n_iter)
     F, M = Xs[0].shape[1:]
-    with RaggedBatchPlan([x.shape[0] for x in Xs], F, M, K, model) as plan:
+    with RaggedBatchPlan([x.shape[0] for x in Xs], F, M, K, model, data=data) as plan:
         return _run_overiva(plan, Xs, dtype, n_iter, proj_back, W0, init_eig, return_filters, callback)

@@ -10,6 +10,8 @@
 // oiva_batch_create with K = M: its NMF stages and its covariance pass are kernels_ilrma_batch.hip, its per-bin step the update.
 // The PCA front end of auxiva_pca_batch (oiva_batch_set_w_pca,
 // _project_dev, _compose_w; kernels_pca_batch.hip) reads the table on the device for every batch.
+// A batch of either entry put into the complex128 data path (oiva_batch_set_data_c128, before X is set) holds X as complex128 and
+// runs the stages of kernels_batch_c128.hip, which read the table, in float64; the per-bin update stays the shared one.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -69,6 +71,15 @@ struct oiva_batch {
     float* Spart = nullptr;        // [max stgs nsplit][F][K][3]: projection-back sums of one problem at a time
     float2* Y = nullptr;           // (sum T_b, F, K), allocated on first demix
     double2* Y128 = nullptr;
+    // the complex128 data path (oiva_batch_set_data_c128, kernels_batch_c128.hip): X as the caller's complex128 and every stage in
+    // float64; these replace X, Ppart, R, wscale and Spart, which are released; Y is Y128
+    bool c128 = false;
+    const double2* X128 = nullptr; // (sum T_b, F, M) packed
+    double2* X128_owned = nullptr;
+    double* Ppart64 = nullptr;     // problem b's [nb][T_b][K] at probs[b].p_off (doubles)
+    double* Rw64 = nullptr;        // (sum T_b, K): r, then the weights 1 / max(r / gamma, eps)
+    double* Gs64 = nullptr;        // [B][rblocks][K]: sums of r over blocks of kBlock frames
+    double2* Z128 = nullptr;       // (B*F, K): projection-back scales
     float2* Xr = nullptr;          // (sum T_b, F, K): X projected onto the principal subspace (oiva_batch_project_dev), allocated on first use
     // T is the largest T_b, and nsplit / pw_nsplit / tcp / rblocks the largest over the problems (the grids); every problem's own
     // geometry is in its record (host copy `probs`, device copy `probs_dev`) and stgs[p] is its projection-back statistics
@@ -120,7 +131,7 @@ UpdateArgs update_args(oiva_batch* b, bool init_only) {
     a.Cx = b->Cx;
     a.Vpart = b->Vpart;
     a.vpart_f64 = 1;
-    a.wscale = init_only ? nullptr : b->wscale;
+    a.wscale = init_only || b->c128 ? nullptr : b->wscale;     // (complex128 data: the scale is applied in float64 by the activation)
     a.nsplit = b->nsplit;
     a.T = b->T;
     a.F = (int)nbins(b);
@@ -130,7 +141,7 @@ UpdateArgs update_args(oiva_batch* b, bool init_only) {
     a.use_double = 1;
     a.layout = 0;
     a.wscale_bins = b->F;
-    a.ragged = b->ragged ? b->probs_dev : nullptr;
+    a.ragged = b->ragged || b->c128 ? b->probs_dev : nullptr;
     return a;
 }
 
@@ -145,10 +156,18 @@ DenseArgs dense_args(const oiva_batch* b) {
     return {d.T, d.tc, d.tcp, d.pw_nsplit, d.nsplit, r_buffer_bytes(d.T, b->K) / sizeof(float)};
 }
 
-// the four launches of one iteration (overiva.py:138-190)
+// the four launches of one iteration (overiva.py:138-190); five with complex128 data, whose activation is two
 int stage(oiva_batch* b, int s) {
     if (s == 3) {
         OIVA_TRY_HIP(launch_update(b->stream, update_args(b, false)));
+    } else if (b->c128) {
+        if (s == 0)
+            OIVA_TRY_HIP(launch_c128_power(b->stream, b->X128, b->What64, b->Ppart64, b->probs_dev, b->B, b->T, b->F, b->M, b->K));
+        else if (s == 1)
+            OIVA_TRY_HIP(launch_c128_activation(b->stream, b->Ppart64, b->Rw64, b->Gs64, b->What64, b->What, b->probs_dev, b->B, b->T, b->F,
+                                           b->M, b->K, b->model, b->rblocks));
+        else
+            OIVA_TRY_HIP(launch_c128_cov(b->stream, b->X128, b->Rw64, b->probs_dev, b->Vpart, b->B, b->F, b->M, b->K, b->nsplit));
     } else if (b->ragged) {
         if (s == 0)
             OIVA_TRY_HIP(launch_ragged_power(b->stream, b->X, b->What, b->Ppart, b->probs_dev, b->B, b->F, b->M, b->K, b->kp, b->pw_nsplit,
@@ -179,7 +198,7 @@ int one_iteration(oiva_batch* b) {
     return OIVA_OK;
 }
 
-// the executable graph of `iters` iterations on the batch's stream: one linear chain of 4 * iters kernel nodes
+// the executable graph of `iters` iterations on the batch's stream: one linear chain of 4 (complex128 data: 5) * iters kernel nodes
 int graph_for(oiva_batch* b, int iters, hipGraphExec_t* out) {
     return b->graphs.get(b->stream, iters, [&] {
         int r = OIVA_OK;
@@ -211,6 +230,12 @@ int download_w(oiva_batch* b, void* W_host, int f64, std::vector<int>& bad) {
 int demix_on_device(oiva_batch* b, int proj_back) {
     const int F = b->F, M = b->M, K = b->K;
     const size_t ny = b->frames_total * F * K;
+    if (b->c128) {
+        if (!b->Y128) OIVA_TRY_HIP(b->mem.take_one(&b->Y128, ny * sizeof(double2)));
+        if (proj_back && !b->Z128) OIVA_TRY_HIP(b->mem.take_one(&b->Z128, nbins(b) * K * sizeof(double2)));
+        OIVA_TRY_HIP(launch_c128_demix(b->stream, b->X128, b->What64, b->Z128, b->Y128, b->probs_dev, b->B, b->T, F, M, K, proj_back != 0));
+        return OIVA_OK;
+    }
     if (!b->Y) OIVA_TRY_HIP(b->mem.take_one(&b->Y, ny * sizeof(float2)));
     // overiva.py:192-199 per problem, with the single-problem kernels (projection back against that problem's X[b][:, :, 0]):
     // every problem at its packed frame offset with the statistics geometry of its own T_b
@@ -227,13 +252,16 @@ int demix_on_device(oiva_batch* b, int proj_back) {
 }
 
 // X of the batch is now the array at X (its own copy or the caller's): captured graphs hold the pointer, Cx is of the old one
-int install_x(oiva_batch* b, const float2* X) {
-    if (b->X != X) {
+int install_x(oiva_batch* b, const void* X) {
+    if ((b->c128 ? (const void*)b->X128 : (const void*)b->X) != X) {
         OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
         const int rc = drop_graphs(b);
         if (rc) return rc;
     }
-    b->X = X;
+    if (b->c128)
+        b->X128 = static_cast<const double2*>(X);
+    else
+        b->X = static_cast<const float2*>(X);
     b->have_x = true;
     b->have_cx = false;
     return OIVA_OK;
@@ -329,6 +357,7 @@ int ilrma_stage(oiva_batch* b, int s) {
 int check_ilrma(oiva_batch* b, bool begun) {
     OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
     OIVA_NEED(!b->ragged, OIVA_ERR_ARG, "ILRMA is not supported on a ragged batch");
+    OIVA_NEED(!b->c128, OIVA_ERR_ARG, "ILRMA is not supported on a complex128 batch");
     const int rc = check_ready(b);
     if (rc) return rc;
     OIVA_NEED(b->K == b->M, OIVA_ERR_ARG, "ILRMA is determined: create the batch with K = M");
@@ -403,6 +432,14 @@ int oiva_batch_set_x_host(oiva_batch* b, const void* X, int f64) {
     OIVA_NEED(b && X, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(b->device);
     const size_t n = b->frames_total * b->F * b->M;
+    if (b->c128) {
+        // the caller's bits: no conversion pass
+        OIVA_NEED(f64, OIVA_ERR_ARG, "a complex128 batch takes complex128 X");
+        if (!b->X128_owned) OIVA_TRY_HIP(b->mem.take_one(&b->X128_owned, n * sizeof(double2)));
+        OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+        OIVA_TRY_HIP(hipMemcpy(b->X128_owned, X, n * sizeof(double2), hipMemcpyHostToDevice));
+        return install_x(b, b->X128_owned);
+    }
     if (!b->X_owned) OIVA_TRY_HIP(b->mem.take_one(&b->X_owned, n * sizeof(float2)));
     OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
     if (f64) {
@@ -418,7 +455,7 @@ int oiva_batch_set_x_host(oiva_batch* b, const void* X, int f64) {
 int oiva_batch_set_x_dev(oiva_batch* b, const void* X_dev) {
     OIVA_NEED(b && X_dev, OIVA_ERR_ARG, "null argument");
     DeviceGuard guard(b->device);
-    return install_x(b, static_cast<const float2*>(X_dev));
+    return install_x(b, X_dev);
 }
 
 int oiva_batch_covariance(oiva_batch* b) {
@@ -427,7 +464,10 @@ int oiva_batch_covariance(oiva_batch* b) {
     DeviceGuard guard(b->device);
     // unit weights, one "source": partials [nsplit][B*F][1][M*M]; problem b's own nsplit_b partials added in split order and
     // divided by T_b (overiva.py:87)
-    if (b->ragged) {
+    if (b->c128) {
+        OIVA_TRY_HIP(launch_c128_cov(b->stream, b->X128, nullptr, b->probs_dev, b->Vpart, b->B, b->F, b->M, 1, b->nsplit));
+        OIVA_TRY_HIP(launch_ragged_sum_parts(b->stream, b->Vpart, b->probs_dev, b->Cx, b->B, b->F, b->M));
+    } else if (b->ragged) {
         OIVA_TRY_HIP(launch_ragged_cov(b->stream, b->X, nullptr, b->probs_dev, nullptr, b->model, b->Vpart, b->B, b->F, b->M, 1, b->nsplit));
         OIVA_TRY_HIP(launch_ragged_sum_parts(b->stream, b->Vpart, b->probs_dev, b->Cx, b->B, b->F, b->M));
     } else {
@@ -490,7 +530,16 @@ int oiva_batch_demix(oiva_batch* b, void* Y_host, int f64, int proj_back) {
     rc = demix_on_device(b, proj_back);
     if (rc) return rc;
     const size_t ny = b->frames_total * b->F * b->K;
-    if (f64) {
+    if (b->c128 && !f64) {
+        // the rounded copy of what the device computed in float64
+        std::vector<double2> y(ny);
+        OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+        OIVA_TRY_HIP(hipMemcpy(y.data(), b->Y128, ny * sizeof(double2), hipMemcpyDeviceToHost));
+        float2* out = static_cast<float2*>(Y_host);
+        for (size_t i = 0; i < ny; ++i) out[i] = make_float2((float)y[i].x, (float)y[i].y);
+        return OIVA_OK;
+    }
+    if (f64 && !b->c128) {
         if (!b->Y128) OIVA_TRY_HIP(b->mem.take_one(&b->Y128, ny * sizeof(double2)));
         OIVA_TRY_HIP(launch_cast_c64_to_c128(b->stream, b->Y, b->Y128, (long long)ny));
     }
@@ -505,6 +554,7 @@ oiva_status oiva_batch_demix_dev(oiva_batch* b, int proj_back, void** Y_dev) {
     *Y_dev = nullptr;
     int rc = check_ready(b);
     if (rc) return rc;
+    OIVA_NEED(!b->c128, OIVA_ERR_ARG, "oiva_batch_demix_dev hands out complex64: not on a complex128 batch");
     DeviceGuard guard(b->device);
     rc = demix_on_device(b, proj_back);
     if (rc) return rc;
@@ -575,6 +625,79 @@ int oiva_batch_time_stages(oiva_batch* b, int n, float* total_ms, float* per_sta
     return OIVA_OK;
 }
 
+// ---- complex128 data (kernels_batch_c128.hip) -------------------------------------------------------------------
+oiva_status oiva_batch_set_data_c128(oiva_batch* b) {
+    OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    if (b->c128) return OIVA_OK;
+    OIVA_NEED(!b->have_x, OIVA_ERR_STATE, "the complex128 data path is chosen before X is set");
+    DeviceGuard guard(b->device);
+    DeviceArena& mem = b->mem;
+    const size_t before = mem.mark();
+    size_t p_doubles = 0;
+    for (const RaggedProblem& d : b->probs) p_doubles = std::max(p_doubles, d.p_off + (size_t)b->nb * d.T * b->K);
+    mem.take(&b->Ppart64, p_doubles * sizeof(double));
+    mem.take(&b->Rw64, b->frames_total * b->K * sizeof(double));
+    mem.take(&b->Gs64, (size_t)b->B * b->rblocks * b->K * sizeof(double));
+    if (!mem.ok()) {
+        mem.release_to(before);
+        return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(mem.status()));
+    }
+    // the float32 stages' buffers are not used on this path
+    mem.release(&b->Ppart);
+    mem.release(&b->R);
+    mem.release(&b->wscale);
+    mem.release(&b->Spart);
+    b->c128 = true;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_c128_get_weights(oiva_batch* b, double* w) {
+    OIVA_NEED(b && w, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(b->c128, OIVA_ERR_ARG, "not a complex128 batch");
+    const int rc = check_ready(b);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(w, b->Rw64, b->frames_total * b->K * sizeof(double), hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_c128_get_cov(oiva_batch* b, void* V) {
+    OIVA_NEED(b && V, OIVA_ERR_ARG, "null argument");
+    OIVA_NEED(b->c128, OIVA_ERR_ARG, "not a complex128 batch");
+    const int rc = check_ready(b);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    const int M = b->M, K = b->K, MM = M * M;
+    const size_t per_split = nbins(b) * K * MM;
+    std::vector<double> part((size_t)b->nsplit * per_split);
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(part.data(), b->Vpart, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    // every problem's own splits added in order and divided by its T, unpacked from the Hermitian half
+    double2* out = static_cast<double2*>(V);
+    std::vector<double> acc(MM);
+    for (int p = 0; p < b->B; ++p) {
+        const RaggedProblem& d = b->probs[p];
+        for (size_t fk = (size_t)p * b->F * K; fk < (size_t)(p + 1) * b->F * K; ++fk) {
+            for (int e = 0; e < MM; ++e) {
+                double s = 0.;
+                for (int i = 0; i < d.nsplit; ++i) s += part[(size_t)i * per_split + fk * MM + e];
+                acc[e] = s / (double)d.T;
+            }
+            double2* o = out + fk * MM;
+            for (int c = 0; c < M; ++c) {
+                o[c * M + c] = make_double2(acc[c], 0.);
+                for (int dd = c + 1; dd < M; ++dd) {
+                    const int a = herm_pair_index(M, c, dd);
+                    o[c * M + dd] = make_double2(acc[a], acc[a + 1]);
+                    o[dd * M + c] = make_double2(acc[a], -acc[a + 1]);
+                }
+            }
+        }
+    }
+    return OIVA_OK;
+}
+
 // ---- batched OGIVE (reference ive.py:33-256, one problem per batch entry) -------------------------------------------------
 oiva_status oiva_batch_get_cx(oiva_batch* b, void* Cx_host, int f64) {
     OIVA_NEED(b && Cx_host, OIVA_ERR_ARG, "null argument");
@@ -594,6 +717,7 @@ oiva_status oiva_batch_get_cx(oiva_batch* b, void* Cx_host, int f64) {
 oiva_status oiva_batch_ogive_begin(oiva_batch* b, int update_mode, int model) {
     OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
     OIVA_NEED(!b->ragged, OIVA_ERR_ARG, "OGIVE is not supported on a ragged batch");
+    OIVA_NEED(!b->c128, OIVA_ERR_ARG, "OGIVE is not supported on a complex128 batch");
     int rc = check_ready(b);
     if (rc) return rc;
     OIVA_NEED(b->K == 1, OIVA_ERR_ARG, "OGIVE extracts one source: create the batch with K = 1");
@@ -641,6 +765,7 @@ oiva_status oiva_batch_ogive_iterate(oiva_batch* b, int first_epoch, int n, doub
                                  double* max_delta) {
     OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
     OIVA_NEED(!b->ragged, OIVA_ERR_ARG, "OGIVE is not supported on a ragged batch");
+    OIVA_NEED(!b->c128, OIVA_ERR_ARG, "OGIVE is not supported on a complex128 batch");
     int rc = check_ready(b);
     if (rc) return rc;
     OIVA_NEED(b->og_ready, OIVA_ERR_STATE, "call oiva_batch_ogive_begin first");
@@ -820,6 +945,7 @@ oiva_status oiva_batch_ilrma_time_stages(oiva_batch* b, int n, float* per_stage_
 // ---- batched PCA front end (reference auxiva_pca.py:63-92, one problem per batch entry) -------------------------------------
 oiva_status oiva_batch_set_w_pca(oiva_batch* b, double* evals_host) {
     OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(!b->c128, OIVA_ERR_ARG, "the PCA front end is not supported on a complex128 batch");
     OIVA_NEED(b->have_cx, OIVA_ERR_STATE, "input covariance not computed (oiva_batch_covariance)");
     DeviceGuard guard(b->device);
     // auxiva_pca.py:75-81 per bin, the device eigensolver on B*F bins; the eigenvalues pass through Vpart (free between the
@@ -840,6 +966,7 @@ oiva_status oiva_batch_project_dev(oiva_batch* b, void** Xr_dev) {
     *Xr_dev = nullptr;
     const int rc = check_ready(b);
     if (rc) return rc;
+    OIVA_NEED(!b->c128, OIVA_ERR_ARG, "the PCA front end is not supported on a complex128 batch");
     DeviceGuard guard(b->device);
     if (!b->Xr) OIVA_TRY_HIP(b->mem.take_one(&b->Xr, b->frames_total * b->F * b->K * sizeof(float2)));
     // auxiva_pca.py:79-81 for every problem in one launch, from the problem table
@@ -852,6 +979,7 @@ oiva_status oiva_batch_project_dev(oiva_batch* b, void** Xr_dev) {
 oiva_status oiva_batch_compose_w(oiva_batch* outer, const oiva_batch* inner) {
     OIVA_NEED(outer != nullptr && inner != nullptr, OIVA_ERR_ARG, "null batch");
     OIVA_NEED(outer != inner, OIVA_ERR_ARG, "the reduced batch must be another batch");
+    OIVA_NEED(!outer->c128 && !inner->c128, OIVA_ERR_ARG, "the PCA front end is not supported on a complex128 batch");
     OIVA_NEED(inner->B == outer->B && inner->F == outer->F, OIVA_ERR_ARG, "the two batches differ in B or F");
     OIVA_NEED(inner->M == inner->K && inner->K == outer->K, OIVA_ERR_ARG,
               "the reduced batch must be determined on the K channels of the projection");

@@ -326,6 +326,21 @@ hipError_t launch_ragged_cov(hipStream_t s, const float2* X, const float* R, con
 // Cx [B*F][M*M] = (1 / T_b) * the sum of problem b's own nsplit_b unit-weight partials (as launch_sum_parts for one problem)
 hipError_t launch_ragged_sum_parts(hipStream_t s, const double* parts, const RaggedProblem* prob, double* Cx, int B, int F, int M);
 
+// The complex128 data path of either batch (kernels_batch_c128.hip, batch.hip: oiva_batch_set_data_c128), float64 throughout, from
+// the problem table.  X packed (sum T, F, M) complex128; Ppart: problem b's [c128_parts(F)][T_b][K] at p_off_b; Rw (sum T, K): r,
+// then the weights; Gs [B][rblocks][K]: the block sums of r; Vpart as above (Wt == nullptr: unit weights, K = 1).
+int c128_parts(int F);
+hipError_t launch_c128_power(hipStream_t s, const double2* X, const double2* What64, double* Ppart, const RaggedProblem* prob, int B,
+                             int max_T, int F, int M, int K);
+// two launches: r and its block sums; then gamma, the weights in place, and W's columns divided by gamma | sqrt(gamma)
+hipError_t launch_c128_activation(hipStream_t s, const double* Ppart, double* Rw, double* Gs, double2* What64, float2* What,
+                                  const RaggedProblem* prob, int B, int max_T, int F, int M, int K, int model, int rblocks);
+hipError_t launch_c128_cov(hipStream_t s, const double2* X, const double* Wt, const RaggedProblem* prob, double* Vpart, int B, int F,
+                           int M, int K, int max_nsplit);
+// Y (sum T, F, K) complex128; with proj_back the scales Z (B*F, K) first
+hipError_t launch_c128_demix(hipStream_t s, const double2* X, const double2* What64, double2* Z, double2* Y, const RaggedProblem* prob,
+                             int B, int max_T, int F, int M, int K, bool proj_back);
+
 // The batched PCA front end (kernels_pca_batch.hip, batch.hip; auxiva_pca.py:79-81 and the composition of the filters behind it).
 //   project: Xr (sum T, F, K) packed = the K principal components of every problem's X, one launch from the problem table; What
 //   (B*F, M, M) holds P in columns 0..K-1.  The float32 chain of launch_demix_write without projection back, element by element.

@@ -14,7 +14,8 @@ arithmetic is (``resolve_precision``).  ``"fast"`` is float32 in the per-bin alg
 
 Documented deviations from the reference:
 * X is held as complex64 on the device even for complex128 input (a 6e-8 relative input perturbation); the
-  result is cast back to the input's complex dtype;
+  result is cast back to the input's complex dtype.  That holds for ``overiva()``; the batched solver has an opt-in complex128
+  data path, ``overiva_batch(X[None], ..., data="complex128")`` (batch.py), which keeps X as it is and runs every stage in float64;
 * at most 32 channels (``OIVA_MAX_CHANNELS``; the reference has no limit): more raise ``ValueError`` before any device
   call.  17..32 channels run one generic wide path (``csrc/kernels_wide.hip``) under the same arithmetic contract;
 * an unknown ``model`` raises ``ValueError`` (the reference silently returns NaN, ``overiva.py:152-167``);
