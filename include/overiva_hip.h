@@ -396,6 +396,12 @@ int oiva_test_cov_blocks_per_cu(int M, int kc, int rows, int *n);
  * Kinds count from 0 in the order of CovKind / PowKind. */
 int oiva_test_kernel_choice(int device, int T, int F, int F_total, int M, int K, int prec_flags, int quad_on, int hmfma_on,
                             int cov_splits_req, int pow_splits_req, int *out);
+/* Test hook: the per-bin update kernel that is LAUNCHED for these fields of the update's arguments (channels, sources, float64
+ * arithmetic, float64 partials, J initialisation only, row layout, covariance splits) and the process's switches ($OIVA_UPDATE_GRAM,
+ * $OIVA_UPDATE_DET, $OIVA_DET16_INVERSE, $OIVA_DET16_ROWS).  The launch of one bin with null pointers is captured on a stream of
+ * its own, so nothing runs and nothing is allocated; name (n bytes) receives the captured kernel node's function in the normal
+ * form of csrc/kernel_choice.h, e.g. "update_sq_kernel<8, double, 8, 2>". */
+int oiva_test_update_choice(int M, int K, int use_double, int vpart_f64, int init_only, int layout, int nsplit, char *name, int n);
 
 /*
  * OGIVE -- orthogonally constrained independent vector extraction of ONE source by gradient steps, the reference's

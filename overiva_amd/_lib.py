@@ -116,6 +116,7 @@ SIGNATURES = {
     "oiva_test_time_stage": [_vp, _i, _i, _fp],
     "oiva_test_live_buffers": [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
     "oiva_test_kernel_choice": [_i] * 11 + [C.POINTER(_i)],
+    "oiva_test_update_choice": [_i] * 7 + [C.c_char_p, _i],
     "oiva_plan_ogive_begin": [_vp, _i, _i],
     "oiva_plan_ogive_iterate": [_vp, _i, _i, C.c_double, C.c_double, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double)],
     "oiva_batch_create": [C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i, _vp],

@@ -87,6 +87,20 @@ oiva::KernelTimer& oiva::kernel_timer() {
     return t;
 }
 
+// the switches of the per-bin update's choice (choose_update, kernel_choice.h; INTEGRATION.md "switches"), read once per process
+const oiva::UpdSwitches& oiva::update_switches() {
+    static const UpdSwitches sw = [] {
+        UpdSwitches u;
+        auto is = [](const char* name, char c) { const char* v = std::getenv(name); return v && v[0] == c; };
+        if (const char* v = std::getenv("OIVA_UPDATE_GRAM")) u.gram = std::atoi(v);
+        u.det = !is("OIVA_UPDATE_DET", '0');
+        u.det16_inverse = is("OIVA_DET16_INVERSE", '1');
+        u.det16_rows = !is("OIVA_DET16_ROWS", '0');
+        return u;
+    }();
+    return sw;
+}
+
 hipError_t oiva::dev_malloc(void** out, size_t bytes) { return handed_out(malloc_retry(out, bytes), bytes); }
 hipError_t oiva::fine_malloc(void** out, size_t bytes) {
     return handed_out(hipExtMallocWithFlags(out, bytes, hipDeviceMallocFinegrained), bytes);

@@ -3,9 +3,13 @@
 // Everything else -- the launchers' switches, the partial type, the unit-weights pass, the switches of the C ABI -- reads the
 // table.  Host only, header only, standard C++: no HIP type and no device query in here (the two occupancy figures the choice
 // needs come in as callables), so a plain program can replay any choice (tests/helpers/kernel_choice_main.cpp).
+// Behind them, the same for the third stage: which per-bin update kernel launch_update runs (kUpdTraits, choose_update; replayed by
+// tests/helpers/update_choice_main.cpp), and the shape rule of the fused covariance + update launch.
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <functional>
+#include <string>
 
 #include "overiva_hip.h"
 
@@ -489,6 +493,158 @@ inline PowGeom choose_pow(const ChoiceIn& c, const Occupancy& occ, int nsplit_re
         if (bpc > 0) g.rounds = (int)((((long long)g.nb * g.nsplit * ceil_div(c.K, g.kp)) + (long long)bpc * n_cu - 1) / ((long long)bpc * n_cu));
     }
     return g;
+}
+
+// ---- the per-bin update ------------------------------------------------------------------------------------------------------
+// Which kernel launch_update runs (kernels_update.hip), for the plan, every batch, ILRMA and the PCA front end: one kind per kernel
+// family, the table of what each is launched with (kUpdTraits), and the one function that chooses (choose_update).  The launchers
+// behind launch_update only turn the integers of an UpdChoice into template arguments.
+//   Sq .. Det: square layout, 1..8 channels, MP x MP lanes per bin (update_sq_kernel, update_bg_kernel, update_gram_kernel,
+//   update_det_kernel); Rows: update_kernel, the row layout, SG lanes per bin (all kernels_update.hip); Wave16, Det16: one wavefront
+//   per bin of 9..16 channels (update_wave16_kernel, update_det16_kernel: kernels_update16.hip); Det16Rows: update_det16r_kernel,
+//   one matrix row per lane, three waves per four bins (kernels_update16r.hip); Wide: wide_update_kernel, 17..32 channels.
+enum class UpdKind { Sq, Bg, Gram, Det, Rows, Wave16, Det16, Det16Rows, Wide };
+constexpr int kUpdKinds = 9;
+static_assert((int)UpdKind::Wide + 1 == kUpdKinds, "one traits row per kind");
+
+// what the choice reads of the update's arguments (UpdateArgs, oiva_internal.h)
+struct UpdIn {
+    int M, K;
+    bool use_double;   // per-bin algebra in float64
+    bool vpart_f64;    // the covariance partials are float64
+    bool init_only;    // only the J initialisation of the prologue
+    int layout;        // 0: square (one lane per matrix element up to 8 channels), 1: one lane per matrix row
+    int nsplit;        // covariance splits behind V (a ragged batch: the largest)
+};
+// the process's switches (update_switches(), host_util.hip): $OIVA_UPDATE_GRAM (0: off, 2: measurement only, every K through the
+// Gram form), $OIVA_UPDATE_DET=0, $OIVA_DET16_INVERSE=1, $OIVA_DET16_ROWS=0
+struct UpdSwitches {
+    int gram = 1;
+    bool det = true, det16_inverse = false, det16_rows = true;
+};
+struct UpdChoice {
+    bool ok = false;               // false: no kernel takes these arguments
+    UpdKind kind = UpdKind::Sq;
+    int mp = 0;                    // Sq .. Det: MP, the padded channel count; Rows: SG, the lanes per bin
+    int mt = 0, kt = 0;            // channel and source count as compile-time constants (0: taken at run time)
+    bool f64 = false;              // arithmetic type (Gram, Det, Det16, Det16Rows, Wide: float64 always, not a template argument)
+    bool vpart_f64 = false;        // partial type (a template argument of the 9..16-channel kernels only)
+    bool flag = false;             // Wave16: OVER (K < M); Det16: INVERSE
+    int block = 0;                 // lanes per workgroup
+    int bins_per_block = 0;        // the grid is ceil_div(F, bins_per_block) workgroups
+};
+
+struct UpdTraits {
+    const char* kernel;
+    int m_lo, m_hi;                // channel counts
+    int block;
+    int bins;                      // bins per workgroup; 0: block / lanes per bin (MP x MP resp. SG of the choice)
+    int max_splits;                // covariance splits the kernel adds (0: any number)
+};
+constexpr UpdTraits kUpdTraits[kUpdKinds] = {
+    /* Sq        */ {"update_sq_kernel", 1, 8, kBlock, 0, 0},
+    /* Bg        */ {"update_bg_kernel", 3, 8, kBlock, 0, 0},
+    /* Gram      */ {"update_gram_kernel", 3, 8, kBlock, 0, 0},
+    /* Det       */ {"update_det_kernel", 2, 8, kBlock, 0, 0},
+    /* Rows      */ {"update_kernel", 1, kNarrowMax, kBlock, 0, 0},
+    /* Wave16    */ {"update_wave16_kernel", 9, kNarrowMax, 64, 1, 0},
+    /* Det16     */ {"update_det16_kernel", 9, kNarrowMax, 64, 1, 0},
+    // frame splits the eliminating waves add, two in flight at a time (more: the one-matrix-per-wave kernel)
+    /* Det16Rows */ {"update_det16r_kernel", 9, kNarrowMax, 192, 4, 4},
+    /* Wide      */ {"wide_update_kernel", kNarrowMax + 1, kWideMax, kBlock, 1, 0},
+};
+constexpr const UpdTraits& traits(UpdKind k) { return kUpdTraits[(int)k]; }
+
+// The instantiations there are of the 1..8-channel kernels: what choose_update can ask of the launcher of kernels_update.hip.
+// Channel count MT (MP / 2 < MT <= MP) as a compile-time constant, and with it the source counts the reference's own sweeps use
+// (overiva_sim_config.json: 2..8 microphones, 1..4 targets, determined AuxIVA): 1, 2, 3, 4, MT; other source counts (5 .. MT - 1)
+// at run time; one channel: the run-time-shape kernel.
+constexpr int upd_padded(int M) { return M <= 2 ? 2 : (M <= 4 ? 4 : (M <= 8 ? 8 : 16)); }
+constexpr bool upd_instantiated(UpdKind k, int mp, int mt, int kt) {
+    const bool shape = mt >= 2 && mt <= 8 && mp == upd_padded(mt);
+    const bool few = kt >= 1 && kt <= 4 && kt < mt, rest = kt == 0 && mt >= 6;
+    switch (k) {
+        case UpdKind::Sq: return (mp == 2 && mt == 0 && kt == 0) || (shape && (kt == mt || few || rest));
+        case UpdKind::Bg: return shape && mp >= 4 && few && kt <= 2;
+        case UpdKind::Gram: return shape && mp >= 4 && (few || rest);
+        case UpdKind::Det: return shape && kt == mt;
+        case UpdKind::Rows: return mt == 0 && kt == 0 && (mp == 2 || mp == 4 || mp == 8 || mp == 16);
+        default: return true;
+    }
+}
+
+// the rules, by priority: the first that holds
+inline UpdChoice choose_update(const UpdIn& u, const UpdSwitches& sw) {
+    UpdChoice c{};
+    const int M = u.M, K = u.K;
+    if (M < 1 || M > kWideMax || K < 1 || K > M) return c;
+    c.f64 = u.use_double, c.vpart_f64 = u.vpart_f64;
+    auto chosen = [&c](UpdKind k, int mp, int mt, int kt, bool flag = false) {
+        const UpdTraits& t = traits(k);
+        c.ok = true, c.kind = k, c.mp = mp, c.mt = mt, c.kt = kt, c.flag = flag;
+        c.block = t.block;
+        c.bins_per_block = t.bins ? t.bins : t.block / (k == UpdKind::Rows ? mp : mp * mp);
+        return c;
+    };
+    // 17..32 channels, either layout: the matrices live in LDS; float64 in every arithmetic mode (use_double is not consulted)
+    if (M > kNarrowMax) return chosen(UpdKind::Wide, 0, 0, 0);
+    // the row layout.  Run-time M and K only: folding them as constants made this variant slower (the fully unrolled source
+    // loop spills: 16 channels / 16 sources 0.89 -> 1.67 ms)
+    if (u.layout != 0) return chosen(UpdKind::Rows, upd_padded(M), 0, 0);
+    const bool det_case = K == M && u.use_double && !u.init_only;      // determined, float64, a whole update
+    if (M > 8) {      // 9..16 channels, square layout: one wavefront per bin ...
+        // ... or, determined in float64 on at most four splits, one matrix row per lane ($OIVA_DET16_ROWS=0: the kernels below)
+        if (sw.det16_rows && det_case && u.nsplit <= traits(UpdKind::Det16Rows).max_splits) return chosen(UpdKind::Det16Rows, 0, 0, 0);
+        if (sw.det && det_case) return chosen(UpdKind::Det16, 0, 0, 0, sw.det16_inverse);
+        return chosen(UpdKind::Wave16, 0, 0, 0, K < M);
+    }
+    // square layout, up to 8 channels: one lane per matrix element
+    const int mp = upd_padded(M);
+    if (M == 1) return chosen(UpdKind::Sq, mp, 0, 0);
+    // 1 or 2 sources with background channels: the structured chain with closed-form K x K solves; 3 and more (float64): the
+    // Gram form (update_gram_kernel).  2049 x 235, float64, update stage, generic kernel -> this dispatch: 8 / 3 23.0 -> 21.9 us,
+    // 6 / 3 20.2 -> 16.6, 5 / 3 18.7 -> 15.4, 8 / 4 39.5 -> 28.4, 6 / 4 37.8 -> 22.2, 8 / 6 64.2 -> 37.3; with one or two sources the
+    // Gram form is on a par with the structured chain (8 / 2 15.4 against 13.7 us, 6 / 2 11.2 / 11.9, 8 / 1 8.6 / 7.7), which
+    // the X-resident kernel shares.  (The J initialisation of the prologue keeps the generic kernel.)
+    if (mp >= 4 && !u.init_only && K < M) {
+        if (sw.gram == 2 && u.use_double && K <= 2) return chosen(UpdKind::Gram, mp, M, K);      // (measurement only: every K through the Gram form)
+        if (K <= 2) return chosen(UpdKind::Bg, mp, M, K);
+        if (sw.gram && u.use_double) return chosen(UpdKind::Gram, mp, M, K <= 4 ? K : 0);
+    }
+    // determined: one elimination for the inverse of W_hat^H, a rank-one step per source
+    // (float64 only: in float32 the explicit inverses cost accuracy -- 8 / 8 mixture, 20 iterations: 6.5 reference floors
+    //  against 2.8 with the elimination per source -- and `fast` keeps the latter)
+    if (sw.det && det_case) return chosen(UpdKind::Det, mp, M, M);
+    return chosen(UpdKind::Sq, mp, M, K == M || K <= 4 ? K : 0);
+}
+
+// the normal form of a choice: the kernel with its template arguments as a demangler prints them, `update_sq_kernel<8, double, 8, 2>`
+inline std::string update_kernel_name(const UpdChoice& c) {
+    const std::string r = c.f64 ? "double" : "float", v = c.vpart_f64 ? "double" : "float", b = c.flag ? "true" : "false";
+    const std::string mp = std::to_string(c.mp), mt = std::to_string(c.mt), kt = std::to_string(c.kt);
+    std::string args;
+    switch (c.kind) {
+        case UpdKind::Sq:
+        case UpdKind::Bg:
+        case UpdKind::Rows: args = mp + ", " + r + ", " + mt + ", " + kt; break;
+        case UpdKind::Gram: args = mp + ", " + mt + ", " + kt; break;
+        case UpdKind::Det: args = mp + ", double, " + mt; break;
+        case UpdKind::Wave16: args = r + ", " + v + ", " + b; break;
+        case UpdKind::Det16: args = v + ", " + b; break;
+        case UpdKind::Det16Rows: args = v; break;
+        case UpdKind::Wide: return traits(c.kind).kernel;
+    }
+    return std::string(traits(c.kind).kernel) + "<" + args + ">";
+}
+
+// ---- the fused covariance + update launch (kernels_cov_update.hip) -----------------------------------------------------------
+constexpr int kCovUpdateBins = 4;      // bins per workgroup = waves (one per bin in the update)
+// eligible: 8 channels, 2 sources, four frame splits of a whole number of 16-frame steps (what the plan chooses at the headline
+// shape)
+inline bool cov_update_supported(int M, int K, int T, int F, int nsplit, int tc) {
+    // (32-bit buffer offsets; whole steps: every split, and with it T, a multiple of 16 frames)
+    return M == 8 && K == 2 && nsplit == kWaves && tc % 16 == 0 && T % 16 == 0 && T > (kWaves - 1) * tc && F >= kCovUpdateBins &&
+           (size_t)T * F * M * 8 < ((size_t)1 << 31);       // (buffer addressing of X: 32-bit offsets)
 }
 
 }  // namespace oiva

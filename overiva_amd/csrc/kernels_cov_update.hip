@@ -238,13 +238,7 @@ __global__ __launch_bounds__(kBlock, 2) void cov_update_kernel(const float2* __r
 
 }  // namespace
 
-// eligible: 8 channels, 2 sources, four frame splits of a whole number of 16-frame steps (what the plan chooses at the headline
-// shape)
-bool cov_update_supported(int M, int K, int T, int F, int nsplit, int tc) {
-    // (32-bit buffer offsets; whole steps: every split, and with it T, a multiple of 16 frames)
-    return M == 8 && K == 2 && nsplit == kWaves && tc % 16 == 0 && T % 16 == 0 && T > (kWaves - 1) * tc && F >= kCuBins &&
-           (size_t)T * F * M * 8 < ((size_t)1 << 31);       // (buffer addressing of X: 32-bit offsets)
-}
+static_assert(kCuBins == kCovUpdateBins && kWaves == kCuBins, "cov_update_supported, kernel_choice.h: four bins, four splits, one wave each");
 
 hipError_t launch_cov_update(hipStream_t s, const float2* X, const float* R, float* wscale, int model, const UpdateArgs& a, int tc) {
     const dim3 grid((unsigned)((a.F + kCuBins - 1) / kCuBins));

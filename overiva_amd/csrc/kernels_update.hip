@@ -13,8 +13,6 @@
 // exchanged with sub-group shuffles; Gauss-Jordan elimination with partial pivoting never moves a
 // row (the pivot lane just broadcasts).  Every register array is indexed with compile-time
 // constants only (loops over columns are fully unrolled; run-time M and K enter as predicates).
-#include <cstdlib>
-
 #include "oiva_device.h"
 #include "update_chain.h"
 
@@ -629,128 +627,75 @@ __global__ __launch_bounds__(kBlock) void update_gram_kernel(UpdateArgs a) {
     if (fvalid && in) store_what<R>(a, ((size_t)f * M + j) * M + i, B.re, -B.im);
 }
 
+// the launch of a choice of the 1..8-channel kinds (kernel_choice.h): its integers as template arguments, nothing else.  MP follows
+// from MT; upd_instantiated says which kernels there are.
 template <int MP, int MT, int KT>
-hipError_t launch_gram_one(hipStream_t s, const UpdateArgs& a) {
-    const int bins_per_block = kBlock / (MP * MP);
-    dim3 grid((a.F + bins_per_block - 1) / bins_per_block);
-    hipLaunchKernelGGL((update_gram_kernel<MP, MT, KT>), grid, dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int MP, int MT>
-hipError_t launch_det_one(hipStream_t s, const UpdateArgs& a) {
-    const int bins_per_block = kBlock / (MP * MP);
-    dim3 grid((a.F + bins_per_block - 1) / bins_per_block);
-    hipLaunchKernelGGL((update_det_kernel<MP, double, MT>), grid, dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int MP, int MT, int KT>
-hipError_t launch_sq_one(hipStream_t s, const UpdateArgs& a) {
-    const int bins_per_block = kBlock / (MP * MP);
-    dim3 grid((a.F + bins_per_block - 1) / bins_per_block);
-    if (a.use_double)
-        hipLaunchKernelGGL((update_sq_kernel<MP, double, MT, KT>), grid, dim3(kBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL((update_sq_kernel<MP, float, MT, KT>), grid, dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-// specialised instantiations for the common shapes (full power-of-two channel count with 2 sources or
-// determined), generic otherwise
-template <int MP, int MT, int KT>
-hipError_t launch_bg_one(hipStream_t s, const UpdateArgs& a) {
-    const int bins_per_block = kBlock / (MP * MP);
-    dim3 grid((a.F + bins_per_block - 1) / bins_per_block);
-    if (a.use_double)
-        hipLaunchKernelGGL((update_bg_kernel<MP, double, MT, KT>), grid, dim3(kBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL((update_bg_kernel<MP, float, MT, KT>), grid, dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-// channel count MT (MP / 2 < MT <= MP) as a compile-time constant, and with it the source counts the reference's own
-// sweeps use (overiva_sim_config.json: 2..8 microphones, 1..4 targets, determined AuxIVA): 1, 2, 3, 4, MT
-template <int MP, int MT>
-hipError_t launch_sq_m(hipStream_t s, const UpdateArgs& a) {
-    // 1 or 2 sources with background channels: the structured chain with closed-form K x K solves; 3 and more (float64): the
-    // Gram form (update_gram_kernel).  2049 x 235, float64, update stage, generic kernel -> this dispatch: 8 / 3 23.0 -> 21.9 us,
-    // 6 / 3 20.2 -> 16.6, 5 / 3 18.7 -> 15.4, 8 / 4 39.5 -> 28.4, 6 / 4 37.8 -> 22.2, 8 / 6 64.2 -> 37.3; with one or two sources the
-    // Gram form is on a par with the structured chain (8 / 2 15.4 against 13.7 us, 6 / 2 11.2 / 11.9, 8 / 1 8.6 / 7.7), which
-    // the X-resident kernel shares.  (The J initialisation of the prologue keeps the generic kernel.)
-    if constexpr (MP >= 4) {
-        if (!a.init_only && a.K < MT) {
-            static const int gram = [] { const char* v = getenv("OIVA_UPDATE_GRAM"); return v ? atoi(v) : 1; }();
-            if (gram == 2 && a.use_double) {      // (measurement only: every K through the Gram form)
-                if (a.K == 1) return launch_gram_one<MP, MT, 1>(s, a);
-                if (a.K == 2) return launch_gram_one<MP, MT, 2>(s, a);
-            }
-            if (a.K == 2) return launch_bg_one<MP, MT, 2>(s, a);
-            if (a.K == 1) return launch_bg_one<MP, MT, 1>(s, a);
-            if (gram && a.use_double) {
-                if constexpr (MT > 3) if (a.K == 3) return launch_gram_one<MP, MT, 3>(s, a);
-                if constexpr (MT > 4) if (a.K == 4) return launch_gram_one<MP, MT, 4>(s, a);
-                if constexpr (MT > 5) return launch_gram_one<MP, MT, 0>(s, a);
-            }
-        }
+hipError_t launch_as(hipStream_t s, const UpdateArgs& a, const UpdChoice& c) {
+    const dim3 grid(ceil_div(a.F, c.bins_per_block)), block(c.block);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, a);
+        return hipGetLastError();
+    };
+    switch (c.kind) {
+        case UpdKind::Sq:
+            if constexpr (upd_instantiated(UpdKind::Sq, MP, MT, KT))
+                return c.f64 ? go(update_sq_kernel<MP, double, MT, KT>) : go(update_sq_kernel<MP, float, MT, KT>);
+            break;
+        case UpdKind::Bg:
+            if constexpr (upd_instantiated(UpdKind::Bg, MP, MT, KT))
+                return c.f64 ? go(update_bg_kernel<MP, double, MT, KT>) : go(update_bg_kernel<MP, float, MT, KT>);
+            break;
+        case UpdKind::Gram:
+            if constexpr (upd_instantiated(UpdKind::Gram, MP, MT, KT)) return go(update_gram_kernel<MP, MT, KT>);
+            break;
+        case UpdKind::Det:
+            if constexpr (upd_instantiated(UpdKind::Det, MP, MT, KT)) return go(update_det_kernel<MP, double, MT>);
+            break;
+        case UpdKind::Rows:
+            if constexpr (upd_instantiated(UpdKind::Rows, MP, MT, KT))
+                return c.f64 ? go(update_kernel<MP, double, MT, KT>) : go(update_kernel<MP, float, MT, KT>);
+            break;
+        default: break;
     }
-    if (a.K == MT) {
-        static const bool det = [] { const char* v = getenv("OIVA_UPDATE_DET"); return !(v && v[0] == '0'); }();
-        // (float64 only: in float32 the explicit inverses cost accuracy -- 8 / 8 mixture, 20 iterations: 6.5 reference floors
-        //  against 2.8 with the elimination per source -- and `fast` keeps the latter)
-        if (det && a.use_double && !a.init_only && MT >= 2) return launch_det_one<MP, MT>(s, a);
-        return launch_sq_one<MP, MT, MT>(s, a);
+    return hipErrorInvalidValue;
+}
+
+// (mt, kt) of the choice among 0..8 x 0..8, as constants
+template <int I = 0>
+hipError_t launch_square(hipStream_t s, const UpdateArgs& a, const UpdChoice& c) {
+    if constexpr (I < 81) {
+        if (c.mt == I / 9 && c.kt == I % 9) return c.mp == upd_padded(I / 9) ? launch_as<upd_padded(I / 9), I / 9, I % 9>(s, a, c) : hipErrorInvalidValue;
+        return launch_square<I + 1>(s, a, c);
     }
-    if constexpr (MT > 1) if (a.K == 1) return launch_sq_one<MP, MT, 1>(s, a);
-    if constexpr (MT > 2) if (a.K == 2) return launch_sq_one<MP, MT, 2>(s, a);
-    if constexpr (MT > 3) if (a.K == 3) return launch_sq_one<MP, MT, 3>(s, a);
-    if constexpr (MT > 4) if (a.K == 4) return launch_sq_one<MP, MT, 4>(s, a);
-    return launch_sq_one<MP, MT, 0>(s, a);
-}
-
-template <int MP>
-hipError_t launch_sq(hipStream_t s, const UpdateArgs& a) {
-    if (a.M == MP) return launch_sq_m<MP, MP>(s, a);
-    if constexpr (MP >= 4) if (a.M == MP - 1) return launch_sq_m<MP, MP - 1>(s, a);
-    if constexpr (MP >= 8) {
-        if (a.M == MP - 2) return launch_sq_m<MP, MP - 2>(s, a);
-        if (a.M == MP - 3) return launch_sq_m<MP, MP - 3>(s, a);
-    }
-    return launch_sq_one<MP, 0, 0>(s, a);
-}
-
-template <int SG, int MT, int KT>
-hipError_t launch_sg_one(hipStream_t s, const UpdateArgs& a) {
-    const int bins_per_block = kBlock / SG;
-    dim3 grid((a.F + bins_per_block - 1) / bins_per_block);
-    if (a.use_double)
-        hipLaunchKernelGGL((update_kernel<SG, double, MT, KT>), grid, dim3(kBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL((update_kernel<SG, float, MT, KT>), grid, dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int SG>
-hipError_t launch_sg(hipStream_t s, const UpdateArgs& a) {
-    // run-time M and K only: folding them as constants made this variant slower (the fully unrolled source
-    // loop spills: 16 channels / 16 sources 0.89 -> 1.67 ms)
-    return launch_sg_one<SG, 0, 0>(s, a);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
 
+static_assert(traits(UpdKind::Sq).block == kBlock && traits(UpdKind::Bg).block == kBlock && traits(UpdKind::Gram).block == kBlock &&
+              traits(UpdKind::Det).block == kBlock && traits(UpdKind::Rows).block == kBlock, "kernel_choice.h");
+
 hipError_t launch_update(hipStream_t s, const UpdateArgs& a) {
-    if (a.M > kNarrowMax) return launch_update_wide(s, a);      // (either layout: the matrices live in LDS)
-    if (a.layout == 0) {  // square layout: one lane per matrix element
-        if (a.M <= 2) return launch_sq<2>(s, a);
-        if (a.M <= 4) return launch_sq<4>(s, a);
-        if (a.M <= 8) return launch_sq<8>(s, a);
+    const UpdChoice c = choose_update({a.M, a.K, a.use_double != 0, a.vpart_f64 != 0, a.init_only != 0, a.layout, a.nsplit}, update_switches());
+    if (!c.ok) return hipErrorInvalidValue;
+    switch (c.kind) {
+        case UpdKind::Sq:
+        case UpdKind::Bg:
+        case UpdKind::Gram:
+        case UpdKind::Det: return launch_square(s, a, c);
+        case UpdKind::Rows:
+            switch (c.mp) {
+                case 2: return launch_as<2, 0, 0>(s, a, c);
+                case 4: return launch_as<4, 0, 0>(s, a, c);
+                case 8: return launch_as<8, 0, 0>(s, a, c);
+                case 16: return launch_as<16, 0, 0>(s, a, c);
+            }
+            return hipErrorInvalidValue;
+        case UpdKind::Wave16:
+        case UpdKind::Det16: return launch_update_wave16(s, a, c);
+        case UpdKind::Det16Rows: return launch_update_det16r(s, a, c);
+        case UpdKind::Wide: return launch_update_wide(s, a, c);
     }
-    if (a.layout == 0 && a.M > 8 && a.M <= 16) return launch_update_wave16(s, a);   // one wavefront per bin
-    if (a.M <= 2) return launch_sg<2>(s, a);
-    if (a.M <= 4) return launch_sg<4>(s, a);
-    if (a.M <= 8) return launch_sg<8>(s, a);
-    if (a.M <= 16) return launch_sg<16>(s, a);
     return hipErrorInvalidValue;
 }
 

@@ -5,7 +5,6 @@
 // bin and four matrix elements per lane (a 16 x 16 matrix has 256).
 #include "oiva_device.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace oiva {
@@ -711,31 +710,33 @@ __global__ __launch_bounds__(64) void update_det16_kernel(UpdateArgs a) {
 
 }  // namespace
 
-hipError_t launch_update_wave16(hipStream_t s, const UpdateArgs& a) {
-    if (update_det16r_applies(a)) return launch_update_det16r(s, a);       // (round 6; $OIVA_DET16_ROWS=0: the kernels below)
-    dim3 grid(a.F);
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(64), 0, s, a); };
-    const bool over = a.K < a.M;
-    static const bool det = [] { const char* v = getenv("OIVA_UPDATE_DET"); return !(v && v[0] == '0'); }();
-    if (det && !over && a.use_double && !a.init_only) {
-        static const bool inv = [] { const char* v = getenv("OIVA_DET16_INVERSE"); return v && v[0] == '1'; }();
-        if (a.vpart_f64) {
-            if (inv) go(update_det16_kernel<double, true>); else go(update_det16_kernel<double, false>);
-        } else {
-            if (inv) go(update_det16_kernel<float, true>); else go(update_det16_kernel<float, false>);
-        }
+static_assert(traits(UpdKind::Wave16).block == 64 && traits(UpdKind::Wave16).bins == 1 && traits(UpdKind::Det16).block == 64 &&
+              traits(UpdKind::Det16).bins == 1 && traits(UpdKind::Wave16).m_hi == N && traits(UpdKind::Det16).m_hi == N, "kernel_choice.h");
+
+hipError_t launch_update_wave16(hipStream_t s, const UpdateArgs& a, const UpdChoice& c) {
+    const dim3 grid(ceil_div(a.F, c.bins_per_block)), block(c.block);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, a);
         return hipGetLastError();
+    };
+    const int args = (c.f64 ? 4 : 0) + (c.vpart_f64 ? 2 : 0) + (c.flag ? 1 : 0);      // arithmetic, partials, OVER | INVERSE
+    if (c.kind == UpdKind::Det16) switch (args) {
+        case 4: return go(update_det16_kernel<float, false>);
+        case 5: return go(update_det16_kernel<float, true>);
+        case 6: return go(update_det16_kernel<double, false>);
+        case 7: return go(update_det16_kernel<double, true>);
     }
-#define OIVA_GO(RR, VV)                                         \
-    if (over) go(update_wave16_kernel<RR, VV, true>);           \
-    else go(update_wave16_kernel<RR, VV, false>);
-    if (a.use_double) {
-        if (a.vpart_f64) { OIVA_GO(double, double) } else { OIVA_GO(double, float) }
-    } else {
-        if (a.vpart_f64) { OIVA_GO(float, double) } else { OIVA_GO(float, float) }
+    if (c.kind == UpdKind::Wave16) switch (args) {
+        case 0: return go(update_wave16_kernel<float, float, false>);
+        case 1: return go(update_wave16_kernel<float, float, true>);
+        case 2: return go(update_wave16_kernel<float, double, false>);
+        case 3: return go(update_wave16_kernel<float, double, true>);
+        case 4: return go(update_wave16_kernel<double, float, false>);
+        case 5: return go(update_wave16_kernel<double, float, true>);
+        case 6: return go(update_wave16_kernel<double, double, false>);
+        case 7: return go(update_wave16_kernel<double, double, true>);
     }
-#undef OIVA_GO
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 }  // namespace oiva

@@ -30,7 +30,6 @@
 #include "oiva_device.h"
 
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 namespace oiva {
@@ -270,7 +269,7 @@ __global__ __launch_bounds__(192) void update_det16r_kernel(UpdateArgs a) {
         // The sources are not dealt out in advance: a wave takes the next one nobody has (a counter in LDS) when it starts on its
         // current one -- the hardware places the six waves of two workgroups on a CU's four SIMDs as {A}, {A, B}, {B, B}, {B}, and a
         // wave alone on its SIMD eliminates a source in half the time of one that shares it (2.5 against 5 us).  Source n goes
-        // through buffer n & 1 whoever eliminated it; wave 0 takes them in order.
+        // through buffer n % kFacBufs whoever eliminated it; wave 0 takes them in order.
         auto claim = [&]() {
             int nx = 0;
             if (lane == 0) nx = atomicAdd(&s.claim, 1);
@@ -555,18 +554,15 @@ __global__ __launch_bounds__(192) void update_det16r_kernel(UpdateArgs a) {
 
 }  // namespace
 
-// the determined float64 update of 9..16 channels with one matrix row per lane; false: not this kernel's case
-bool update_det16r_applies(const UpdateArgs& a) {
-    static const bool on = [] { const char* v = getenv("OIVA_DET16_ROWS"); return !(v && v[0] == '0'); }();
-    return on && a.K == a.M && a.M > 8 && a.M <= 16 && a.use_double && !a.init_only && a.layout == 0 && a.nsplit <= kMaxSplitsR;
-}
+static_assert(traits(UpdKind::Det16Rows).max_splits == kMaxSplitsR && traits(UpdKind::Det16Rows).bins == kBinsPerWaveR &&
+              traits(UpdKind::Det16Rows).block == 192 && traits(UpdKind::Det16Rows).m_hi == N, "kernel_choice.h");
 
-hipError_t launch_update_det16r(hipStream_t s, const UpdateArgs& a) {
-    const dim3 grid((a.F + kBinsPerWaveR - 1) / kBinsPerWaveR);
-    if (a.vpart_f64)
-        hipLaunchKernelGGL(update_det16r_kernel<double>, grid, dim3(192), 0, s, a);
+hipError_t launch_update_det16r(hipStream_t s, const UpdateArgs& a, const UpdChoice& c) {
+    const dim3 grid(ceil_div(a.F, c.bins_per_block)), block(c.block);
+    if (c.vpart_f64)
+        hipLaunchKernelGGL(update_det16r_kernel<double>, grid, block, 0, s, a);
     else
-        hipLaunchKernelGGL(update_det16r_kernel<float>, grid, dim3(192), 0, s, a);
+        hipLaunchKernelGGL(update_det16r_kernel<float>, grid, block, 0, s, a);
     return hipGetLastError();
 }
 

@@ -508,11 +508,11 @@ hipError_t launch_demix_write_wide(hipStream_t s, const float2* X, const float2*
     return launch_demix_wide<kWideWrite>(s, X, What, nullptr, Spart, nsplit, Y, T, F, M, K, 2, (T + tc - 1) / tc, tc);
 }
 
-hipError_t launch_update_wide(hipStream_t s, const UpdateArgs& a) {
-    if (!wide_channels(a.M) || a.K < 1 || a.K > a.M) return hipErrorInvalidValue;
-    // float64 in every arithmetic mode (a.use_double is not consulted); with `fast` (a.What64 == nullptr) W_hat is carried in
-    // complex64 between iterations
-    hipLaunchKernelGGL(wide_update_kernel, dim3(a.F), dim3(kBlock), 0, s, a);
+static_assert(traits(UpdKind::Wide).block == kBlock && traits(UpdKind::Wide).bins == 1, "kernel_choice.h");
+
+hipError_t launch_update_wide(hipStream_t s, const UpdateArgs& a, const UpdChoice& c) {
+    // float64 in every arithmetic mode; with `fast` (a.What64 == nullptr) W_hat is carried in complex64 between iterations
+    hipLaunchKernelGGL(wide_update_kernel, dim3(ceil_div(a.F, c.bins_per_block)), dim3(c.block), 0, s, a);
     return hipGetLastError();
 }
 

@@ -246,16 +246,17 @@ __device__ __forceinline__ void sum_vpart(const void* base, int f64, size_t idx,
         sum_vpart_t(static_cast<const float*>(base), idx, stride, nsplit, sr, si);
     if (!pair) si = 0.;
 }
+// the per-bin update: choose_update (kernel_choice.h) on the arguments and the process's switches, then the launcher of the file
+// that holds the chosen kernel -- which only turns the choice's integers into template arguments
 hipError_t launch_update(hipStream_t s, const UpdateArgs& a);
+const UpdSwitches& update_switches();      // the four environment switches, read once per process (host_util.hip)
+hipError_t launch_update_wave16(hipStream_t s, const UpdateArgs& a, const UpdChoice& c);   // Wave16, Det16 (kernels_update16.hip)
+hipError_t launch_update_det16r(hipStream_t s, const UpdateArgs& a, const UpdChoice& c);   // Det16Rows (kernels_update16r.hip)
 // covariance + per-bin update of the same bins in ONE launch (kernels_cov_update.hip): 8 channels, 2 sources + background,
 // float32 products; frames in four splits of tc (one per wave of a 4-bin workgroup).  Same bits as launch_cov followed by
-// launch_update when the plan's covariance geometry is those four splits.  a: What, What64, Cx, T, F, use_double.
-bool cov_update_supported(int M, int K, int T, int F, int nsplit, int tc);
+// launch_update when the plan's covariance geometry is those four splits (cov_update_supported, kernel_choice.h).
+// a: What, What64, Cx, T, F, use_double.
 hipError_t launch_cov_update(hipStream_t s, const float2* X, const float* R, float* wscale, int model, const UpdateArgs& a, int tc);
-hipError_t launch_update_wave16(hipStream_t s, const UpdateArgs& a);   // 9..16 channels, one wavefront per bin
-// determined float64 update of 9..16 channels, one matrix row per lane and four bins per wavefront (kernels_update16r.hip)
-bool update_det16r_applies(const UpdateArgs& a);
-hipError_t launch_update_det16r(hipStream_t s, const UpdateArgs& a);
 
 // Epilogue, overiva.py:192-199.
 //   stats: per-bin sums for projection back: [nsplit][F][K][3] = (Re num, Im num, den)
@@ -301,7 +302,7 @@ hipError_t launch_demix_stats_wide(hipStream_t s, const float2* X, const float2*
                                    const CovGeom& g);
 hipError_t launch_demix_write_wide(hipStream_t s, const float2* X, const float2* What, const float* Spart, int nsplit, float2* Y, int T,
                                    int F, int M, int K);
-hipError_t launch_update_wide(hipStream_t s, const UpdateArgs& a);
+hipError_t launch_update_wide(hipStream_t s, const UpdateArgs& a, const UpdChoice& c);
 
 // The batched iteration (kernels_batch.hip, batch.hip): B problems of one shape, <= 8 channels, `precise` arithmetic.
 //   X (B, T, F, M); What (B*F, M, M); Ppart [B][nb][T][K]; R: B buffers of r_stride floats (r_buffer_bytes(T, K) / 4);

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <cxxabi.h>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -1772,6 +1773,52 @@ int oiva_test_kernel_choice(int device, int T, int F, int F_total, int M, int K,
     const int o[18] = {(int)g.kind, g.nsplit, g.tc, g.kc, g.nbg, g.pad, g.part32, partials_f64(g, c.cov_f64) ? 1 : 0, (int)traits(g.kind).unit,
                        (int)w.kind, w.nb, w.nsplit, w.tcp, w.kp, w.rounds, asked[0], asked[1], p.n_cu};
     std::copy(o, o + 18, out);
+    return OIVA_OK;
+}
+
+int oiva_test_update_choice(int M, int K, int use_double, int vpart_f64, int init_only, int layout, int nsplit, char* name, int n) {
+    OIVA_NEED(name && n > 1 && M >= 1 && M <= OIVA_MAX_CHANNELS && K >= 1 && K <= M && nsplit >= 1, OIVA_ERR_ARG, "bad arguments");
+    UpdateArgs a{};      // (every pointer null: the launch is captured, never run)
+    a.vpart_f64 = vpart_f64 ? 1 : 0, a.nsplit = nsplit, a.T = 16, a.F = 1, a.M = M, a.K = K;
+    a.init_only = init_only ? 1 : 0, a.use_double = use_double ? 1 : 0, a.layout = layout ? 1 : 0;
+    hipStream_t s = nullptr;
+    OIVA_TRY_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    hipGraph_t graph = nullptr;
+    hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    const hipError_t launched = e == hipSuccess ? launch_update(s, a) : e;
+    if (e == hipSuccess) e = hipStreamEndCapture(s, &graph);
+    if (e == hipSuccess) e = launched;
+    std::string mangled;
+    size_t kernels = 0;
+    if (e == hipSuccess) {
+        size_t nodes = 0;
+        e = hipGraphGetNodes(graph, nullptr, &nodes);
+        std::vector<hipGraphNode_t> node(nodes);
+        if (e == hipSuccess && nodes) e = hipGraphGetNodes(graph, node.data(), &nodes);
+        for (size_t i = 0; e == hipSuccess && i < nodes; ++i) {
+            hipGraphNodeType type;
+            hipKernelNodeParams kp{};
+            if ((e = hipGraphNodeGetType(node[i], &type)) != hipSuccess || type != hipGraphNodeTypeKernel) continue;
+            if ((e = hipGraphKernelNodeGetParams(node[i], &kp)) != hipSuccess) break;
+            const char* nm = hipKernelNameRefByPtr(kp.func, s);
+            mangled = nm ? nm : "";
+            ++kernels;
+        }
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+    (void)hipStreamDestroy(s);
+    OIVA_TRY_HIP(e);
+    OIVA_NEED(kernels == 1 && !mangled.empty(), OIVA_ERR_STATE, "the captured update is not one named kernel launch");
+    // the normal form of kernel_choice.h: the demangled name without return type, namespaces and parameter list
+    int status = 0;
+    char* dem = abi::__cxa_demangle(mangled.c_str(), nullptr, nullptr, &status);
+    std::string nm = status == 0 && dem ? dem : mangled;
+    std::free(dem);
+    for (const char* drop : {"(anonymous namespace)::", "oiva::", "void "})
+        for (size_t at; (at = nm.find(drop)) != std::string::npos;) nm.erase(at, std::strlen(drop));
+    nm = nm.substr(0, nm.find('('));
+    OIVA_NEED((int)nm.size() < n, OIVA_ERR_ARG, "name buffer too small");
+    std::memcpy(name, nm.c_str(), nm.size() + 1);
     return OIVA_OK;
 }
 

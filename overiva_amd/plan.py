@@ -412,3 +412,13 @@ def kernel_choice(T, F, M, K, mode="fast", F_total=None, cov_quad=True, cov_hmfm
     d["x_n16"], d["x_nt"], d["x_why"], d["x_budget_mb"] = x[0], bool(x[1]), Plan.X_RESIDENT_REASONS[x[2]], mb.value
     d["cov_kind"], d["unit_kind"], d["pow_kind"] = COV_KINDS[d["cov_kind"]], COV_KINDS[d["unit_kind"]], POW_KINDS[d["pow_kind"]]
     return d
+
+
+def update_choice(M, K, use_double=False, vpart_f64=True, init_only=False, layout=0, nsplit=1):
+    """the per-bin update kernel that is launched for these fields of the update's arguments and this process's switches
+    (csrc/kernel_choice.h: choose_update), in its normal form, e.g. ``update_sq_kernel<8, double, 8, 2>``.  Test hook: the launch
+    is captured, not run, and the name is read from the captured kernel node; allocates nothing."""
+    name = C.create_string_buffer(128)
+    _lib.check(_lib.load().oiva_test_update_choice(int(M), int(K), int(bool(use_double)), int(bool(vpart_f64)), int(bool(init_only)),
+                                                   int(layout), int(nsplit), name, len(name)))
+    return name.value.decode()

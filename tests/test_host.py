@@ -198,6 +198,29 @@ def test_kernel_choice_replays_the_recorded_table(tmp_path):
     assert run.stdout.strip() == f"kernel choice ok: {len(kernel_choice_table.sweep())} rows"      # every row of the sweep
 
 
+def test_update_choice_replays_the_recorded_table(tmp_path):
+    """choose_update (csrc/kernel_choice.h, host only) against every row of tests/golden/update_choice.json -- the kernel the commit
+    before the function existed LAUNCHED for every input and switch, read from captured launches -- in a stand-alone program: the
+    same kernel and template arguments on every row, and the traits' invariants (the kind takes the channel and split count, the
+    launcher has the instantiation, a workgroup holds whole bins and the grid covers 1, bins_per_block + 1 and 2049 bins)"""
+    import subprocess
+
+    from overiva_amd import build
+
+    exe = tmp_path / "update_choice_main"
+    host_flags = [f for f in build.FLAGS if not f.startswith("--offload-arch")]
+    r = subprocess.run([build._hipcc(), *host_flags, os.path.join(REPO, "tests", "helpers", "update_choice_main.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    run = subprocess.run([str(exe), os.path.join(REPO, "tests", "golden", "update_choice.json")], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout[-4000:] + run.stderr
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import update_choice_table as table
+
+    rows = sum(len(table.set_rows(n)) for n in range(len(table.SETS)))
+    assert run.stdout.strip() == f"update choice ok: {rows} rows, 0 differ"      # every row of the sweep
+
+
 def test_resident_kernels_use_no_scratch_memory(lib):
     """the X-resident kernels hold 128 covariance accumulators in the architectural registers and up to 128 floats of X in
     the accumulator file; a build whose register allocation falls over into scratch memory (per-lane stack in HBM) would

@@ -11,6 +11,11 @@ problem ran).  Run it on two checkouts: the files are equal exactly when every c
   * ``ogive_batch`` for the three update modes at 2, 4 and 8 channels;
   * ``separate_batch`` on rooms of one length (an array) and of different lengths (a list).
 Inputs are ``oracle.synth_iid`` / ``synth_mixture`` with fixed seeds.
+
+    python tools/ab_batch_bits.py --update-cases --out tests/golden/update_parent_bits.json
+
+instead runs the batches of tests/helpers/update_choice_cases.py and puts their digests into the file, next to what
+``tools/ab_plan_bits.py --update-cases`` put there for the plans.
 """
 import argparse
 import hashlib
@@ -54,9 +59,19 @@ def dense_cases():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
+    ap.add_argument("--update-cases", action="store_true", help="the batches of tests/helpers/update_choice_cases.py, merged into --out")
     args = ap.parse_args()
     import overiva_amd as oa
     from oracle import overiva_oracle as orc
+    if args.update_cases:
+        sys.path.insert(1, os.path.join(REPO, "tests", "helpers"))
+        sys.path.insert(1, os.path.join(REPO, "tools"))
+        import update_choice_cases as uc
+        from ab_plan_bits import merge_into
+
+        n = merge_into(args.out, "batch ", {uc.batch_id(c): uc.combined(uc.run_batch(oa, orc, c)) for c in uc.BATCH_CASES})
+        print(json.dumps({"tool": "ab_batch_bits", "cases": n, "out": args.out}))
+        return
     from test_ragged_batch_gpu import BIT_CASES, _problems
 
     out = {}

@@ -7,6 +7,12 @@ and after 3 iterations and of Y with projection back (in that order; ``--parts``
 ``set_cov_splits(3)``; and one chunk of OGIVE epochs at one one-source shape per kind.  Only entry points every build has: run it
 on two checkouts, the files are equal exactly when every case gives the same bits.  Inputs are ``oracle.synth_iid`` with fixed
 seeds.
+
+    python tools/ab_plan_bits.py --update-cases --out tests/golden/update_parent_bits.json
+
+instead runs the plans of tests/helpers/update_choice_cases.py -- every per-bin update kernel family at one bin and at one bin more
+than a workgroup holds -- and puts one digest per case (over those of W after 1 and 3 iterations and of Y) into the file, next to what
+``tools/ab_batch_bits.py --update-cases`` put there for the batches.
 """
 import argparse
 import hashlib
@@ -72,13 +78,34 @@ def run_ogive(oa, orc, case):
         return {"W": digest(p.get_w(np.complex128)), "Y": digest(p.demix(proj_back=True)), "epochs": str(ran), "maxdelta": repr(md)}
 
 
+def merge_into(path, prefix, cases):
+    """the file at path with its entries of this prefix replaced by cases"""
+    out = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            out = {k: v for k, v in json.load(f).items() if not k.startswith(prefix)}
+    out.update(cases)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+    return len(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     ap.add_argument("--parts", action="store_true", help="the digests of every output of a case, not one per case")
+    ap.add_argument("--update-cases", action="store_true", help="the plans of tests/helpers/update_choice_cases.py, merged into --out")
     args = ap.parse_args()
     import overiva_amd as oa
     from oracle import overiva_oracle as orc
+    if args.update_cases:
+        import update_choice_cases as uc
+
+        n = merge_into(args.out, "plan ", {uc.plan_id(c): uc.combined(uc.run_plan(oa, orc, c)) for c in uc.PLAN_CASES})
+        print(json.dumps({"tool": "ab_plan_bits", "cases": n, "out": args.out}))
+        return
     from kernel_choice_cases import OGIVE_CASES, PLAN_CASES, case_id
 
     saved = os.environ.get("OIVA_HMFMA_PART32")
