@@ -568,6 +568,36 @@ oiva_status oiva_batch_ilrma_get_cov(oiva_batch *b, double *C, double *lambda);
 oiva_status oiva_batch_ilrma_time_stages(oiva_batch *b, int n, float *per_stage_ms);
 
 /*
+ * Batched ISS: determined AuxIVA by iterative source steering (rank-1 updates of the demixed signals; Scheibler & Ono, ICASSP
+ * 2020) on B rooms per set of launches (kernels_iss_batch.hip; DESIGN.md 3.15 states the algorithm, which is the contract).  The
+ * batch is made by oiva_batch_create or oiva_batch_create_ragged with K = M <= 8, and every room must satisfy T_b * M <= 8192
+ * (one bin's complex128 slab of 128 KiB of LDS): otherwise OIVA_ERR_ARG, as on a complex128 batch (oiva_batch_set_data_c128).
+ * X stays complex64; every stage is float64 and W is carried in complex128 as by oiva_batch_iterate.  The source model and the
+ * auxiliary weights are oiva_batch_iterate's (the batch's model); no covariance is formed and no linear system solved.
+ *   oiva_batch_iss_begin       : after oiva_batch_set_x_* and oiva_batch_set_w / _set_w_eig.  Allocates the state and forms the
+ *                                source powers of the W that is set (the sweep with no step)
+ *   oiva_batch_iss_stage       : one stage of an iteration (OIVA_ISS_STAGE_*), eager on the batch's stream
+ *   oiva_batch_iss_iterate     : n iterations = n times the stages in order (three launches per iteration whatever B)
+ *   oiva_batch_iss_time_stages : n iterations with events around every stage: per_stage_ms[2], ms per iteration by stage
+ *   oiva_batch_iss_sweep_steps : test hook: the sweep with its first n_steps rank-1 steps only, 0 <= n_steps <= M
+ *   oiva_batch_iss_get_weights : test hook: the weights 1 / max(r / gamma, eps) of the last activation, (sum T_b, M) float64
+ *   oiva_batch_iss_get_powers  : test hook: the source powers sum_f |y|^2 the last sweep left, (sum T_b, M) float64
+ * All but _begin return OIVA_ERR_STATE before _begin.  A room's bits do not depend on B, on its place in the batch or on the
+ * lengths of the other rooms.  The result is read with oiva_batch_demix / _demix_dev / _get_w / _status.
+ */
+enum {
+    OIVA_ISS_STAGE_ACTIVATION = 0,  /* r, gamma and the weights from the group powers; the columns of W scaled (two launches) */
+    OIVA_ISS_STAGE_SWEEP = 1        /* demix, the M rank-1 steps in LDS, the new W and the group powers (one launch) */
+};
+oiva_status oiva_batch_iss_begin(oiva_batch *b);
+oiva_status oiva_batch_iss_stage(oiva_batch *b, int stage);
+oiva_status oiva_batch_iss_iterate(oiva_batch *b, int n);
+oiva_status oiva_batch_iss_time_stages(oiva_batch *b, int n, float *per_stage_ms);
+oiva_status oiva_batch_iss_sweep_steps(oiva_batch *b, int n_steps);
+oiva_status oiva_batch_iss_get_weights(oiva_batch *b, double *phi);
+oiva_status oiva_batch_iss_get_powers(oiva_batch *b, double *p);
+
+/*
  * STFT analysis / synthesis on the GPU (hipFFT): time-domain audio in and out next to the solver.
  * Replaces, in the reference's drivers, pra.transform.analysis(mics_signals.T, framesize, framesize // 2, win=win_a)
  * (overiva_oneshot.py:293-295, overiva_sim.py:206-207) and pra.transform.synthesis(Y, framesize, framesize // 2,

@@ -148,6 +148,13 @@ SIGNATURES = {
     "oiva_batch_ilrma_get_pr": [_vp, _vp, _vp],
     "oiva_batch_ilrma_get_cov": [_vp, _vp, _vp],
     "oiva_batch_ilrma_time_stages": [_vp, _i, _fp],
+    "oiva_batch_iss_begin": [_vp],
+    "oiva_batch_iss_stage": [_vp, _i],
+    "oiva_batch_iss_iterate": [_vp, _i],
+    "oiva_batch_iss_time_stages": [_vp, _i, _fp],
+    "oiva_batch_iss_sweep_steps": [_vp, _i],
+    "oiva_batch_iss_get_weights": [_vp, _vp],
+    "oiva_batch_iss_get_powers": [_vp, _vp],
     "oiva_stft_create": [C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp],
     "oiva_stft_destroy": [_vp],
     "oiva_stft_shape": [_vp, C.POINTER(_i), C.POINTER(_i)],

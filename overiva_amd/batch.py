@@ -33,6 +33,8 @@ _overiva_module = sys.modules[__package__ + ".overiva"]   # (the package's attri
 MAX_CHANNELS = 8
 DATA_MODES = ("complex64", "complex128")
 ILRMA_STAGES = ("t_update", "v_update", "r_rewrite", "weighted_cov", "ip_update", "power", "normalise")   # OIVA_ILRMA_STAGE_*
+ISS_STAGES = ("activation", "sweep")   # OIVA_ISS_STAGE_*
+ISS_MAX_SLAB = 8192                    # frames x channels of one room at most: one bin's complex128 slab of 128 KiB of LDS
 _info = {}
 
 
@@ -40,7 +42,7 @@ def last_batch_info():
     """what the last batched call ran: ``{"precision": "precise", "batched": B, "data": "complex64" | "complex128", ...}``; after ``auxiva_pca_batch()`` also
     ``algorithm`` ("auxiva_pca") and ``reduced`` (the channel count of the inner solve); after
     ``ogive_batch()`` also ``epochs`` (B ints: epochs each problem ran) and ``converged`` (B bools: its stopping rule fired); after
-    ``ilrma_batch()`` also ``algorithm`` ("ilrma") and ``n_components``; after
+    ``ilrma_batch()`` also ``algorithm`` ("ilrma") and ``n_components``; after ``auxiva_iss_batch()`` ``algorithm`` ("auxiva_iss"); after
     ``overiva_batch_ragged()`` also ``ragged`` (True) and ``frames`` (B ints), ``shape`` then holding the largest T; after
     ``bss_eval_batch()`` ``algorithm`` ("bss_eval"), ``batched``, ``n_sources``, ``filter_length`` and, for rooms of different
     lengths, ``ragged`` (True) and ``lengths`` (B ints); after ``sweep_batch()`` ``algorithm`` ("sweep"), ``batched``,
@@ -80,6 +82,8 @@ class BatchPlan(_lib.Handle):
     ``auxiva_pca_batch()`` (pca_batch.py).  With K = 1, ``ogive_begin`` / ``ogive_iterate`` run OGIVE instead of
     ``iterate`` (``get_cx`` reads the input covariance for the host's ``init_eig``).  With K = M, ``ilrma_begin`` /
     ``ilrma_iterate`` run ILRMA (ilrma.py); ``ilrma_stage`` runs one stage of an epoch, ``get_nmf`` reads the source model.
+    With K = M, ``iss_begin`` / ``iss_iterate`` run determined AuxIVA by rank-1 ISS updates (iss.py), on a ragged plan too;
+    ``iss_stage`` runs one stage of an iteration.
 
     On the device X and Y are packed along the frames, (sum T_b, F, .): ``frames`` holds the B frame counts (here B times T)
     and ``offsets`` every problem's first frame.
@@ -263,6 +267,46 @@ class BatchPlan(_lib.Handle):
         arr = (C.c_float * len(ILRMA_STAGES))()
         _lib.check(self.lib.oiva_batch_ilrma_time_stages(self.h, int(n), arr))
         return dict(zip(ILRMA_STAGES, list(arr)))
+
+    def iss_begin(self):
+        """start ISS (iss.py; needs K = M, X and W set, ``T_b * M <= 8192`` in every room): forms the source powers of the
+        current W"""
+        self._no_c128("ISS")
+        _lib.check(self.lib.oiva_batch_iss_begin(self.h))
+
+    def iss_iterate(self, n=1):
+        self._no_c128("ISS")
+        _lib.check(self.lib.oiva_batch_iss_iterate(self.h, int(n)))
+
+    def iss_stage(self, stage):
+        """one stage of an iteration: a name of ``ISS_STAGES`` or its index"""
+        self._no_c128("ISS")
+        _lib.check(self.lib.oiva_batch_iss_stage(self.h, ISS_STAGES.index(stage) if isinstance(stage, str) else int(stage)))
+
+    def iss_sweep_steps(self, n_steps):
+        """test hook: the sweep with its first ``n_steps`` rank-1 steps only (0: demix and powers)"""
+        self._no_c128("ISS")
+        _lib.check(self.lib.oiva_batch_iss_sweep_steps(self.h, int(n_steps)))
+
+    def _iss_frames_by_k(self, fn):
+        out = np.empty((int(self.offsets[-1]), self.K), np.float64)
+        _lib.check(fn(self.h, _lib.ptr(out)))
+        return out.reshape(self.B, self.T, self.K) if self.dense else out
+
+    def get_iss_weights(self):
+        """test hook: the weights 1 / max(r / gamma, eps) of the last ISS activation, (B, T, K) float64, or packed
+        (sum T_b, K) on a ragged plan"""
+        return self._iss_frames_by_k(self.lib.oiva_batch_iss_get_weights)
+
+    def get_iss_powers(self):
+        """test hook: the source powers sum_f |y|^2 the last ISS sweep left, shaped as ``get_iss_weights``"""
+        return self._iss_frames_by_k(self.lib.oiva_batch_iss_get_powers)
+
+    def iss_time_stages(self, n):
+        """n iterations with events around every stage: {stage: ms per iteration}; advances the state"""
+        arr = (C.c_float * len(ISS_STAGES))()
+        _lib.check(self.lib.oiva_batch_iss_time_stages(self.h, int(n), arr))
+        return dict(zip(ISS_STAGES, list(arr)))
 
     def _demix_packed(self, proj_back, dtype):
         out = np.empty((int(self.offsets[-1]), self.F, self.K), dtype)

@@ -8,6 +8,8 @@
 // B*F bins.  Batched OGIVE (oiva_batch_ogive_*) runs on a batch of oiva_batch_create with K = 1, with its own kernels
 // (kernels_ogive_batch.hip) and a stopping rule per problem.  Batched ILRMA (oiva_batch_ilrma_*) runs on a batch of
 // oiva_batch_create with K = M: its NMF stages and its covariance pass are kernels_ilrma_batch.hip, its per-bin step the update.
+// Batched ISS (oiva_batch_iss_*) runs on a batch of either entry with K = M: determined AuxIVA by rank-1 updates of the demixed
+// signals, its two stages are kernels_iss_batch.hip, which read the table.
 // The PCA front end of auxiva_pca_batch (oiva_batch_set_w_pca,
 // _project_dev, _compose_w; kernels_pca_batch.hip) reads the table on the device for every batch.
 // A batch of either entry put into the complex128 data path (oiva_batch_set_data_c128, before X is set) holds X as complex128 and
@@ -35,6 +37,7 @@ constexpr int kOgFramesPerSplit = 64;     // frame splits of the OGIVE frame sum
 constexpr int kOgMinGraphEpochs = 8;      // shorter OGIVE chunks run eagerly
 constexpr int kIlrmaMaxComponents = 16;
 constexpr int kIlrmaStages = OIVA_ILRMA_STAGE_NORMALISE + 1;
+constexpr int kIssStages = OIVA_ISS_STAGE_SWEEP + 1;
 
 // geometry of the frame-split passes of a problem of T frames: a function of T alone (never of B or of other problems), so a
 // problem gets the same bits whatever batch it is in
@@ -107,6 +110,13 @@ struct oiva_batch {
     // batched ILRMA: the NMF state (Tn, Vn), the source models R and the powers P, allocated by ilrma_begin
     IlrmaState il{};
     bool il_ready = false;
+    // batched ISS: the group partial powers, the activations r and the weights, allocated by iss_begin
+    double* iss_part = nullptr;    // room b's [groups_b][T_b][M] at x_off_b * iss_groups * M
+    double* iss_rw = nullptr;      // (sum T_b, M): r
+    double* iss_phi = nullptr;     // (sum T_b, M): the weights
+    int iss_groups = 0;            // the grid: the most groups of any room
+    size_t iss_slab = 0;           // the largest group slab, bytes of dynamic LDS
+    bool iss_ready = false;
 };
 
 namespace {
@@ -264,6 +274,7 @@ int install_x(oiva_batch* b, const void* X) {
         b->X = static_cast<const float2*>(X);
     b->have_x = true;
     b->have_cx = false;
+    b->iss_ready = false;          // (its partial powers are of the old X)
     return OIVA_OK;
 }
 
@@ -362,6 +373,30 @@ int check_ilrma(oiva_batch* b, bool begun) {
     if (rc) return rc;
     OIVA_NEED(b->K == b->M, OIVA_ERR_ARG, "ILRMA is determined: create the batch with K = M");
     if (begun) OIVA_NEED(b->il_ready, OIVA_ERR_STATE, "call oiva_batch_ilrma_begin first");
+    return OIVA_OK;
+}
+
+// one stage of an ISS iteration (OIVA_ISS_STAGE_*); the sweep with n_steps of its M rank-1 steps
+int iss_stage(oiva_batch* b, int s, int n_steps) {
+    if (s == OIVA_ISS_STAGE_ACTIVATION)
+        OIVA_TRY_HIP(launch_iss_activation(b->stream, b->iss_part, b->iss_rw, b->iss_phi, b->What64, b->What, b->probs_dev, b->B, b->T, b->F,
+                                           b->M, b->model, b->iss_groups));
+    else
+        OIVA_TRY_HIP(launch_iss_sweep(b->stream, b->X, b->What64, b->What, b->iss_phi, b->iss_part, b->probs_dev, b->B, b->F, b->M,
+                                      b->iss_groups, b->iss_slab, n_steps));
+    return OIVA_OK;
+}
+
+int check_iss(oiva_batch* b, bool begun) {
+    OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(!b->c128, OIVA_ERR_ARG, "ISS is not supported on a complex128 batch");
+    OIVA_NEED(b->K == b->M, OIVA_ERR_ARG, "ISS is determined: create the batch with K = M");
+    for (const RaggedProblem& d : b->probs)
+        OIVA_NEED((long long)d.T * b->M <= kIssSlabElems, OIVA_ERR_ARG,
+                  "ISS needs T * M <= " + std::to_string(kIssSlabElems) + " in every room (one bin's slab of 128 KiB of LDS)");
+    OIVA_NEED(b->have_x, OIVA_ERR_STATE, "X not set (oiva_batch_set_x_host/_dev)");
+    OIVA_NEED(b->have_w, OIVA_ERR_STATE, "demixing matrices not set (oiva_batch_set_w)");
+    if (begun) OIVA_NEED(b->iss_ready, OIVA_ERR_STATE, "call oiva_batch_iss_begin first");
     return OIVA_OK;
 }
 
@@ -939,6 +974,117 @@ oiva_status oiva_batch_ilrma_time_stages(oiva_batch* b, int n, float* per_stage_
         }
     }
     for (int s = 0; s < kIlrmaStages; ++s) per_stage_ms[s] = (float)(acc[s] / n);
+    return OIVA_OK;
+}
+
+// ---- batched ISS (one room per batch entry of either kind, determined, eager launches) -----------------------------
+oiva_status oiva_batch_iss_begin(oiva_batch* b) {
+    int rc = check_iss(b, false);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    b->iss_ready = false;
+    if (!b->iss_phi) {                   // (the last of the state: all of it or none)
+        b->iss_groups = 0;
+        b->iss_slab = 0;
+        for (const RaggedProblem& d : b->probs) {
+            b->iss_groups = std::max(b->iss_groups, iss_groups(d.T, b->F, b->M));
+            b->iss_slab = std::max(b->iss_slab, (size_t)iss_group_bins(d.T, b->F, b->M) * d.T * b->M * sizeof(double2));
+        }
+        DeviceArena& mem = b->mem;
+        const size_t before = mem.mark();
+        mem.take(&b->iss_part, b->frames_total * b->iss_groups * b->M * sizeof(double));
+        mem.take(&b->iss_rw, b->frames_total * b->M * sizeof(double));
+        mem.take(&b->iss_phi, b->frames_total * b->M * sizeof(double));
+        if (!mem.ok()) {
+            mem.release_to(before);
+            return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(mem.status()));
+        }
+    }
+    OIVA_TRY_HIP(iss_sweep_prepare(b->M));
+    // the powers of the W that is set: demix and partial powers, no step
+    rc = iss_stage(b, OIVA_ISS_STAGE_SWEEP, 0);
+    if (rc) return rc;
+    b->iss_ready = true;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_iss_stage(oiva_batch* b, int stage) {
+    const int rc = check_iss(b, true);
+    if (rc) return rc;
+    OIVA_NEED(stage >= 0 && stage < kIssStages, OIVA_ERR_ARG, "unknown ISS stage");
+    DeviceGuard guard(b->device);
+    return iss_stage(b, stage, b->M);
+}
+
+oiva_status oiva_batch_iss_iterate(oiva_batch* b, int n) {
+    int rc = check_iss(b, true);
+    if (rc) return rc;
+    OIVA_NEED(n >= 0, OIVA_ERR_ARG, "n must be >= 0");
+    DeviceGuard guard(b->device);
+    for (int e = 0; e < n; ++e)
+        for (int s = 0; s < kIssStages; ++s)
+            if ((rc = iss_stage(b, s, b->M))) return rc;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_iss_sweep_steps(oiva_batch* b, int n_steps) {
+    const int rc = check_iss(b, true);
+    if (rc) return rc;
+    OIVA_NEED(n_steps >= 0 && n_steps <= b->M, OIVA_ERR_ARG, "n_steps must be in 0..M");
+    DeviceGuard guard(b->device);
+    return iss_stage(b, OIVA_ISS_STAGE_SWEEP, n_steps);
+}
+
+oiva_status oiva_batch_iss_get_weights(oiva_batch* b, double* phi) {
+    const int rc = check_iss(b, true);
+    if (rc) return rc;
+    OIVA_NEED(phi != nullptr, OIVA_ERR_ARG, "null argument");
+    DeviceGuard guard(b->device);
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(phi, b->iss_phi, b->frames_total * b->M * sizeof(double), hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_iss_get_powers(oiva_batch* b, double* p) {
+    const int rc = check_iss(b, true);
+    if (rc) return rc;
+    OIVA_NEED(p != nullptr, OIVA_ERR_ARG, "null argument");
+    DeviceGuard guard(b->device);
+    const size_t M = b->M;
+    std::vector<double> part(b->frames_total * b->iss_groups * M);
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(part.data(), b->iss_part, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    // every room's own groups, added as the activation adds them: 16 strided sequences, then those in order
+    for (const RaggedProblem& d : b->probs) {
+        const int ng = iss_groups(d.T, b->F, b->M);
+        const double* base = part.data() + d.x_off * b->iss_groups * M;
+        for (size_t i = 0; i < (size_t)d.T * M; ++i) {
+            double s = 0.;
+            for (int j = 0; j < kIssGroupLanes; ++j) {
+                double a = 0.;
+                for (int g = j; g < ng; g += kIssGroupLanes) a += base[(size_t)g * d.T * M + i];
+                s += a;
+            }
+            p[d.x_off * M + i] = s;
+        }
+    }
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_iss_time_stages(oiva_batch* b, int n, float* per_stage_ms) {
+    int rc = check_iss(b, true);
+    if (rc) return rc;
+    OIVA_NEED(n >= 1 && per_stage_ms, OIVA_ERR_ARG, "n must be >= 1");
+    DeviceGuard guard(b->device);
+    double acc[kIssStages] = {};
+    for (int e = 0; e < n; ++e) {
+        for (int s = 0; s < kIssStages; ++s) {
+            float ms = 0.f;
+            if ((rc = b->stream.elapsed_ms(0, 1, [&] { return iss_stage(b, s, b->M); }, &ms))) return rc;
+            acc[s] += ms;
+        }
+    }
+    for (int s = 0; s < kIssStages; ++s) per_stage_ms[s] = (float)(acc[s] / n);
     return OIVA_OK;
 }
 

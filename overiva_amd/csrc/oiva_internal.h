@@ -395,6 +395,34 @@ hipError_t launch_ilrma_cov(hipStream_t s, const float2* X, const IlrmaState& st
 //   rowsum, lam = sqrt(mean P), then P, R, Tn / lam^2 and W / lam (three launches)
 hipError_t launch_ilrma_normalise(hipStream_t s, const IlrmaState& st, float2* What, double2* What64, int B, int T, int F, int M);
 
+// Batched determined AuxIVA by iterative source steering (kernels_iss_batch.hip, batch.hip): B rooms from the
+// problem table, K = M <= 8, float64 on complex64 X.  A workgroup of the sweep holds a group of consecutive bins of one room as
+// complex128 in LDS; the group size is a function of the room's own T and of F and M alone.
+constexpr int kIssMaxGroup = 8;               // bins of a group at most
+constexpr int kIssSlabElems = 8192;           // T * M of one room at most: one bin's slab of 128 KiB
+constexpr int kIssSlabBytes = kIssSlabElems * 16;
+constexpr int kIssGroupLanes = 16;            // the activation adds a room's group partials in 16 strided sequences, then those in order
+__host__ __device__ inline int iss_group_bins(int T, int F, int M) {
+    const int fit = kIssSlabElems / (T * M);  // bins whose slab fits
+    int g = M < 4 ? kIssMaxGroup : 4;         // a frame's read of 128 bytes or more where it fits, a bin per wavefront
+    g = g < fit ? g : fit;
+    g = g < F ? g : F;
+    return g > 1 ? g : 1;
+}
+__host__ __device__ inline int iss_groups(int T, int F, int M) {
+    const int g = iss_group_bins(T, F, M);
+    return (F + g - 1) / g;
+}
+//   raises the dynamic LDS limit of the sweep kernel of M channels (once per device and M)
+hipError_t iss_sweep_prepare(int M);
+//   Part: room b's [iss_groups(T_b, F, M)][T_b][M] at x_off_b * max_groups * M; Phi (sum T_b, M): the weights; n_steps rank-1
+//   steps (0: demix and partial powers only); slab_bytes: the largest group slab of the batch
+hipError_t launch_iss_sweep(hipStream_t s, const float2* X, double2* What64, float2* What, const double* Phi, double* Part,
+                            const RaggedProblem* prob, int B, int F, int M, int max_groups, size_t slab_bytes, int n_steps);
+//   two launches: r into Rw (sum T_b, M); then gamma, the weights into Phi (sum T_b, M), W's columns scaled
+hipError_t launch_iss_activation(hipStream_t s, const double* Part, double* Rw, double* Phi, double2* What64, float2* What,
+                                 const RaggedProblem* prob, int B, int max_T, int F, int M, int model, int max_groups);
+
 // The batched STFT (kernels_bstft.hip, bstft.hip): the passes around hipFFT for B rooms at once.  One record per room; a dense
 // batch is the special case of equal records.
 struct BstftRoom {
