@@ -34,3 +34,6 @@ if __name__ == "__main__":
     # the same rooms through PCA to two channels + determined AuxIVA (the sweep's auxiva_pca column)
     ys = separate_batch(rooms, FRAME, HOP, n_src=SOURCES, n_iter=30, algorithm="auxiva_pca")
     print("auxiva_pca:", [y.shape for y in ys], "info", last_batch_info())
+    # one talker out of every room by FIVE (the sweep's one-target column without OGIVE's thousands of epochs)
+    ys = separate_batch(rooms, FRAME, HOP, n_iter=10, algorithm="five", init_eig=True)
+    print("five:", [y.shape for y in ys], "info", last_batch_info())

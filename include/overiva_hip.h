@@ -503,7 +503,8 @@ oiva_status oiva_batch_create_ragged(oiva_batch **out, int device, int B, const 
  *                                 OIVA_ERR_ARG ("complex128").
  *   oiva_batch_c128_get_weights : test hook: the activation weights 1 / max(r / gamma, eps) of the last iteration, (sum T_b, K)
  *   oiva_batch_c128_get_cov     : test hook: the weighted covariances of the last iteration, every problem's frame splits added
- *                                 in order and divided by its T_b, (B*F, K, M, M) complex128
+ *                                 in order and divided by its T_b, (B*F, K, M, M) complex128; the partials have one layout on
+ *                                 both data paths, so it also reads a complex64 batch (the FIVE tests: DESIGN.md 3.16)
  * A room's bits do not depend on B, on its place in the batch or on the other rooms' lengths.
  */
 oiva_status oiva_batch_set_data_c128(oiva_batch *b);
@@ -596,6 +597,37 @@ oiva_status oiva_batch_iss_time_stages(oiva_batch *b, int n, float *per_stage_ms
 oiva_status oiva_batch_iss_sweep_steps(oiva_batch *b, int n_steps);
 oiva_status oiva_batch_iss_get_weights(oiva_batch *b, double *phi);
 oiva_status oiva_batch_iss_get_powers(oiva_batch *b, double *p);
+
+/*
+ * Batched FIVE: single-source extraction by iterative SINR maximisation (Scheibler & Ono, "Fast independent vector extraction by
+ * iterative SINR maximization", ICASSP 2020) on B rooms per set of launches (kernels_five_batch.hip; DESIGN.md 3.16 states the
+ * algorithm, which is the contract).  The batch is made by oiva_batch_create or oiva_batch_create_ragged with K = 1 and M <= 8:
+ * otherwise OIVA_ERR_ARG, as on a complex128 batch (oiva_batch_set_data_c128).  An iteration is the demix and power pass, the
+ * activation and the weighted covariance with K = 1 (the batch's model) in float64 -- the stages of the complex128 data path, on
+ * a complex128 copy of the batch's complex64 X that _begin makes --, then the new per-bin step: the
+ * eigenpair (lambda, u) of V_f u = lambda Cx_f u with the smallest lambda in float64, w_f = u / sqrt(u^H V_f u).
+ *   oiva_batch_five_begin         : after oiva_batch_set_x_*, oiva_batch_covariance and oiva_batch_set_w / _set_w_eig.  Forms,
+ *                                   once per call, the complex128 copy of X and the reduction Li = L^-1 of Cx_f = L L^H of every bin (Li Cx_f Li^H = I); a
+ *                                   Cx_f that is not positive definite gives a non-finite Li and the room ends non-finite
+ *   oiva_batch_five_stage         : one stage of an iteration (OIVA_FIVE_STAGE_*), eager on the batch's stream
+ *   oiva_batch_five_iterate       : n iterations = n times the stages in order (four launches per iteration whatever B)
+ *   oiva_batch_five_time_stages   : n iterations with events around every stage: per_stage_ms[4], ms per iteration by stage
+ *   oiva_batch_five_get_reduction : test hook: Li, (B, F, M, M) complex128
+ * All but _begin return OIVA_ERR_STATE before _begin.  A room's bits do not depend on B, on its place in the batch or on the
+ * lengths of the other rooms.  The result is read with oiva_batch_demix / _demix_dev / _get_w / _status; once _begin has run,
+ * oiva_batch_demix with f64 = 1 forms Y in float64 from the complex128 copy of X (f64 = 0 and _demix_dev: the complex64 path).
+ */
+enum {
+    OIVA_FIVE_STAGE_POWER = 0,       /* y = w^H x and the powers sum_f |y|^2 */
+    OIVA_FIVE_STAGE_ACTIVATION = 1,  /* r from the powers */
+    OIVA_FIVE_STAGE_COV = 2,         /* V_f = mean_t x x^H / max(r_t / mean r, eps), as frame-split partials */
+    OIVA_FIVE_STAGE_UPDATE = 3       /* the smallest eigenpair of (V_f, Cx_f) per bin, the new w */
+};
+oiva_status oiva_batch_five_begin(oiva_batch *b);
+oiva_status oiva_batch_five_stage(oiva_batch *b, int stage);
+oiva_status oiva_batch_five_iterate(oiva_batch *b, int n);
+oiva_status oiva_batch_five_time_stages(oiva_batch *b, int n, float *per_stage_ms);
+oiva_status oiva_batch_five_get_reduction(oiva_batch *b, void *Li);
 
 /*
  * STFT analysis / synthesis on the GPU (hipFFT): time-domain audio in and out next to the solver.

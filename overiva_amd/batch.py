@@ -35,6 +35,7 @@ DATA_MODES = ("complex64", "complex128")
 ILRMA_STAGES = ("t_update", "v_update", "r_rewrite", "weighted_cov", "ip_update", "power", "normalise")   # OIVA_ILRMA_STAGE_*
 ISS_STAGES = ("activation", "sweep")   # OIVA_ISS_STAGE_*
 ISS_MAX_SLAB = 8192                    # frames x channels of one room at most: one bin's complex128 slab of 128 KiB of LDS
+FIVE_STAGES = ("power", "activation", "cov", "update")   # OIVA_FIVE_STAGE_*
 _info = {}
 
 
@@ -42,7 +43,7 @@ def last_batch_info():
     """what the last batched call ran: ``{"precision": "precise", "batched": B, "data": "complex64" | "complex128", ...}``; after ``auxiva_pca_batch()`` also
     ``algorithm`` ("auxiva_pca") and ``reduced`` (the channel count of the inner solve); after
     ``ogive_batch()`` also ``epochs`` (B ints: epochs each problem ran) and ``converged`` (B bools: its stopping rule fired); after
-    ``ilrma_batch()`` also ``algorithm`` ("ilrma") and ``n_components``; after ``auxiva_iss_batch()`` ``algorithm`` ("auxiva_iss"); after
+    ``ilrma_batch()`` also ``algorithm`` ("ilrma") and ``n_components``; after ``auxiva_iss_batch()`` ``algorithm`` ("auxiva_iss"); after ``five_batch()`` ``algorithm`` ("five"); after
     ``overiva_batch_ragged()`` also ``ragged`` (True) and ``frames`` (B ints), ``shape`` then holding the largest T; after
     ``bss_eval_batch()`` ``algorithm`` ("bss_eval"), ``batched``, ``n_sources``, ``filter_length`` and, for rooms of different
     lengths, ``ragged`` (True) and ``lengths`` (B ints); after ``sweep_batch()`` ``algorithm`` ("sweep"), ``batched``,
@@ -83,7 +84,8 @@ class BatchPlan(_lib.Handle):
     ``iterate`` (``get_cx`` reads the input covariance for the host's ``init_eig``).  With K = M, ``ilrma_begin`` /
     ``ilrma_iterate`` run ILRMA (ilrma.py); ``ilrma_stage`` runs one stage of an epoch, ``get_nmf`` reads the source model.
     With K = M, ``iss_begin`` / ``iss_iterate`` run determined AuxIVA by rank-1 ISS updates (iss.py), on a ragged plan too;
-    ``iss_stage`` runs one stage of an iteration.
+    ``iss_stage`` runs one stage of an iteration.  With K = 1, ``five_begin`` / ``five_iterate`` run FIVE (five.py), on a ragged
+    plan too; ``five_stage`` runs one stage of an iteration, ``get_five_reduction`` reads the reduction of the pencil.
 
     On the device X and Y are packed along the frames, (sum T_b, F, .): ``frames`` holds the B frame counts (here B times T)
     and ``offsets`` every problem's first frame.
@@ -308,6 +310,35 @@ class BatchPlan(_lib.Handle):
         _lib.check(self.lib.oiva_batch_iss_time_stages(self.h, int(n), arr))
         return dict(zip(ISS_STAGES, list(arr)))
 
+    def five_begin(self):
+        """start FIVE (five.py; needs K = 1, X, the covariance and W set): forms the complex128 copy of X its float64 stages
+        stream and the reduction of every bin's input covariance; afterwards ``demix(dtype=np.complex128)`` forms Y in float64"""
+        self._no_c128("FIVE")
+        _lib.check(self.lib.oiva_batch_five_begin(self.h))
+
+    def five_iterate(self, n=1):
+        self._no_c128("FIVE")
+        _lib.check(self.lib.oiva_batch_five_iterate(self.h, int(n)))
+
+    def five_stage(self, stage):
+        """one stage of an iteration: a name of ``FIVE_STAGES`` or its index"""
+        self._no_c128("FIVE")
+        _lib.check(self.lib.oiva_batch_five_stage(self.h, FIVE_STAGES.index(stage) if isinstance(stage, str) else int(stage)))
+
+    def get_five_reduction(self):
+        """test hook: Li (B, F, M, M) complex128 with Li Cx Li^H = I, the inverse of the lower Cholesky factor of every bin's Cx"""
+        self._no_c128("FIVE")
+        out = np.empty((self.B, self.F, self.M, self.M), np.complex128)
+        _lib.check(self.lib.oiva_batch_five_get_reduction(self.h, _lib.ptr(out)))
+        return out
+
+    def five_time_stages(self, n):
+        """n iterations with events around every stage: {stage: ms per iteration}; advances the state"""
+        self._no_c128("FIVE")
+        arr = (C.c_float * len(FIVE_STAGES))()
+        _lib.check(self.lib.oiva_batch_five_time_stages(self.h, int(n), arr))
+        return dict(zip(FIVE_STAGES, list(arr)))
+
     def _demix_packed(self, proj_back, dtype):
         out = np.empty((int(self.offsets[-1]), self.F, self.K), dtype)
         _lib.check(self.lib.oiva_batch_demix(self.h, _lib.ptr(out), 1 if out.dtype == np.complex128 else 0, 1 if proj_back else 0))
@@ -349,8 +380,8 @@ class BatchPlan(_lib.Handle):
         return out.reshape(self.B, self.T, self.K) if self.dense else out
 
     def get_weighted_cov(self):
-        """test hook of a complex128 plan: the weighted covariances V of the last iteration, every room's frame splits added in
-        order and divided by its T: (B, F, K, M, M) complex128"""
+        """test hook: the weighted covariances V of the last iteration (of the last ``cov`` stage of FIVE), every room's frame
+        splits added in order and divided by its T: (B, F, K, M, M) complex128; on either data path"""
         out = np.empty((self.B, self.F, self.K, self.M, self.M), np.complex128)
         _lib.check(self.lib.oiva_batch_c128_get_cov(self.h, _lib.ptr(out)))
         return out

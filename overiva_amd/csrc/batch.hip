@@ -10,6 +10,8 @@
 // oiva_batch_create with K = M: its NMF stages and its covariance pass are kernels_ilrma_batch.hip, its per-bin step the update.
 // Batched ISS (oiva_batch_iss_*) runs on a batch of either entry with K = M: determined AuxIVA by rank-1 updates of the demixed
 // signals, its two stages are kernels_iss_batch.hip, which read the table.
+// Batched FIVE (oiva_batch_five_*) runs on a batch of either entry with K = 1: the first three stages of the iteration, then the
+// smallest eigenpair of every bin's pencil (V, Cx) in place of the update (kernels_five_batch.hip, which reads the table).
 // The PCA front end of auxiva_pca_batch (oiva_batch_set_w_pca,
 // _project_dev, _compose_w; kernels_pca_batch.hip) reads the table on the device for every batch.
 // A batch of either entry put into the complex128 data path (oiva_batch_set_data_c128, before X is set) holds X as complex128 and
@@ -38,6 +40,7 @@ constexpr int kOgMinGraphEpochs = 8;      // shorter OGIVE chunks run eagerly
 constexpr int kIlrmaMaxComponents = 16;
 constexpr int kIlrmaStages = OIVA_ILRMA_STAGE_NORMALISE + 1;
 constexpr int kIssStages = OIVA_ISS_STAGE_SWEEP + 1;
+constexpr int kFiveStages = OIVA_FIVE_STAGE_UPDATE + 1;
 
 // geometry of the frame-split passes of a problem of T frames: a function of T alone (never of B or of other problems), so a
 // problem gets the same bits whatever batch it is in
@@ -117,6 +120,11 @@ struct oiva_batch {
     int iss_groups = 0;            // the grid: the most groups of any room
     size_t iss_slab = 0;           // the largest group slab, bytes of dynamic LDS
     bool iss_ready = false;
+    // batched FIVE: the reduction of every bin's Cx, formed by five_begin
+    double2* five_li = nullptr;    // (B*F, M, M): L^-1 of Cx = L L^H
+    double2* five_x128 = nullptr;  // (sum T_b, F, M): X widened to complex128, what the float64 stages of FIVE stream (with
+                                   // Ppart64, Rw64 and Gs64, which a complex64 batch does not hold otherwise)
+    bool five_ready = false;
 };
 
 namespace {
@@ -275,6 +283,7 @@ int install_x(oiva_batch* b, const void* X) {
     b->have_x = true;
     b->have_cx = false;
     b->iss_ready = false;          // (its partial powers are of the old X)
+    b->five_ready = false;         // (its reduction is of the old Cx)
     return OIVA_OK;
 }
 
@@ -400,6 +409,32 @@ int check_iss(oiva_batch* b, bool begun) {
     return OIVA_OK;
 }
 
+// one stage of a FIVE iteration (OIVA_FIVE_STAGE_*): the float64 stages 0 to 2 of stage() (the complex128 data path's, from the
+// problem table) with K = 1 on the widened X, then the per-bin eigenpair in place of the IP1 update (the activation's scale of
+// w does not matter: the step forms w afresh)
+int five_stage(oiva_batch* b, int s) {
+    if (s == OIVA_FIVE_STAGE_POWER)
+        OIVA_TRY_HIP(launch_c128_power(b->stream, b->five_x128, b->What64, b->Ppart64, b->probs_dev, b->B, b->T, b->F, b->M, 1));
+    else if (s == OIVA_FIVE_STAGE_ACTIVATION)
+        OIVA_TRY_HIP(launch_c128_activation(b->stream, b->Ppart64, b->Rw64, b->Gs64, b->What64, b->What, b->probs_dev, b->B, b->T, b->F,
+                                            b->M, 1, b->model, b->rblocks));
+    else if (s == OIVA_FIVE_STAGE_COV)
+        OIVA_TRY_HIP(launch_c128_cov(b->stream, b->five_x128, b->Rw64, b->probs_dev, b->Vpart, b->B, b->F, b->M, 1, b->nsplit));
+    else
+        OIVA_TRY_HIP(launch_five_update(b->stream, b->Vpart, b->five_li, b->What64, b->What, b->probs_dev, (int)nbins(b), b->F, b->M));
+    return OIVA_OK;
+}
+
+int check_five(oiva_batch* b, bool begun) {
+    OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(!b->c128, OIVA_ERR_ARG, "FIVE is not supported on a complex128 batch");
+    OIVA_NEED(b->K == 1, OIVA_ERR_ARG, "FIVE extracts one source: create the batch with K = 1");
+    const int rc = check_ready(b);
+    if (rc) return rc;
+    if (begun) OIVA_NEED(b->five_ready, OIVA_ERR_STATE, "call oiva_batch_five_begin first");
+    return OIVA_OK;
+}
+
 // the batch of frames[p] frames per problem (T = the largest); arguments checked by the callers
 int create_batch(oiva_batch** out, int device, const std::vector<int>& frames, int F, int M, int K, int model, void* stream) {
     DeviceGuard guard(device);
@@ -511,6 +546,7 @@ int oiva_batch_covariance(oiva_batch* b) {
         OIVA_TRY_HIP(launch_sum_parts(b->stream, b->Vpart, true, d.nsplit, b->Cx, (long long)nbins(b) * b->M * b->M, 1. / (double)d.T));
     }
     b->have_cx = true;
+    b->five_ready = false;
     return OIVA_OK;
 }
 
@@ -574,7 +610,13 @@ int oiva_batch_demix(oiva_batch* b, void* Y_host, int f64, int proj_back) {
         for (size_t i = 0; i < ny; ++i) out[i] = make_float2((float)y[i].x, (float)y[i].y);
         return OIVA_OK;
     }
-    if (f64 && !b->c128) {
+    if (f64 && !b->c128 && b->five_ready) {
+        // FIVE holds X widened to complex128: a complex128 Y is formed in float64 from it, not widened from the complex64 one
+        if (!b->Y128) OIVA_TRY_HIP(b->mem.take_one(&b->Y128, ny * sizeof(double2)));
+        if (proj_back && !b->Z128) OIVA_TRY_HIP(b->mem.take_one(&b->Z128, nbins(b) * b->K * sizeof(double2)));
+        OIVA_TRY_HIP(launch_c128_demix(b->stream, b->five_x128, b->What64, b->Z128, b->Y128, b->probs_dev, b->B, b->T, b->F, b->M, b->K,
+                                       proj_back != 0));
+    } else if (f64 && !b->c128) {
         if (!b->Y128) OIVA_TRY_HIP(b->mem.take_one(&b->Y128, ny * sizeof(double2)));
         OIVA_TRY_HIP(launch_cast_c64_to_c128(b->stream, b->Y, b->Y128, (long long)ny));
     }
@@ -699,8 +741,7 @@ oiva_status oiva_batch_c128_get_weights(oiva_batch* b, double* w) {
 
 oiva_status oiva_batch_c128_get_cov(oiva_batch* b, void* V) {
     OIVA_NEED(b && V, OIVA_ERR_ARG, "null argument");
-    OIVA_NEED(b->c128, OIVA_ERR_ARG, "not a complex128 batch");
-    const int rc = check_ready(b);
+    const int rc = check_ready(b);        // (either data path: Vpart has one layout)
     if (rc) return rc;
     DeviceGuard guard(b->device);
     const int M = b->M, K = b->K, MM = M * M;
@@ -1085,6 +1126,81 @@ oiva_status oiva_batch_iss_time_stages(oiva_batch* b, int n, float* per_stage_ms
         }
     }
     for (int s = 0; s < kIssStages; ++s) per_stage_ms[s] = (float)(acc[s] / n);
+    return OIVA_OK;
+}
+
+// ---- batched FIVE (one room per batch entry of either kind, one source, eager launches) ----------------------------
+oiva_status oiva_batch_five_begin(oiva_batch* b) {
+    const int rc = check_five(b, false);
+    if (rc) return rc;
+    DeviceGuard guard(b->device);
+    b->five_ready = false;
+    const size_t nx = b->frames_total * b->F * b->M;
+    if (!b->five_x128) {                 // (the last of the state: all of it or none)
+        DeviceArena& mem = b->mem;
+        const size_t before = mem.mark();
+        size_t p_doubles = 0;
+        for (const RaggedProblem& d : b->probs) p_doubles = std::max(p_doubles, d.p_off + (size_t)b->nb * d.T);
+        mem.take(&b->five_li, nbins(b) * b->M * b->M * sizeof(double2));
+        mem.take(&b->Ppart64, p_doubles * sizeof(double));
+        mem.take(&b->Rw64, b->frames_total * sizeof(double));
+        mem.take(&b->Gs64, (size_t)b->B * b->rblocks * sizeof(double));
+        mem.take(&b->five_x128, nx * sizeof(double2));
+        if (!mem.ok()) {
+            mem.release_to(before);
+            b->five_li = nullptr, b->Ppart64 = b->Rw64 = b->Gs64 = nullptr, b->five_x128 = nullptr;
+            return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(mem.status()));
+        }
+    }
+    OIVA_TRY_HIP(launch_cast_c64_to_c128(b->stream, b->X, b->five_x128, (long long)nx));
+    OIVA_TRY_HIP(launch_five_begin(b->stream, b->Cx, b->five_li, (int)nbins(b), b->M));
+    b->five_ready = true;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_five_stage(oiva_batch* b, int stage) {
+    const int rc = check_five(b, true);
+    if (rc) return rc;
+    OIVA_NEED(stage >= 0 && stage < kFiveStages, OIVA_ERR_ARG, "unknown FIVE stage");
+    DeviceGuard guard(b->device);
+    return five_stage(b, stage);
+}
+
+oiva_status oiva_batch_five_iterate(oiva_batch* b, int n) {
+    int rc = check_five(b, true);
+    if (rc) return rc;
+    OIVA_NEED(n >= 0, OIVA_ERR_ARG, "n must be >= 0");
+    DeviceGuard guard(b->device);
+    for (int e = 0; e < n; ++e)
+        for (int s = 0; s < kFiveStages; ++s)
+            if ((rc = five_stage(b, s))) return rc;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_five_time_stages(oiva_batch* b, int n, float* per_stage_ms) {
+    int rc = check_five(b, true);
+    if (rc) return rc;
+    OIVA_NEED(n >= 1 && per_stage_ms, OIVA_ERR_ARG, "n must be >= 1");
+    DeviceGuard guard(b->device);
+    double acc[kFiveStages] = {};
+    for (int e = 0; e < n; ++e) {
+        for (int s = 0; s < kFiveStages; ++s) {
+            float ms = 0.f;
+            if ((rc = b->stream.elapsed_ms(0, 1, [&] { return five_stage(b, s); }, &ms))) return rc;
+            acc[s] += ms;
+        }
+    }
+    for (int s = 0; s < kFiveStages; ++s) per_stage_ms[s] = (float)(acc[s] / n);
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_five_get_reduction(oiva_batch* b, void* Li) {
+    const int rc = check_five(b, true);
+    if (rc) return rc;
+    OIVA_NEED(Li != nullptr, OIVA_ERR_ARG, "null argument");
+    DeviceGuard guard(b->device);
+    OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
+    OIVA_TRY_HIP(hipMemcpy(Li, b->five_li, nbins(b) * b->M * b->M * sizeof(double2), hipMemcpyDeviceToHost));
     return OIVA_OK;
 }
 

@@ -423,6 +423,15 @@ hipError_t launch_iss_sweep(hipStream_t s, const float2* X, double2* What64, flo
 hipError_t launch_iss_activation(hipStream_t s, const double* Part, double* Rw, double* Phi, double2* What64, float2* What,
                                  const RaggedProblem* prob, int B, int max_T, int F, int M, int model, int max_groups);
 
+// Batched FIVE (kernels_five_batch.hip, batch.hip): the per-bin step of single-source extraction, the smallest
+// eigenpair of the pencil (V_f, Cx_f) of nbins = B*F bins of M <= 8 channels in float64, 16 lanes per bin.
+//   Li (nbins, M, M) complex128 = L^-1 of the Cholesky factor Cx_f = L L^H; non-finite where Cx_f is not positive definite
+hipError_t launch_five_begin(hipStream_t s, const double* Cx, double2* Li, int nbins, int M);
+//   Vpart [max nsplit][nbins][1][M*M]: bin f's room prob[f / F] adds its own nsplit partials in order and divides by its T;
+//   w = Li^H u / sqrt(lambda) into column 0 of What64 and of What
+hipError_t launch_five_update(hipStream_t s, const double* Vpart, const double2* Li, double2* What64, float2* What,
+                              const RaggedProblem* prob, int nbins, int F, int M);
+
 // The batched STFT (kernels_bstft.hip, bstft.hip): the passes around hipFFT for B rooms at once.  One record per room; a dense
 // batch is the special case of equal records.
 struct BstftRoom {

@@ -20,6 +20,7 @@ from . import ive as _ive
 from . import pca_batch as _pca_batch
 from . import stft as _stft
 from .batch import DeviceBatch
+from .five import run_five          # (the package's attribute `five` is the function)
 from .overiva import get_device
 
 MAX_CHANNELS = _batch.MAX_CHANNELS
@@ -171,8 +172,8 @@ def _check_separate_args(x, frame, hop, n_src, n_iter, algorithm, model, win_a, 
         dtype, M, lens = rooms.dtype, rooms.shape[2], [rooms.shape[1]] * rooms.shape[0]
     if dtype.kind not in "fiu":
         raise ValueError(f"x must be real, got dtype {dtype}")
-    if algorithm not in ("overiva", "ogive", "auxiva_pca", "auxiva_iss"):
-        raise ValueError(f"algorithm must be 'overiva', 'ogive', 'auxiva_pca' or 'auxiva_iss', got {algorithm!r}")
+    if algorithm not in ("overiva", "ogive", "auxiva_pca", "auxiva_iss", "five"):
+        raise ValueError(f"algorithm must be 'overiva', 'ogive', 'auxiva_pca', 'auxiva_iss' or 'five', got {algorithm!r}")
     if algorithm == "ogive" and ragged:
         raise ValueError("OGIVE does not run on a ragged batch: give algorithm='ogive' rooms of one length as a (B, n_samples, M) array")
     if algorithm != "ogive" and algo_kwargs:
@@ -190,6 +191,10 @@ def _check_separate_args(x, frame, hop, n_src, n_iter, algorithm, model, win_a, 
     if algorithm == "ogive":
         if n_src not in (None, 1):
             raise ValueError("OGIVE extracts one source: n_src must be 1 (or None)")
+        K = 1
+    elif algorithm == "five":
+        if n_src is not None and (isinstance(n_src, bool) or not isinstance(n_src, (int, np.integer)) or n_src != 1):
+            raise ValueError(f"FIVE extracts one source: n_src must be None or 1, got {n_src!r}")
         K = 1
     elif algorithm == "auxiva_iss":
         if n_src is not None and (isinstance(n_src, bool) or not isinstance(n_src, (int, np.integer)) or n_src != M):
@@ -217,7 +222,7 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
                    init_eig=False, W0=None, proj_back=True, return_filters=False, **algo_kwargs):
     """
     Audio in, audio out for B rooms: STFT, ``overiva_batch`` / ``overiva_batch_ragged`` / ``ogive_batch`` / ``auxiva_pca_batch`` /
-    ``auxiva_iss_batch`` and inverse STFT with X and Y never leaving the device (the chain of reference overiva_sim.py:206-207, 298-315 for many rooms per call).
+    ``auxiva_iss_batch`` / ``five_batch`` and inverse STFT with X and Y never leaving the device (the chain of reference overiva_sim.py:206-207, 298-315 for many rooms per call).
 
     Parameters
     ----------
@@ -228,7 +233,8 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
     n_src, n_iter, model, init_eig, W0, proj_back, return_filters:
         as ``overiva_batch()`` (``n_src=None``: determined AuxIVA)
     algorithm: "overiva", "auxiva_iss" (determined AuxIVA by rank-1 ISS updates, as ``auxiva_iss_batch()``: ``n_src`` None or
-        n_chan), "ogive" (one source, rooms of one length; ``step_size``, ``tol``, ``update`` as ``ogive_batch()``) or
+        n_chan), "five" (one source by FIVE, as ``five_batch()``: ``n_src`` None or 1; rooms of any lengths), "ogive" (one
+        source, rooms of one length; ``step_size``, ``tol``, ``update`` as ``ogive_batch()``) or
         "auxiva_pca" (PCA to ``n_src`` channels, then determined AuxIVA, as ``auxiva_pca_batch()``: ``W0`` starts the reduced
         solve, (n_freq, n_src, n_src); ``proj_back`` is ignored, the result is always projected back; W is the composed filters)
     win_a, win_s: analysis / synthesis windows; default ``stft.hann(frame)`` and its ``stft.compute_synthesis_window`` when
@@ -258,6 +264,9 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
             elif algorithm == "auxiva_iss":
                 _iss.run_iss(plan, n_iter, W0, init_eig)
                 info.update(algorithm="auxiva_iss")
+            elif algorithm == "five":
+                run_five(plan, n_iter, W0, init_eig)
+                info.update(algorithm="five")
             else:
                 if W0 is None and init_eig:
                     plan.set_w_eig()
