@@ -44,8 +44,15 @@ EXTRA_FLAGS = {"kernels_resident_m8.hip": _RESIDENT, "kernels_resident_m4.hip": 
                "kernels_resident_m2.hip": _RESIDENT}
 # every file that holds kernels leaves its resource remarks next to its object: tests/test_host.py checks that no kernel of the
 # iteration spills to scratch memory (round 5: a select of an (re, im) pair put 80 bytes per lane of update_det16_kernel there)
+# "holds kernels" is read from the source, not from its name (exchange.hip has one): tools/kernel_census.py takes the list of
+# compiled kernels from these remarks, and a kernel in a file without them would be missing from it
+def _holds_kernels(src):
+    with open(os.path.join(CSRC, src)) as f:
+        return "__global__" in f.read()
+
+
 for _src in SOURCES:
-    if _src.startswith("kernels_") or _src == "stft.hip":
+    if _src.startswith("kernels_") or _src == "stft.hip" or _holds_kernels(_src):
         EXTRA_FLAGS.setdefault(_src, _REMARKS)
 
 

@@ -205,6 +205,9 @@ constexpr int pow_sources_per_pass(int /*M*/, int K) {
     //  140 -> 111: eight demixing products per frame make the pass arithmetic-bound, two passes of four overlap)
     return K >= 3 ? 4 : (K >= 2 ? 2 : 1);
 }
+// the (channels, sources per pass) that rule can ask for with K <= M: the launchers of the lane power kernels (plan, batch, ragged
+// batch, PCA projection) instantiate these and no others (tests/test_kernel_census.py)
+constexpr bool pow_kp_reachable(int M, int kp) { return kp == 1 || (kp == 2 && M >= 2) || (kp == 4 && M >= 3); }
 constexpr PowTraits kPowTraits[kPowKinds] = {
     /* Lane */ {[](int M, int K) { return M >= 1 && M <= kNarrowMax && K >= 1 && K <= M && (M <= 8 || K <= 4); }, [](int K) { return pow_sources_per_pass(0, K); }, kBinsPerWave * kWaves, 4, false, true},
     // more than 4 sources would take several VALU passes over X (register budget): one MFMA pass instead

@@ -10,12 +10,16 @@
 // the frame within the problem (never of B, of the problem's place in the batch, or of the grid position): a problem gets the
 // same bits alone, in a batch of 8, or in a permuted batch.  The per-bin stages that read neither X nor the activations (the
 // update, the J initialisation, the eigensolver) run the single-problem kernels on B*F bins (UpdateArgs::wscale_bins).
+#include <type_traits>
 #include "oiva_device.h"
 #include "activation_arith.h"
 #include "demix_arith.h"
 #include "batch_cov_arith.h"
 
 namespace oiva {
+// (the kernel of a (channels, sources per pass) pair is instantiated only where pow_kp_reachable holds: kernel_choice.h)
+template <int I>
+using IntC = std::integral_constant<int, I>;
 namespace {
 
 // ---------------------------------------------------------------------------------------------
@@ -81,11 +85,16 @@ hipError_t launch_batch_power(hipStream_t s, const float2* X, const float2* What
     const dim3 grid((unsigned)nb, (unsigned)nsplit, (unsigned)(B * nz));
     const size_t shmem = (size_t)kWaves * tcp * kp * sizeof(float);
     if (M < 1 || M > 8 || tcp > kPowMaxFrames) return hipErrorInvalidValue;
-#define CALL(MM)                                                                                                              \
-    if (kp == 1) hipLaunchKernelGGL((batch_power_kernel<MM, 1>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, tcp, nz); \
-    else if (kp == 2) hipLaunchKernelGGL((batch_power_kernel<MM, 2>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, tcp, nz); \
-    else if (kp == 4) hipLaunchKernelGGL((batch_power_kernel<MM, 4>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, tcp, nz); \
-    else return hipErrorInvalidValue;
+    auto go = [&](auto mm, auto kk) -> hipError_t {      // (a generic lambda: the branch not taken is not instantiated)
+        constexpr int MM = decltype(mm)::value, KP = decltype(kk)::value;
+        if constexpr (pow_kp_reachable(MM, KP)) {
+            hipLaunchKernelGGL((batch_power_kernel<MM, KP>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, tcp, nz);
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;
+    };
+#define CALL(MM) \
+    return kp == 1 ? go(IntC<MM>{}, IntC<1>{}) : kp == 2 ? go(IntC<MM>{}, IntC<2>{}) : kp == 4 ? go(IntC<MM>{}, IntC<4>{}) : hipErrorInvalidValue;
     OIVA_BATCH_DISPATCH_M(CALL)
 #undef CALL
     return hipGetLastError();

@@ -418,26 +418,29 @@ hipError_t dispatch_kc(int kc, bool unit, bool rows, Fn&& fn) {
                 break;
         }
         return hipErrorInvalidValue;
+    } else {
+        // (instantiated only where the choice can ask for it: two sources per pass need two channels, four need three --
+        //  lane_sources_per_pass, K <= M -- and 4 and 8 channels in float32 never come here; tests/test_kernel_census.py)
+        switch (kc) {
+            case 1:
+                return fn((CovKernel<ACC>)cov_kernel<M, 1, false, ACC>, 1);
+            case 2:
+                if constexpr (kRegs * 2 <= 144 && M >= 2) return fn((CovKernel<ACC>)cov_kernel<M, 2, false, ACC>, 2);
+                break;
+            case 4:
+                if constexpr (kRegs * 4 <= 144 && M >= 3) return fn((CovKernel<ACC>)cov_kernel<M, 4, false, ACC>, 4);
+                break;
+            // (round 5) one source more than the budget of 144 accumulator registers allows where that saves a pass over X on a
+            // short frame axis: 7 channels x 3 sources (147), 5 x 5 (125) -- see cov_sources_per_pass
+            case 3:
+                if constexpr (M == 7 && sizeof(ACC) == 4) return fn((CovKernel<ACC>)cov_kernel<M, 3, false, ACC>, 3);
+                break;
+            case 5:
+                if constexpr (M == 5 && sizeof(ACC) == 4) return fn((CovKernel<ACC>)cov_kernel<M, 5, false, ACC>, 5);
+                break;
+        }
+        return hipErrorInvalidValue;
     }
-    switch (kc) {
-        case 1:
-            return fn((CovKernel<ACC>)cov_kernel<M, 1, false, ACC>, 1);
-        case 2:
-            if constexpr (kRegs * 2 <= 144) return fn((CovKernel<ACC>)cov_kernel<M, 2, false, ACC>, 2);
-            break;
-        case 4:
-            if constexpr (kRegs * 4 <= 144) return fn((CovKernel<ACC>)cov_kernel<M, 4, false, ACC>, 4);
-            break;
-        // (round 5) one source more than the budget of 144 accumulator registers allows where that saves a pass over X on a
-        // short frame axis: 7 channels x 3 sources (147), 5 x 5 (125) -- see cov_sources_per_pass
-        case 3:
-            if constexpr (M == 7 && sizeof(ACC) == 4) return fn((CovKernel<ACC>)cov_kernel<M, 3, false, ACC>, 3);
-            break;
-        case 5:
-            if constexpr (M == 5 && sizeof(ACC) == 4) return fn((CovKernel<ACC>)cov_kernel<M, 5, false, ACC>, 5);
-            break;
-    }
-    return hipErrorInvalidValue;
 }
 
 template <typename ACC, typename Fn>
@@ -450,7 +453,10 @@ hipError_t dispatch_cov(int M, int kc, bool unit, bool rows, Fn&& fn) {
         case 5: return dispatch_kc<5, ACC>(kc, unit, rows, fn);
         case 6: return dispatch_kc<6, ACC>(kc, unit, rows, fn);
         case 7: return dispatch_kc<7, ACC>(kc, unit, rows, fn);
-        case 8: return dispatch_kc<8, ACC>(kc, unit, rows, fn);
+        case 8:
+            // (8 channels in float64 are cov_pair64_kernel's, with weights and with unit weights: choose_cov_kind, traits(..).unit)
+            if constexpr (sizeof(ACC) == 4) return dispatch_kc<8, ACC>(kc, unit, rows, fn);
+            break;
     }
     return hipErrorInvalidValue;
 }

@@ -297,17 +297,29 @@ __global__ __launch_bounds__(kBlock) void write_kernel(const float2* __restrict_
 template <int M, int KP>
 hipError_t launch_power_one(hipStream_t s, const float2* X, const float2* What, float* Ppart, int T, int F, int K,
                             const PowGeom& g) {
+    if constexpr (!pow_kp_reachable(M, KP)) return hipErrorInvalidValue;      // (more sources per pass than channels: never asked for)
     dim3 grid(g.nb, g.nsplit, (K + KP - 1) / KP);
     const size_t shmem = (size_t)kWaves * g.tcp * KP * sizeof(float);
-    if constexpr (M == 8) {
+    // (the streamed form: X streams only behind the lane covariance kernel, which 8 channels take with one or two sources --
+    //  choose_cov_kind, choose_x_policy)
+    if constexpr (M == 8 && KP <= 2) {
         if (g.xplain < kXPeriod) {
             if (g.xctc < g.tcp || g.xctc % kXGroup != 0) return hipErrorInvalidValue;      // (choose_x_policy never asks for it)
             hipLaunchKernelGGL((power_kernel<M, KP, true>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, g.tcp, g.rev, g.ord, g.xplain, g.xctc);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((power_kernel<M, KP, false>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, g.tcp, g.rev, g.ord, kXPeriod, 0);
-    return hipGetLastError();
+    if constexpr (pow_kp_reachable(M, KP)) {
+        hipLaunchKernelGGL((power_kernel<M, KP, false>), grid, dim3(kBlock), shmem, s, X, What, Ppart, T, F, K, g.tcp, g.rev, g.ord, kXPeriod, 0);
+        return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int M, int KP>
+hipError_t pow_occupancy_one(int* n, size_t shmem) {
+    if constexpr (pow_kp_reachable(M, KP)) return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, power_kernel<M, KP>, kBlock, shmem);
+    return hipErrorInvalidValue;
 }
 
 template <int M, int KP>
@@ -353,9 +365,9 @@ hipError_t launch_write_one(hipStream_t s, const float2* X, const float2* What, 
 hipError_t pow_blocks_per_cu(int M, int kp, int tcp, int* n) {
     const size_t shmem = (size_t)kWaves * tcp * kp * sizeof(float);
 #define CALL(MM)                                                                                                   \
-    if (kp == 1) return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, power_kernel<MM, 1>, kBlock, shmem);       \
-    if (kp == 2) return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, power_kernel<MM, 2>, kBlock, shmem);       \
-    if (kp == 4) return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, power_kernel<MM, 4>, kBlock, shmem);
+    if (kp == 1) return pow_occupancy_one<MM, 1>(n, shmem);       \
+    if (kp == 2) return pow_occupancy_one<MM, 2>(n, shmem);       \
+    if (kp == 4) return pow_occupancy_one<MM, 4>(n, shmem);
     OIVA_DISPATCH_M(CALL)
 #undef CALL
     return hipErrorInvalidValue;

@@ -11,10 +11,14 @@
 // consumed -- and the per-lane arithmetic of the epilogue (load_wconj / demix_one, demix_arith.h): every output element is the
 // float32 FMA chain write_kernel (kernels_demix.hip) forms without projection back.  No sum crosses lanes, so a problem's bits do
 // not depend on the batch it is in.  A workgroup past its own problem's extent returns at entry.
+#include <type_traits>
 #include "oiva_device.h"
 #include "demix_arith.h"
 
 namespace oiva {
+// (the kernel of a (channels, sources per pass) pair is instantiated only where pow_kp_reachable holds: kernel_choice.h)
+template <int I>
+using IntC = std::integral_constant<int, I>;
 namespace {
 
 template <int M, int KP>
@@ -106,11 +110,16 @@ hipError_t launch_pca_project(hipStream_t s, const float2* X, const float2* What
     const int nz = (K + kp - 1) / kp;
     const dim3 grid((unsigned)nb, (unsigned)max_pw_nsplit, (unsigned)(B * nz));
     if (M < 1 || M > 8 || K < 1 || K > M) return hipErrorInvalidValue;
-#define CALL(MM)                                                                                                           \
-    if (kp == 1) hipLaunchKernelGGL((pca_project_kernel<MM, 1>), grid, dim3(kBlock), 0, s, X, What, Xr, prob, F, K, nz);      \
-    else if (kp == 2) hipLaunchKernelGGL((pca_project_kernel<MM, 2>), grid, dim3(kBlock), 0, s, X, What, Xr, prob, F, K, nz); \
-    else if (kp == 4) hipLaunchKernelGGL((pca_project_kernel<MM, 4>), grid, dim3(kBlock), 0, s, X, What, Xr, prob, F, K, nz); \
-    else return hipErrorInvalidValue;
+    auto go = [&](auto mm, auto kk) -> hipError_t {      // (a generic lambda: the branch not taken is not instantiated)
+        constexpr int MM = decltype(mm)::value, KP = decltype(kk)::value;
+        if constexpr (pow_kp_reachable(MM, KP)) {
+            hipLaunchKernelGGL((pca_project_kernel<MM, KP>), grid, dim3(kBlock), 0, s, X, What, Xr, prob, F, K, nz);
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;
+    };
+#define CALL(MM) \
+    return kp == 1 ? go(IntC<MM>{}, IntC<1>{}) : kp == 2 ? go(IntC<MM>{}, IntC<2>{}) : kp == 4 ? go(IntC<MM>{}, IntC<4>{}) : hipErrorInvalidValue;
     switch (M) {
         case 1: CALL(1); break;
         case 2: CALL(2); break;

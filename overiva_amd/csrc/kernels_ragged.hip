@@ -11,12 +11,16 @@
 // activation_block, batch_cov_block), so problem b gets the bits of a dense batch of T_b frames.  A grid is sized by the largest
 // problem; a workgroup past its own problem's extent returns at entry, before any barrier.  The records are read through a
 // pointer, so a captured graph stays valid for the batch's life.
+#include <type_traits>
 #include "oiva_device.h"
 #include "activation_arith.h"
 #include "batch_cov_arith.h"
 #include "demix_arith.h"
 
 namespace oiva {
+// (the kernel of a (channels, sources per pass) pair is instantiated only where pow_kp_reachable holds: kernel_choice.h)
+template <int I>
+using IntC = std::integral_constant<int, I>;
 namespace {
 
 // demix + power (grid = 64-bin batches x max power splits x problem * source passes)
@@ -87,11 +91,16 @@ hipError_t launch_ragged_power(hipStream_t s, const float2* X, const float2* Wha
     const dim3 grid((unsigned)nb, (unsigned)max_pw_nsplit, (unsigned)(B * nz));
     const size_t shmem = (size_t)kWaves * max_tcp * kp * sizeof(float);
     if (M < 1 || M > 8 || max_tcp > kPowMaxFrames) return hipErrorInvalidValue;
-#define CALL(MM)                                                                                                                   \
-    if (kp == 1) hipLaunchKernelGGL((ragged_power_kernel<MM, 1>), grid, dim3(kBlock), shmem, s, X, What, Ppart, prob, F, K, nz);      \
-    else if (kp == 2) hipLaunchKernelGGL((ragged_power_kernel<MM, 2>), grid, dim3(kBlock), shmem, s, X, What, Ppart, prob, F, K, nz); \
-    else if (kp == 4) hipLaunchKernelGGL((ragged_power_kernel<MM, 4>), grid, dim3(kBlock), shmem, s, X, What, Ppart, prob, F, K, nz); \
-    else return hipErrorInvalidValue;
+    auto go = [&](auto mm, auto kk) -> hipError_t {      // (a generic lambda: the branch not taken is not instantiated)
+        constexpr int MM = decltype(mm)::value, KP = decltype(kk)::value;
+        if constexpr (pow_kp_reachable(MM, KP)) {
+            hipLaunchKernelGGL((ragged_power_kernel<MM, KP>), grid, dim3(kBlock), shmem, s, X, What, Ppart, prob, F, K, nz);
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;
+    };
+#define CALL(MM) \
+    return kp == 1 ? go(IntC<MM>{}, IntC<1>{}) : kp == 2 ? go(IntC<MM>{}, IntC<2>{}) : kp == 4 ? go(IntC<MM>{}, IntC<4>{}) : hipErrorInvalidValue;
     OIVA_RAGGED_DISPATCH_M(CALL)
 #undef CALL
     return hipGetLastError();

@@ -278,11 +278,18 @@ template <int MODE>
 hipError_t launch_demix_wide(hipStream_t s, const float2* X, const float2* What, float* out, const float* Spart, int nsplit_s, float2* Y,
                              int T, int F, int M, int K, int kp, int nsplit, int tc) {
     const dim3 grid((F + 63) / 64, nsplit, (K + kp - 1) / kp);
-    if (kp == 1) hipLaunchKernelGGL((wide_demix_kernel<1, MODE>), grid, dim3(kBlock), 0, s, X, What, out, Spart, nsplit_s, Y, T, F, M, K, tc);
-    else if (kp == 2) hipLaunchKernelGGL((wide_demix_kernel<2, MODE>), grid, dim3(kBlock), 0, s, X, What, out, Spart, nsplit_s, Y, T, F, M, K, tc);
-    else if (kp == 4) hipLaunchKernelGGL((wide_demix_kernel<4, MODE>), grid, dim3(kBlock), 0, s, X, What, out, Spart, nsplit_s, Y, T, F, M, K, tc);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    // (the statistics and the write of the epilogue take two sources per pass whatever K; only the power pass has 1 and 4)
+    if (kp == 2) {
+        hipLaunchKernelGGL((wide_demix_kernel<2, MODE>), grid, dim3(kBlock), 0, s, X, What, out, Spart, nsplit_s, Y, T, F, M, K, tc);
+        return hipGetLastError();
+    }
+    if constexpr (MODE == kWidePower) {
+        if (kp == 1) hipLaunchKernelGGL((wide_demix_kernel<1, MODE>), grid, dim3(kBlock), 0, s, X, What, out, Spart, nsplit_s, Y, T, F, M, K, tc);
+        else if (kp == 4) hipLaunchKernelGGL((wide_demix_kernel<4, MODE>), grid, dim3(kBlock), 0, s, X, What, out, Spart, nsplit_s, Y, T, F, M, K, tc);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -1253,9 +1253,11 @@ hipError_t launch_resident_m(hipStream_t s, const ResidentArgs& a, int K, bool u
         }
         return hipErrorInvalidValue;
     }
-    if (K == 2) {
-        if (regs) return update_f64 ? launch_resident_one<M, 2, JRM, double>(s, a) : launch_resident_one<M, 2, JRM, float>(s, a);
-        return update_f64 ? launch_resident_one<M, 2, 0, double>(s, a) : launch_resident_one<M, 2, 0, float>(s, a);
+    if constexpr (M > 2) {      // (sources with background channels only, K < M: resident_geometry)
+        if (K == 2) {
+            if (regs) return update_f64 ? launch_resident_one<M, 2, JRM, double>(s, a) : launch_resident_one<M, 2, JRM, float>(s, a);
+            return update_f64 ? launch_resident_one<M, 2, 0, double>(s, a) : launch_resident_one<M, 2, 0, float>(s, a);
+        }
     }
     if (K == 1) {
         if (regs) return update_f64 ? launch_resident_one<M, 1, JRM, double>(s, a) : launch_resident_one<M, 1, JRM, float>(s, a);

@@ -232,7 +232,9 @@ def test_resident_kernels_use_no_scratch_memory(lib):
     if not any(os.path.exists(os.path.join(build.OBJ, s + ".usage.txt")) for s in ("kernels_resident_m4", "kernels_resident_m8", "kernels_resident_m6", "kernels_resident_m2")):
         build.build_library(force=True)          # objects came from a build without remarks
     usage = build.resident_kernel_usage()
-    assert len(usage) >= 26, usage.keys()      # 2, 4, 6, 8 channels x sources x frame residency x arithmetic
+    # 2, 4, 6, 8 channels x sources x frame residency x arithmetic; 26 until the two of 2 channels with 2 sources went, which
+    # resident_geometry never asks for (K < M; tests/test_kernel_census.py)
+    assert len(usage) == 24, usage.keys()
     for name, u in usage.items():
         assert u["scratch"] == 0, (name, u)
         assert u["vgprs"] + u["agprs"] <= 512
