@@ -630,6 +630,34 @@ oiva_status oiva_batch_five_time_stages(oiva_batch *b, int n, float *per_stage_m
 oiva_status oiva_batch_five_get_reduction(oiva_batch *b, void *Li);
 
 /*
+ * Batched IP2: OverIVA / AuxIVA whose demixing vectors are updated two at a time by the exact minimiser of the surrogate over the
+ * pair (Ono, "Fast stereo independent vector analysis and its implementation on mobile phone", IWAENC 2012; Scheibler & Ono's
+ * OverIVA-IP2) on B rooms per set of launches (kernels_ip2_batch.hip; DESIGN.md 3.17 states the algorithm, which is the
+ * contract).  The batch is made by oiva_batch_create or oiva_batch_create_ragged with 1 <= K <= M <= 8; a complex128 batch
+ * (oiva_batch_set_data_c128) is refused with OIVA_ERR_ARG.  Needs X, the covariance and W (OIVA_ERR_STATE otherwise).  An
+ * iteration is the demix and power pass, the activation (which scales W) and the weighted covariances of all K sources in
+ * float64 -- the stages of the complex128 data path, on a complex128 copy of the batch's complex64 X made on first use --, then
+ * the per-bin schedule of the iteration's index n, counted from the start of the separation:
+ *     n even: (0,1), (2,3), ..., then (K-1) alone if K is odd;   n odd and K > 2: (0) alone, (1,2), ..., then (K-1) alone if K
+ *     is even;   K = 2: (0,1) always;   K = 1: (0) alone.   A single step is IP1; J follows every step when K < M.
+ *   oiva_batch_ip2_iterate     : iterations first_iteration .. first_iteration + n - 1 (five launches each whatever B); the index
+ *                                is explicit, so the result does not depend on how a run is cut into calls
+ *   oiva_batch_ip2_stage       : one stage (OIVA_IP2_STAGE_*) of iteration `iteration`, eager on the batch's stream
+ *   oiva_batch_ip2_time_stages : iterations 0 .. n - 1 with events around every stage: per_stage_ms[4], ms per iteration by stage
+ * A room's bits do not depend on B, on its place in the batch or on the lengths of the other rooms.  The result is read with
+ * oiva_batch_demix / _demix_dev / _get_w / _status.
+ */
+enum {
+    OIVA_IP2_STAGE_POWER = 0,       /* y = W^H x and the powers sum_f |y|^2 */
+    OIVA_IP2_STAGE_ACTIVATION = 1,  /* r, gamma and the weights from the powers; the columns of W scaled */
+    OIVA_IP2_STAGE_COV = 2,         /* V_s = mean_t x x^H / max(r_ts / gamma_s, eps) for every source, as frame-split partials */
+    OIVA_IP2_STAGE_UPDATE = 3       /* the schedule of pair and single steps per bin */
+};
+oiva_status oiva_batch_ip2_iterate(oiva_batch *b, int first_iteration, int n);
+oiva_status oiva_batch_ip2_stage(oiva_batch *b, int stage, int iteration);
+oiva_status oiva_batch_ip2_time_stages(oiva_batch *b, int n, float *per_stage_ms);
+
+/*
  * STFT analysis / synthesis on the GPU (hipFFT): time-domain audio in and out next to the solver.
  * Replaces, in the reference's drivers, pra.transform.analysis(mics_signals.T, framesize, framesize // 2, win=win_a)
  * (overiva_oneshot.py:293-295, overiva_sim.py:206-207) and pra.transform.synthesis(Y, framesize, framesize // 2,

@@ -160,6 +160,9 @@ SIGNATURES = {
     "oiva_batch_five_iterate": [_vp, _i],
     "oiva_batch_five_time_stages": [_vp, _i, _fp],
     "oiva_batch_five_get_reduction": [_vp, _vp],
+    "oiva_batch_ip2_iterate": [_vp, _i, _i],
+    "oiva_batch_ip2_stage": [_vp, _i, _i],
+    "oiva_batch_ip2_time_stages": [_vp, _i, _fp],
     "oiva_stft_create": [C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp],
     "oiva_stft_destroy": [_vp],
     "oiva_stft_shape": [_vp, C.POINTER(_i), C.POINTER(_i)],

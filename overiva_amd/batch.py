@@ -36,6 +36,7 @@ ILRMA_STAGES = ("t_update", "v_update", "r_rewrite", "weighted_cov", "ip_update"
 ISS_STAGES = ("activation", "sweep")   # OIVA_ISS_STAGE_*
 ISS_MAX_SLAB = 8192                    # frames x channels of one room at most: one bin's complex128 slab of 128 KiB of LDS
 FIVE_STAGES = ("power", "activation", "cov", "update")   # OIVA_FIVE_STAGE_*
+IP2_STAGES = ("power", "activation", "cov", "update")    # OIVA_IP2_STAGE_*
 _info = {}
 
 
@@ -338,6 +339,25 @@ class BatchPlan(_lib.Handle):
         arr = (C.c_float * len(FIVE_STAGES))()
         _lib.check(self.lib.oiva_batch_five_time_stages(self.h, int(n), arr))
         return dict(zip(FIVE_STAGES, list(arr)))
+
+    def ip2_iterate(self, first, n=1):
+        """iterations ``first .. first + n - 1`` of IP2 (ip2.py; needs X, the covariance and W set): the index of an iteration,
+        counted from the start of the separation, selects its schedule, so a run may be cut into calls anywhere"""
+        self._no_c128("IP2")
+        _lib.check(self.lib.oiva_batch_ip2_iterate(self.h, int(first), int(n)))
+
+    def ip2_stage(self, stage, iteration=0):
+        """one stage of iteration ``iteration``: a name of ``IP2_STAGES`` or its index"""
+        self._no_c128("IP2")
+        _lib.check(self.lib.oiva_batch_ip2_stage(self.h, IP2_STAGES.index(stage) if isinstance(stage, str) else int(stage),
+                                                 int(iteration)))
+
+    def ip2_time_stages(self, n):
+        """iterations 0 .. n - 1 with events around every stage: {stage: ms per iteration}; advances the state"""
+        self._no_c128("IP2")
+        arr = (C.c_float * len(IP2_STAGES))()
+        _lib.check(self.lib.oiva_batch_ip2_time_stages(self.h, int(n), arr))
+        return dict(zip(IP2_STAGES, list(arr)))
 
     def _demix_packed(self, proj_back, dtype):
         out = np.empty((int(self.offsets[-1]), self.F, self.K), dtype)

@@ -12,6 +12,8 @@
 // signals, its two stages are kernels_iss_batch.hip, which read the table.
 // Batched FIVE (oiva_batch_five_*) runs on a batch of either entry with K = 1: the first three stages of the iteration, then the
 // smallest eigenpair of every bin's pencil (V, Cx) in place of the update (kernels_five_batch.hip, which reads the table).
+// Batched IP2 (oiva_batch_ip2_*) runs on a batch of either entry with any K <= M: the float64 stages on a complex128 copy of X, then
+// the pairwise update of kernels_ip2_batch.hip in place of the IP1 update.
 // The PCA front end of auxiva_pca_batch (oiva_batch_set_w_pca,
 // _project_dev, _compose_w; kernels_pca_batch.hip) reads the table on the device for every batch.
 // A batch of either entry put into the complex128 data path (oiva_batch_set_data_c128, before X is set) holds X as complex128 and
@@ -41,6 +43,7 @@ constexpr int kIlrmaMaxComponents = 16;
 constexpr int kIlrmaStages = OIVA_ILRMA_STAGE_NORMALISE + 1;
 constexpr int kIssStages = OIVA_ISS_STAGE_SWEEP + 1;
 constexpr int kFiveStages = OIVA_FIVE_STAGE_UPDATE + 1;
+constexpr int kIp2Stages = OIVA_IP2_STAGE_UPDATE + 1;
 
 // geometry of the frame-split passes of a problem of T frames: a function of T alone (never of B or of other problems), so a
 // problem gets the same bits whatever batch it is in
@@ -125,6 +128,12 @@ struct oiva_batch {
     double2* five_x128 = nullptr;  // (sum T_b, F, M): X widened to complex128, what the float64 stages of FIVE stream (with
                                    // Ppart64, Rw64 and Gs64, which a complex64 batch does not hold otherwise)
     bool five_ready = false;
+    // batched IP2: what its float64 stages stream and leave, allocated by the first oiva_batch_ip2_* call
+    double2* ip2_x128 = nullptr;   // (sum T_b, F, M): X widened to complex128
+    double* ip2_ppart = nullptr;   // room b's [nb][T_b][K] at probs[b].p_off (doubles)
+    double* ip2_rw = nullptr;      // (sum T_b, K): r, then the weights 1 / max(r / gamma, eps)
+    double* ip2_gs = nullptr;      // [B][rblocks][K]: sums of r over blocks of kBlock frames
+    bool ip2_ready = false;        // ip2_x128 holds the X that is set
 };
 
 namespace {
@@ -284,6 +293,7 @@ int install_x(oiva_batch* b, const void* X) {
     b->have_cx = false;
     b->iss_ready = false;          // (its partial powers are of the old X)
     b->five_ready = false;         // (its reduction is of the old Cx)
+    b->ip2_ready = false;          // (its complex128 copy is of the old X)
     return OIVA_OK;
 }
 
@@ -432,6 +442,54 @@ int check_five(oiva_batch* b, bool begun) {
     const int rc = check_ready(b);
     if (rc) return rc;
     if (begun) OIVA_NEED(b->five_ready, OIVA_ERR_STATE, "call oiva_batch_five_begin first");
+    return OIVA_OK;
+}
+
+// one stage of an IP2 iteration (OIVA_IP2_STAGE_*): the float64 stages 0 to 2 of stage() (the complex128 data path's, from the
+// problem table) on the widened X, whose activation applies the scale of W in float64; then the schedule of `iteration`
+int ip2_stage(oiva_batch* b, int s, int iteration) {
+    if (s == OIVA_IP2_STAGE_POWER) {
+        OIVA_TRY_HIP(launch_c128_power(b->stream, b->ip2_x128, b->What64, b->ip2_ppart, b->probs_dev, b->B, b->T, b->F, b->M, b->K));
+    } else if (s == OIVA_IP2_STAGE_ACTIVATION) {
+        OIVA_TRY_HIP(launch_c128_activation(b->stream, b->ip2_ppart, b->ip2_rw, b->ip2_gs, b->What64, b->What, b->probs_dev, b->B, b->T,
+                                            b->F, b->M, b->K, b->model, b->rblocks));
+    } else if (s == OIVA_IP2_STAGE_COV) {
+        OIVA_TRY_HIP(launch_c128_cov(b->stream, b->ip2_x128, b->ip2_rw, b->probs_dev, b->Vpart, b->B, b->F, b->M, b->K, b->nsplit));
+    } else {
+        UpdateArgs a = update_args(b, false);
+        a.wscale = nullptr;                  // (applied by the activation)
+        a.ragged = b->probs_dev;             // every room's own T and splits, dense batch or not
+        OIVA_TRY_HIP(launch_ip2_update(b->stream, a, iteration));
+    }
+    return OIVA_OK;
+}
+
+// the arguments and the state every oiva_batch_ip2_* entry needs; forms the complex128 copy of X on first use
+int prepare_ip2(oiva_batch* b) {
+    OIVA_NEED(b != nullptr, OIVA_ERR_ARG, "null batch");
+    OIVA_NEED(!b->c128, OIVA_ERR_ARG, "IP2 is not supported on a complex128 batch");
+    const int rc = check_ready(b);
+    if (rc) return rc;
+    if (b->ip2_ready) return OIVA_OK;
+    DeviceGuard guard(b->device);
+    const size_t nx = b->frames_total * b->F * b->M;
+    if (!b->ip2_x128) {                  // (the last of the state: all of it or none)
+        DeviceArena& mem = b->mem;
+        const size_t before = mem.mark();
+        size_t p_doubles = 0;
+        for (const RaggedProblem& d : b->probs) p_doubles = std::max(p_doubles, d.p_off + (size_t)b->nb * d.T * b->K);
+        mem.take(&b->ip2_ppart, p_doubles * sizeof(double));
+        mem.take(&b->ip2_rw, b->frames_total * b->K * sizeof(double));
+        mem.take(&b->ip2_gs, (size_t)b->B * b->rblocks * b->K * sizeof(double));
+        mem.take(&b->ip2_x128, nx * sizeof(double2));
+        if (!mem.ok()) {
+            mem.release_to(before);
+            b->ip2_ppart = b->ip2_rw = b->ip2_gs = nullptr, b->ip2_x128 = nullptr;
+            return fail_with(OIVA_ERR_HIP, std::string("allocation failed: ") + hipGetErrorString(mem.status()));
+        }
+    }
+    OIVA_TRY_HIP(launch_cast_c64_to_c128(b->stream, b->X, b->ip2_x128, (long long)nx));
+    b->ip2_ready = true;
     return OIVA_OK;
 }
 
@@ -1201,6 +1259,44 @@ oiva_status oiva_batch_five_get_reduction(oiva_batch* b, void* Li) {
     DeviceGuard guard(b->device);
     OIVA_TRY_HIP(hipStreamSynchronize(b->stream));
     OIVA_TRY_HIP(hipMemcpy(Li, b->five_li, nbins(b) * b->M * b->M * sizeof(double2), hipMemcpyDeviceToHost));
+    return OIVA_OK;
+}
+
+// ---- batched IP2 (one room per batch entry of either kind, any K <= M, eager launches) ---------------------------------
+oiva_status oiva_batch_ip2_stage(oiva_batch* b, int stage, int iteration) {
+    const int rc = prepare_ip2(b);
+    if (rc) return rc;
+    OIVA_NEED(stage >= 0 && stage < kIp2Stages, OIVA_ERR_ARG, "unknown IP2 stage");
+    OIVA_NEED(iteration >= 0, OIVA_ERR_ARG, "iteration must be >= 0");
+    DeviceGuard guard(b->device);
+    return ip2_stage(b, stage, iteration);
+}
+
+oiva_status oiva_batch_ip2_iterate(oiva_batch* b, int first_iteration, int n) {
+    int rc = prepare_ip2(b);
+    if (rc) return rc;
+    OIVA_NEED(first_iteration >= 0 && n >= 0, OIVA_ERR_ARG, "first_iteration and n must be >= 0");
+    DeviceGuard guard(b->device);
+    for (int e = 0; e < n; ++e)
+        for (int s = 0; s < kIp2Stages; ++s)
+            if ((rc = ip2_stage(b, s, first_iteration + e))) return rc;
+    return OIVA_OK;
+}
+
+oiva_status oiva_batch_ip2_time_stages(oiva_batch* b, int n, float* per_stage_ms) {
+    int rc = prepare_ip2(b);
+    if (rc) return rc;
+    OIVA_NEED(n >= 1 && per_stage_ms, OIVA_ERR_ARG, "n must be >= 1");
+    DeviceGuard guard(b->device);
+    double acc[kIp2Stages] = {};
+    for (int e = 0; e < n; ++e) {
+        for (int s = 0; s < kIp2Stages; ++s) {
+            float ms = 0.f;
+            if ((rc = b->stream.elapsed_ms(0, 1, [&] { return ip2_stage(b, s, e); }, &ms))) return rc;
+            acc[s] += ms;
+        }
+    }
+    for (int s = 0; s < kIp2Stages; ++s) per_stage_ms[s] = (float)(acc[s] / n);
     return OIVA_OK;
 }
 

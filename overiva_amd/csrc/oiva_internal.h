@@ -432,6 +432,12 @@ hipError_t launch_five_begin(hipStream_t s, const double* Cx, double2* Li, int n
 hipError_t launch_five_update(hipStream_t s, const double* Vpart, const double2* Li, double2* What64, float2* What,
                               const RaggedProblem* prob, int nbins, int F, int M);
 
+// The per-bin update of batched IP2 (kernels_ip2_batch.hip, batch.hip): the schedule of iteration `iteration`
+// (pair steps and at most two single IP1 steps, J after every step when K < M) for every bin of the batch in one launch, float64.
+// a: What, What64, Cx, Vpart (float64 partials), F = all bins, M <= 8, K, wscale_bins = bins per room, ragged = the problem table
+// or nullptr with T and nsplit; wscale is not read.
+hipError_t launch_ip2_update(hipStream_t s, const UpdateArgs& a, int iteration);
+
 // The batched STFT (kernels_bstft.hip, bstft.hip): the passes around hipFFT for B rooms at once.  One record per room; a dense
 // batch is the special case of equal records.
 struct BstftRoom {

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib, sharded
 from . import batch as _batch
+from . import ip2 as _ip2
 from . import iss as _iss
 from . import ive as _ive
 from . import pca_batch as _pca_batch
@@ -172,8 +173,8 @@ def _check_separate_args(x, frame, hop, n_src, n_iter, algorithm, model, win_a, 
         dtype, M, lens = rooms.dtype, rooms.shape[2], [rooms.shape[1]] * rooms.shape[0]
     if dtype.kind not in "fiu":
         raise ValueError(f"x must be real, got dtype {dtype}")
-    if algorithm not in ("overiva", "ogive", "auxiva_pca", "auxiva_iss", "five"):
-        raise ValueError(f"algorithm must be 'overiva', 'ogive', 'auxiva_pca', 'auxiva_iss' or 'five', got {algorithm!r}")
+    if algorithm not in ("overiva", "ogive", "auxiva_pca", "auxiva_iss", "five", "overiva_ip2"):
+        raise ValueError(f"algorithm must be 'overiva', 'ogive', 'auxiva_pca', 'auxiva_iss', 'five' or 'overiva_ip2', got {algorithm!r}")
     if algorithm == "ogive" and ragged:
         raise ValueError("OGIVE does not run on a ragged batch: give algorithm='ogive' rooms of one length as a (B, n_samples, M) array")
     if algorithm != "ogive" and algo_kwargs:
@@ -222,7 +223,7 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
                    init_eig=False, W0=None, proj_back=True, return_filters=False, **algo_kwargs):
     """
     Audio in, audio out for B rooms: STFT, ``overiva_batch`` / ``overiva_batch_ragged`` / ``ogive_batch`` / ``auxiva_pca_batch`` /
-    ``auxiva_iss_batch`` / ``five_batch`` and inverse STFT with X and Y never leaving the device (the chain of reference overiva_sim.py:206-207, 298-315 for many rooms per call).
+    ``auxiva_iss_batch`` / ``five_batch`` / ``overiva_ip2_batch`` and inverse STFT with X and Y never leaving the device (the chain of reference overiva_sim.py:206-207, 298-315 for many rooms per call).
 
     Parameters
     ----------
@@ -232,7 +233,7 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
         STFT frame length (even) and shift (default frame // 2); n_frames = n_samples // hop as ``stft.analysis``
     n_src, n_iter, model, init_eig, W0, proj_back, return_filters:
         as ``overiva_batch()`` (``n_src=None``: determined AuxIVA)
-    algorithm: "overiva", "auxiva_iss" (determined AuxIVA by rank-1 ISS updates, as ``auxiva_iss_batch()``: ``n_src`` None or
+    algorithm: "overiva", "overiva_ip2" (the same with pairwise IP2 updates, as ``overiva_ip2_batch()``), "auxiva_iss" (determined AuxIVA by rank-1 ISS updates, as ``auxiva_iss_batch()``: ``n_src`` None or
         n_chan), "five" (one source by FIVE, as ``five_batch()``: ``n_src`` None or 1; rooms of any lengths), "ogive" (one
         source, rooms of one length; ``step_size``, ``tol``, ``update`` as ``ogive_batch()``) or
         "auxiva_pca" (PCA to ``n_src`` channels, then determined AuxIVA, as ``auxiva_pca_batch()``: ``W0`` starts the reduced
@@ -267,6 +268,9 @@ def separate_batch(x, frame, hop=None, n_src=None, n_iter=20, algorithm="overiva
             elif algorithm == "five":
                 run_five(plan, n_iter, W0, init_eig)
                 info.update(algorithm="five")
+            elif algorithm == "overiva_ip2":
+                _ip2.run_ip2(plan, n_iter, W0, init_eig)
+                info.update(algorithm="overiva_ip2")
             else:
                 if W0 is None and init_eig:
                     plan.set_w_eig()

@@ -36,9 +36,11 @@ from .overiva import get_device
 
 MAX_MICS = _batch.MAX_CHANNELS
 MAX_TARGETS = _metrics.MAX_SOURCES - 1
-ALGOS = ("auxiva", "overiva", "auxiva_pca", "ogive")
-OVERDET_ALGOS = ("overiva", "ogive", "auxiva_pca")
-_DEFAULT_N_ITER = {"auxiva": 20, "overiva": 20, "auxiva_pca": 20, "ogive": 4000}
+ALGOS = ("auxiva", "overiva", "auxiva_pca", "ogive", "auxiva_ip2", "overiva_ip2")
+OVERDET_ALGOS = ("overiva", "ogive", "auxiva_pca", "overiva_ip2")
+_DEFAULT_N_ITER = {"auxiva": 20, "overiva": 20, "auxiva_pca": 20, "ogive": 4000, "auxiva_ip2": 20, "overiva_ip2": 20}
+_DETERMINED = ("auxiva", "auxiva_ip2")       # run on all the channels, whatever n_targets
+_IP2 = ("auxiva_ip2", "overiva_ip2")         # the pairwise update (ip2.py) with the keys and the cadence of "auxiva" / "overiva"
 _SOLVER_KEYS = {"n_iter", "proj_back", "model", "init_eig", "W0"}
 _OGIVE_KEYS = {"step_size", "tol", "update"}
 
@@ -47,7 +49,7 @@ def checkpoints(algo, n_iter, monitor_convergence=False):
     """the iteration counts at which ``sweep_batch`` evaluates an entry.  Without monitoring: ``[0, n_iter]``, the entry at 0
     being the shared evaluation of the unprocessed microphones (``overiva_sim.py:240-243, 289-290``).  With monitoring the
     callback cadence of the solver and then its final state (``:272-284, 323-332``): epochs 0, 10, 20, ... below ``n_iter`` for
-    "auxiva" and "overiva"; 0, 100, 200, ... for "ogive" -- the list when no group of rooms stops early: the cadence ends once every
+    "auxiva" and "overiva" (and their IP2 forms "auxiva_ip2" and "overiva_ip2"); 0, 100, 200, ... for "ogive" -- the list when no group of rooms stops early: the cadence ends once every
     room's stopping rule has fired.  "auxiva_pca" is evaluated at its ends only, ``[0, n_iter]`` with the shared initial
     evaluation at 0, monitored or not: its iterations run on the reduced channels and composing the filters consumes the PCA
     basis, so there is no state to look at in between."""
@@ -86,16 +88,16 @@ def _check_algorithms(algorithms, n_targets, lens, M, frame, hop, win_a, win_s, 
         if (algo == "auxiva_pca" and n_targets == 1) or (algo == "ogive" and n_targets != 1):      # overiva_sim.py:250-255
             continue
         n_iter = kwargs.get("n_iter", _DEFAULT_N_ITER[algo])
-        n_src = {"auxiva": None, "ogive": None}.get(algo, n_targets)
+        n_src = None if algo in _DETERMINED or algo == "ogive" else n_targets
         if algo == "ogive" and not dense:
             raise ValueError(f"algorithms[{name!r}]: OGIVE needs rooms of one output length")
-        solver = "overiva" if algo == "auxiva" else algo
+        solver = "overiva_ip2" if algo in _IP2 else "overiva" if algo == "auxiva" else algo
         try:
             _separate._check_separate_args(audio, frame, hop, n_src, n_iter, solver, kwargs.get("model", "laplace"), win_a, win_s,
                                            kwargs.get("W0"), {k: kwargs[k] for k in _OGIVE_KEYS if k in kwargs})
         except ValueError as e:
             raise ValueError(f"algorithms[{name!r}]: {e}") from None
-        entries.append(dict(name=name, algo=algo, n_src=M if algo == "auxiva" else 1 if algo == "ogive" else n_targets,
+        entries.append(dict(name=name, algo=algo, n_src=M if algo in _DETERMINED else 1 if algo == "ogive" else n_targets,
                             n_iter=int(n_iter), proj_back=bool(kwargs.get("proj_back", True)) or algo == "auxiva_pca",
                             model=kwargs.get("model", "laplace"), init_eig=bool(kwargs.get("init_eig", False)), W0=kwargs.get("W0"),
                             ogive={k: kwargs[k] for k in _OGIVE_KEYS if k in kwargs}, reorder=algo not in overdet_algos))
@@ -404,7 +406,10 @@ def _run_entry(sb, Xd, entry, monitor, init):
                 if watched and epoch % 10 == 0:
                     look(epoch)
                 step = min(n_iter - epoch, 10 - epoch % 10) if watched else n_iter - epoch
-                plan.iterate(step)
+                if algo in _IP2:
+                    plan.ip2_iterate(epoch, step)
+                else:
+                    plan.iterate(step)
                 epoch += step
         look(n_iter)
     for at, res in zip(gathered, sb.evaluate_sets(len(gathered))):
@@ -443,9 +448,10 @@ def sweep_batch(signals, room_dim, sources, mics, frame, hop=None, algorithms=No
     signals, room_dim, sources, mics, fs, max_order, absorption, c, rir_length, sinr, snr, ref_mic, sources_var, noise:
         as ``simulate_batch()``; 1..8 microphones; ``n_targets`` in 1..min(n_mics, 7)
     frame, hop, win_a, win_s: as ``separate_batch()``
-    algorithms: dict ``{full_name: {"algo": "auxiva" | "overiva" | "auxiva_pca" | "ogive", "kwargs": {...}}}``, the reference's
+    algorithms: dict ``{full_name: {"algo": "auxiva" | "overiva" | "auxiva_pca" | "ogive" | "auxiva_ip2" | "overiva_ip2", "kwargs": {...}}}``, the reference's
         ``algorithm_kwargs`` block as it stands (default: one "overiva" entry with ``n_iter=20``).  "auxiva" is ``overiva`` without
-        ``n_src``; "overiva" and "auxiva_pca" get ``n_src=n_targets``.  kwargs: ``n_iter``, ``proj_back``, ``model``,
+        ``n_src``; "overiva" and "auxiva_pca" get ``n_src=n_targets``; "auxiva_ip2" and "overiva_ip2" are "auxiva" and "overiva" with
+        pairwise IP2 updates (``overiva_ip2_batch``), the same kwargs and checkpoints.  kwargs: ``n_iter``, ``proj_back``, ``model``,
         ``init_eig``, ``W0`` and, for "ogive", ``step_size``, ``tol``, ``update``.  Skipped as the reference skips them:
         "auxiva_pca" with one target, "ogive" with more than one.  "ilrma" is refused.  "ogive" needs rooms of one output length.
     filler: (batch, >= m_b) or a sequence of 1-D arrays: the row that is held against the background (``overiva_sim.py:200``);

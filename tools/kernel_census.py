@@ -9,6 +9,8 @@ namespaces stripped, the argument list dropped.
                                                             # process of the run, OUT_DIR/<pid>.names.txt (the CSV files stay there)
     python tools/kernel_census.py probe setup|eager|graph|child   # the trust check's four small traced programs (below)
     python tools/kernel_census.py write NAMES_ROOT [--parent PARENT_NAMES_ROOT] [--deleted FILE]   # -> tests/golden/kernel_census.json
+    python tools/kernel_census.py amend NAMES_ROOT [--base RECORD] [--out NEW_RECORD]   # the record plus the traced runs of NEW test
+                                                            # files and the NEW kernels; refuses when anything recorded has changed (below)
     python tools/kernel_census.py table                     # the per-family table of DESIGN.md from the recorded file
 
 NAMES_ROOT holds one directory per traced run: ``tests__<file>.py`` for a test file, ``probe_<mode>`` for a probe.
@@ -20,6 +22,14 @@ only.  The kernels of ``eager`` that ``setup`` does not have run, in ``graph``, 
 them there.  ``child`` touches no device itself and starts one child process that runs ``eager``: the trace must show the child's
 kernels.  Per test file the census also names the kernels that only a child process of that file's run launched.  A file whose
 trace cannot be trusted is recorded ``"traced": false`` with the reason, and its kernels are left out of the never-launched list.
+
+``amend`` is for a change that only ADDS kernels and the test files that launch them.  It is valid when every recorded kernel is
+still compiled under the same name from the same source file (it refuses otherwise: record the census again), and NAMES_ROOT
+holds the traced runs of new test files only (a recorded file is refused).  It adds the ``files`` entries of those runs, the
+kernels the build compiles and the census lacks, and the new files to the ``tests`` of every kernel they launched; nothing that
+was recorded is removed or rewritten, and the recorded trust check stands for the new runs (same tracer, same kind of run).
+A committed record stays as it is: the amended one goes to a new file (``--out tests/golden/kernel_census_N.json``) and ``CENSUS``
+below is pointed at it, which is what tests/test_kernel_census.py then reads.
 """
 import argparse
 import csv
@@ -34,7 +44,10 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
-CENSUS = os.path.join(REPO, "tests", "golden", "kernel_census.json")
+# A record, once committed, is not rewritten: ``amend`` reads the current record and writes the next one, a new file, and CENSUS
+# names the current one.  kernel_census.json is the first full recording; _2 adds the kernels of kernels_ip2_batch.hip.
+CENSUS_FIRST = os.path.join(REPO, "tests", "golden", "kernel_census.json")
+CENSUS = os.path.join(REPO, "tests", "golden", "kernel_census_2.json")
 PROBES = ("setup", "eager", "graph", "child")
 # the test files whose traced run must show kernels of a child process (they start children that run kernels)
 CHILD_FILES = ("tests/test_demix_io_gpu.py", "tests/test_update16r_gpu.py")
@@ -262,6 +275,45 @@ def write(names_root, parent_root=None, out=CENSUS, deleted=()):
     return doc
 
 
+def amend(names_root, base=CENSUS, out=CENSUS):
+    """the record ``base`` plus the traced runs of new test files and the kernels the build has gained, written to ``out``"""
+    with open(base) as f:
+        doc = json.load(f)
+    src = compiled_sources()
+    moved = sorted(k for k, v in doc["kernels"].items() if src.get(k) != v["source"])
+    if moved:
+        sys.exit(f"amend refused: {len(moved)} recorded kernel(s) are no longer compiled under their name from their source file "
+                 f"(e.g. {moved[:3]}): record the census again")
+    runs = {os.path.basename(d): load_names(d) for d in sorted(glob.glob(os.path.join(names_root, "*"))) if os.path.isdir(d)}
+    runs = {_run_file(r): v for r, v in runs.items() if _run_file(r) is not None}
+    if not runs:
+        sys.exit(f"amend refused: no tests__<file>.py run under {names_root}")
+    known = sorted(f for f in runs if f in doc["files"])
+    if known:
+        sys.exit(f"amend refused: {known} are recorded already: amend takes the runs of new test files only")
+    if not doc["trust_check"]["graph_replay"]["seen"]:
+        sys.exit("amend refused: the recorded trust check did not see the kernels of a replayed graph: record the census again")
+    added = sorted(set(src) - set(doc["kernels"]))
+    for k in added:
+        doc["kernels"][k] = {"source": src[k], "tests": []}
+    for f, per_pid in sorted(runs.items()):
+        if not os.path.exists(os.path.join(REPO, f)):
+            sys.exit(f"amend refused: {f} does not exist")
+        doc["files"][f] = {"traced": True, "processes": len(per_pid)}
+        for n in set().union(*per_pid.values()) if per_pid else ():
+            if n in doc["kernels"] and f not in doc["kernels"][n]["tests"]:
+                doc["kernels"][n]["tests"] = sorted(doc["kernels"][n]["tests"] + [f])
+    doc["kernels"] = dict(sorted(doc["kernels"].items()))
+    never = [k for k in added if not doc["kernels"][k]["tests"]]
+    if never:
+        sys.exit(f"amend refused: no new test file launched {never}: test them or delete them")
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=0, sort_keys=False)
+        f.write("\n")
+    print(json.dumps({"tool": "kernel_census amend", "out": out, "files_added": sorted(runs), "kernels_added": added}))
+    return doc
+
+
 def table(path=CENSUS):
     """the per-family rows of DESIGN.md: compiled, launched by the parent's suite, launched by this suite"""
     with open(path) as f:
@@ -299,6 +351,10 @@ def main():
     a.add_argument("--parent")
     a.add_argument("--out", default=CENSUS)
     a.add_argument("--deleted", help="a file of kernel names, one per line: instantiations of the parent build that are no longer compiled")
+    a = sub.add_parser("amend")
+    a.add_argument("names_root")
+    a.add_argument("--base", default=CENSUS, help="the record to amend (default: the current one)")
+    a.add_argument("--out", default=CENSUS, help="where the amended record goes: a new file when --base is committed already")
     a = sub.add_parser("table")
     a = sub.add_parser("never")
     args = ap.parse_args()
@@ -309,6 +365,8 @@ def main():
     elif args.cmd == "write":
         deleted = [l.strip() for l in open(args.deleted) if l.strip()] if args.deleted else ()
         write(args.names_root, args.parent, args.out, deleted)
+    elif args.cmd == "amend":
+        amend(args.names_root, args.base, args.out)
     elif args.cmd == "table":
         print(table())
     elif args.cmd == "never":
